@@ -15,7 +15,8 @@ reported (copy-engine peer copies into rank 0's IPC-mapped ring; the kernels' ow
 
 Rank 0's LAST stdout line is ONE compact JSON object (< 4 KB: the contract's keys, a flat `roofline`, `cpu_baseline`, one
 or two scalars per leg); the FULL result -- everything below -- goes to `bench_full.json` in the current directory
-(--full-json PATH) and, as one line, to stderr.  At N = 1 the same run also measures
+(--full-json PATH) and, as one line, to stderr.  --dump-outputs DIR also writes the label maps of the last timed step to DIR
+(dump_outputs), so that two builds can be compared output for output.  At N = 1 the same run also measures
   * `cfg2_single_frame` (ONE 848x480 frame per launch), `cfg3_layered_run` (LayeredDecisionForest.run),
   * `cfg5_shard` (config 5's per-GPU shard: 32 dense 1280x720 frames, 8 trees of depth 22, two frames checked against
     the oracle inside the run),
@@ -30,6 +31,7 @@ or two scalars per leg); the FULL result -- everything below -- goes to `bench_f
 """
 import argparse
 import contextlib
+import hashlib
 import importlib
 import json
 import os
@@ -43,7 +45,15 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-CACHE = os.environ.get("RDF_BENCH_CACHE", "/tmp/rdf_bench_cache")
+
+def _synth_digest():
+    with open(os.path.join(ROOT, "3d-beats_amd", "synth.py"), "rb") as f:
+        return hashlib.sha256(f.read()).hexdigest()[:16]
+
+
+# one directory per version of the input generator: a cache written by another version is never read, so the same arguments
+# give the same inputs from run to run
+CACHE = os.path.join(os.environ.get("RDF_BENCH_CACHE", "/tmp/rdf_bench_cache"), "synth_" + _synth_digest())
 
 
 def parse():
@@ -109,7 +119,15 @@ def parse():
                     "default: bench_full.json in the current directory.  The last stdout line is the compact summary of it (< 4 KB)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend at N>1 (nccl = RCCL; gloo only to "
                     "rehearse the control flow with several ranks on one GPU)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write the label maps the timed "
+                    "path's last step produced (rank 0: every rank's, as gathered) to DIR as float32 / float64 .npy files, "
+                    f"{DUMP_LIMIT // 10 ** 6} MB at most: see dump_outputs")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return a
 
 
 class Events:
@@ -166,6 +184,43 @@ def cached(name, make):
     except Exception:
         pass
     return arr
+
+
+DUMP_LIMIT = 64 * 10 ** 6  # bytes of every file --dump-outputs writes, together
+DUMP_SEED = 20211003       # which frames (or pixels) the dump samples when the label maps do not fit
+
+
+def dump_outputs(path, labels_np, classes):
+    """--dump-outputs: the label maps [frames, h, w] (uint16 class ids, 65535 = not classified) the timed path's last step
+    handed its caller, for comparing two builds output for output.  Written to `path`:
+      labels.npy        float32: every frame, or a seeded sample of whole frames that fits the budget (of pixels, if not one
+                        frame does)
+      labels_index.npy  float64: the batch index of each frame in labels.npy (flat pixel indices when it holds pixels)
+      label_counts.npy  float64 [frames, classes + 2]: pixels per class of EVERY frame, then 65535, then any other value
+    Returns {"dir", "files": {name: shape}, "bytes"} for the result line."""
+    os.makedirs(path, exist_ok=True)
+    n, h, w = labels_np.shape
+
+    def frame_counts(lab):
+        ids = np.where(lab < classes, lab, np.where(lab == 65535, classes, classes + 1)).astype(np.int64)
+        return np.bincount(ids.ravel(), minlength=classes + 2)
+    counts = np.stack([frame_counts(labels_np[i]) for i in range(n)]).astype(np.float64)
+    budget = DUMP_LIMIT - counts.nbytes - 65536        # (room for the .npy headers)
+    rng = np.random.default_rng(DUMP_SEED)
+    k = min(n, budget // (h * w * 4 + 8))
+    if k >= 1:
+        index = np.arange(n) if k == n else np.sort(rng.choice(n, size=k, replace=False))
+        sample = labels_np[index]
+    else:
+        index = np.sort(rng.choice(labels_np.size, size=budget // (4 + 8), replace=False))
+        sample = labels_np.reshape(-1)[index]
+    files = {"labels": sample.astype(np.float32), "labels_index": index.astype(np.float64), "label_counts": counts}
+    total = 0
+    for name, arr in files.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+        total += os.path.getsize(os.path.join(path, name + ".npy"))
+    assert total <= DUMP_LIMIT, total
+    return {"dir": os.path.abspath(path), "files": {name: list(arr.shape) for name, arr in files.items()}, "bytes": total}
 
 
 COMMITTED_COUNTERS = ("r06_roofline_counters.json", "r05_roofline_counters.json", "r04_roofline_counters.json")     # newest first
@@ -949,8 +1004,17 @@ def main():
         else:
             primary = min(intact, key=lambda n: results[n]["elapsed"])
     elapsed, kern_ms = results[primary]["elapsed"], results[primary]["kern_ms"]
+    dumped = None
     if not multi:
-        assert np.array_equal(labels.get(), scratch.get()), "timed path and stats path disagree"
+        last_labels = labels.get()
+        assert np.array_equal(last_labels, scratch.get()), "timed path and stats path disagree"
+        if a.dump_outputs:
+            dumped = dump_outputs(a.dump_outputs, last_labels, C)
+        del last_labels
+    elif a.dump_outputs and rank == 0:
+        # every rank's label maps of the last step, as rank 0 received them from the transport `value` is of
+        got = modes[primary][4]()
+        dumped = dump_outputs(a.dump_outputs, got.get() if hasattr(got, "get") else got.cpu().numpy().view(np.uint16), C)
 
     # ---- the kernel alone on every rank (no gather enqueued): Mpix/s with and without the gather, SURVEY 8(e) ----
     kern_only = None
@@ -1013,6 +1077,8 @@ def main():
         "value_valid_pixels": round(out_value_tmp * valid_px / (F * H * W), 2),
         "valid_pixel_share": round(valid_px / (F * H * W), 4),
     }
+    if dumped:
+        out["dump_outputs"] = dumped
     if multi:
         # what a driver needs to verify the run: N ranks of ONE RCCL communicator on N distinct devices
         uuid = str(getattr(torch.cuda.get_device_properties(dev_index), "uuid", f"index-{dev_index}"))

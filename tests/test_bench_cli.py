@@ -8,6 +8,7 @@ import subprocess
 import sys
 import time
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -336,3 +337,89 @@ def test_compact_line_of_a_full_result_stays_under_four_kilobytes():
                                                             "split_step_helper_workgroups": 96}}
     c68 = bench.compact_line(full6, "x.json")
     assert len(json.dumps(c68)) < LINE_LIMIT and c68["distributed"]["gather_modes"]["rccl gather"]["split_step_helper_workgroups"] == 96
+
+
+def _oracle_labels(oracle, synth, n_frames, first_idx, depth, h=480, w=848):
+    """The label maps bench.py's headline batch must produce: the same seeded frames and forest, through the CPU oracle."""
+    want = np.full((n_frames, h, w), 65535, np.uint16)
+    oracle.eval_forest(synth.mixed_batch(n_frames, first_idx=first_idx, h=h, w=w), synth.forest(4, depth, 4, "full"), want)
+    return want
+
+
+def _load_dump(path):
+    got = {n: np.load(os.path.join(path, n + ".npy")) for n in ("labels", "labels_index", "label_counts")}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(os.path.getsize(os.path.join(path, n + ".npy")) for n in got) <= 64 * 10 ** 6
+    return got
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_timed_steps_labels_and_repeat_from_run_to_run(rdf, oracle, tmp_path):
+    """--dump-outputs DIR: the label maps of the timed path's last step, float32, under 64 MB; two runs with the same arguments
+    (each generating its inputs afresh) dump the same arrays, which are the oracle's labels of the same seeded frames; --steps
+    is the number of timed steps and ms_per_step their time."""
+    runs = []
+    for i in range(2):
+        env = dict(os.environ, RDF_BENCH_CACHE=str(tmp_path / f"cache{i}"))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--frames", "8",
+                            "--depth", "12", "--headline-only", "--dump-outputs", str(tmp_path / f"dump{i}"),
+                            "--full-json", str(tmp_path / f"full{i}.json")], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        c = _last_json(r.stdout)
+        _check_contract(c)
+        d = _full(c, tmp_path / f"full{i}.json")
+        assert d["steps"] == 4 and c["steps"] == 4 and c["ms_per_step"] > 0
+        assert d["dump_outputs"]["files"]["labels"] == [8, 480, 848] and d["dump_outputs"]["bytes"] <= 64 * 10 ** 6
+        runs.append(_load_dump(tmp_path / f"dump{i}"))
+    for name in runs[0]:
+        assert np.array_equal(runs[0][name], runs[1][name]), name
+    want = _oracle_labels(oracle, rdf.synth, 8, 0, 12)
+    assert runs[0]["labels_index"].tolist() == list(range(8))
+    assert np.array_equal(runs[0]["labels"], want.astype(np.float32))
+    assert runs[0]["label_counts"].sum() == want.size and runs[0]["label_counts"][:, 5].sum() == 0
+
+
+@pytest.mark.gpu
+def test_two_ranks_dump_every_ranks_labels_as_rank_zero_received_them(rdf, oracle, tmp_path):
+    """At N > 1 rank 0 dumps the gathered label maps of the last step: rank r's frames follow rank r-1's."""
+    env = dict(os.environ, RDF_BENCH_CACHE=str(tmp_path), HSA_ENABLE_IPC_MODE_LEGACY="0")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+           "--frames", "4", "--depth", "12", "--backend", "gloo", "--gather", "rccl", "--reserve-cus", "0", "--no-cfg5",
+           "--dump-outputs", str(tmp_path / "dump"), "--full-json", str(tmp_path / "full.json")]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    c = _last_json(r.stdout)
+    assert c["config"]["gather"] == "rccl gather" and c["config"]["gather_check"] == "ok"
+    got = _load_dump(tmp_path / "dump")
+    want = np.concatenate([_oracle_labels(oracle, rdf.synth, 4, 4 * g, 12) for g in range(2)])
+    assert np.array_equal(got["labels"], want.astype(np.float32)) and got["labels_index"].tolist() == list(range(8))
+
+
+def test_dump_outputs_samples_within_the_budget(tmp_path):
+    """No GPU needed: bench.dump_outputs keeps every file together under 64 MB -- all frames when they fit, a seeded sample of
+    whole frames when they do not, of pixels when not even one frame does -- the same sample every time, and the per-frame
+    class counts cover every pixel."""
+    bench = _bench_module()
+    rng = np.random.default_rng(1)
+    for shape, frames in (((6, 48, 64), 6), ((60, 480, 848), None), ((1, 4200, 4200), 0)):
+        lab = rng.integers(0, 4, size=shape).astype(np.uint16)
+        lab[:, :2] = 65535
+        lab[0, 2, :3] = 9
+        dumps = []
+        for sub in ("a", "b"):
+            path = tmp_path / f"{shape[0]}_{sub}"
+            assert bench.dump_outputs(str(path), lab, 4)["bytes"] <= 64 * 10 ** 6
+            dumps.append(_load_dump(path))
+        a, b = dumps
+        for name in a:
+            assert np.array_equal(a[name], b[name]), name
+        idx = a["labels_index"].astype(np.int64)
+        if frames == 0:
+            assert a["labels"].ndim == 1 and np.array_equal(a["labels"], lab.reshape(-1)[idx])
+        else:
+            assert np.array_equal(a["labels"], lab[idx])
+            assert len(idx) == frames if frames else 1 <= len(idx) < shape[0]
+        counts = a["label_counts"]
+        assert counts.shape == (shape[0], 6) and counts.sum() == lab.size
+        assert counts[:, 4].sum() == (lab == 65535).sum() and counts[0, 5] == 3

@@ -51,7 +51,9 @@ def _worker(rank, world, port, n_chunks, tmpdir):
         else:
             for _ in range(2):
                 sh.step(depth, labels, prefill=65535)
-        dist.barrier()
+        # gloo's own barrier: dist.barrier() first asks torch for the machine's accelerator, which starts the HIP runtime and
+        # opens the GPU in every one of these CPU-only ranks
+        dist.monitored_barrier()
         if rank == 0:
             got = sh.result().get()
             assert got.shape == (world * frames, h // r, w // r)
