@@ -14,6 +14,7 @@ from .decision_tree import (DecisionForest, DecisionTree, DecisionTreeEvaluator,
                             DecisionTreeTrainer, LayeredDecisionForest)
 from .device import DeviceArray, HipRuntime, device_ptr, get_runtime, host_mapped_array, set_runtime, to_device  # noqa: F401
 from .engine.buffer import GpuBuffer  # noqa: F401
+from .grouping import HandGrouping  # noqa: F401
 from .host_stream import HostFramesEvaluator  # noqa: F401
 from .pipeline import HandPipeline  # noqa: F401
 from .util import MAX_UINT16  # noqa: F401
@@ -44,6 +45,6 @@ def install_reference_aliases(force=False):
 
 
 __all__ = ["DecisionTree", "DecisionForest", "LayeredDecisionForest", "DecisionTreeEvaluator", "DecisionTreeTrainer",
-           "GpuBuffer", "HandPipeline", "HostFramesEvaluator",
+           "GpuBuffer", "HandGrouping", "HandPipeline", "HostFramesEvaluator",
            "DeviceArray", "HipRuntime", "MAX_UINT16", "RdfError", "device_ptr", "get_runtime", "set_runtime",
            "to_device", "host_mapped_array", "library_path", "synth", "install_reference_aliases"]

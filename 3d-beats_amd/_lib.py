@@ -56,6 +56,12 @@ SIGNATURES = {
     "rdf_flip_x": (_c_int, [_c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
     "rdf_prepare_hand_depth": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p]),
     "rdf_make_rgba_from_labels": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "rdf_shrink_image": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
+    "rdf_write_pixel_groups_to_stencil_image": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_void_p]),
+    "rdf_grow_groups": (_c_int, [_c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
+    "rdf_hand_groups_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int, _c_int]),
+    "rdf_hand_groups": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_void_p, _c_void_p, _c_void_p,
+                                 _c_void_p, _c_void_p, _c_int, _c_void_p]),
     "rdf_train_init": (_c_int, [_c_void_p, _c_size_t, _c_int, _c_void_p, _c_void_p, _c_void_p]),
     "rdf_train_histogram": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_int,
                                      _c_int, _c_int, _c_int, _c_void_p, _c_void_p]),

@@ -2,9 +2,10 @@
 // define the forest's input convention (0 / filtered point -> 65535, per-hand stencil, x flip) and the
 // label colouring.  Semantics follow src/cuda/points_ops.cu:117-127 (convert_0s_to_maxuint), :149-165
 // (setup_depth_image_for_forest), :440-463 (stencil_depth_image_by_group), :466-483 (flip_x), :258-281
-// (make_rgba_from_labels); all are byte/integer exact.  Each is a pure HBM stream: one lane per pixel
-// with 2-byte accesses is latency- not bandwidth-limited at these sizes (a 848x480 frame is 814 KB), so
-// lanes take 8 pixels (16 B) where alignment allows.
+// (make_rgba_from_labels); also the three kernels around the hand grouping (8f-3): :376-403 (shrink_image),
+// :487-503 (write_pixel_groups_to_stencil_image), :407-438 (grow_groups).  All are byte/integer exact.  Each is
+// a pure HBM stream: one lane per pixel with 2-byte accesses is latency- not bandwidth-limited at these sizes (a
+// 848x480 frame is 814 KB), so lanes take 8 pixels (16 B) where alignment allows.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -120,6 +121,39 @@ __global__ __launch_bounds__(256) void k_prepare_hand(int dim_x, int dim_y, int 
     }
 }
 
+// shrink_image (points_ops.cu:376-403): out[y][x] = in[y*f][x*f], out = [dim_y / f][dim_x / f]
+__global__ __launch_bounds__(256) void k_shrink(int dim_x, int level, int out_x, int out_y, const uint16_t *in, uint16_t *out)
+{
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= out_x || y >= out_y) return;
+    out[(size_t)y * out_x + x] = in[(size_t)(y << level) * dim_x + (x << level)];
+}
+
+// write_pixel_groups_to_stencil_image (points_ops.cu:487-503): stencil[c[i][0]][c[i][1]] = c[i][2]
+__global__ __launch_bounds__(256) void k_write_groups(const int32_t *coords, int num_coords, uint16_t *stencil, int dim_0,
+                                                      int dim_1)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= num_coords) return;
+    const int a = coords[(size_t)i * 3], b = coords[(size_t)i * 3 + 1];
+    if (a < 0 || a >= dim_0 || b < 0 || b >= dim_1) return;   // (the reference asserts)
+    stencil[(size_t)a * dim_1 + b] = (uint16_t)coords[(size_t)i * 3 + 2];
+}
+
+// grow_groups (points_ops.cu:407-438): own value if nonzero, else the first nonzero of left, right, up, down
+__global__ __launch_bounds__(256) void k_grow(int dim_x, int dim_y, const uint16_t *in, uint16_t *out)
+{
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= dim_x || y >= dim_y) return;
+    const size_t i = (size_t)y * dim_x + x;
+    uint32_t g = in[i];
+    if (!g && x > 0) g = in[i - 1];
+    if (!g && x + 1 < dim_x) g = in[i + 1];
+    if (!g && y > 0) g = in[i - dim_x];
+    if (!g && y + 1 < dim_y) g = in[i + dim_x];
+    out[i] = (uint16_t)g;
+}
+
 dim3 grid2d(int dim_x, int dim_y) { return dim3((dim_x + 63) / 64, (dim_y + 3) / 4); }
 
 } // namespace
@@ -191,6 +225,39 @@ int rdf_make_rgba_from_labels(int dim_x, int dim_y, int num_colors, const uint16
     hipLaunchKernelGGL(k_rgba, grid2d(dim_x, dim_y), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dim_x, dim_y,
                        num_colors, labels, reinterpret_cast<const uint32_t *>(colors_rgba),
                        reinterpret_cast<uint32_t *>(image_rgba));
+    return (int)hipGetLastError();
+}
+
+int rdf_shrink_image(int dim_x, int dim_y, int mipmap_level, const uint16_t *depth_in, uint16_t *depth_out, void *stream)
+{
+    if (dim_x < 0 || dim_y < 0 || mipmap_level < 0 || mipmap_level > 30) return RDF_ERR_BAD_ARG;
+    const int out_x = dim_x >> mipmap_level, out_y = dim_y >> mipmap_level;
+    if (out_x == 0 || out_y == 0) return RDF_OK;
+    if (!depth_in || !depth_out) return RDF_ERR_NULL_PTR;
+    hipLaunchKernelGGL(k_shrink, grid2d(out_x, out_y), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dim_x,
+                       mipmap_level, out_x, out_y, depth_in, depth_out);
+    return (int)hipGetLastError();
+}
+
+int rdf_write_pixel_groups_to_stencil_image(const int32_t *coords, int num_coords, uint16_t *stencil, int stencil_dim_0,
+                                            int stencil_dim_1, void *stream)
+{
+    if (num_coords < 0 || stencil_dim_0 < 0 || stencil_dim_1 < 0) return RDF_ERR_BAD_ARG;
+    if (num_coords == 0) return RDF_OK;
+    if (!coords || !stencil) return RDF_ERR_NULL_PTR;
+    hipLaunchKernelGGL(k_write_groups, dim3((unsigned)((num_coords + 255) / 256)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), coords, num_coords, stencil, stencil_dim_0, stencil_dim_1);
+    return (int)hipGetLastError();
+}
+
+int rdf_grow_groups(int dim_x, int dim_y, const uint16_t *groups_in, uint16_t *groups_out, void *stream)
+{
+    if (dim_x < 0 || dim_y < 0) return RDF_ERR_BAD_ARG;
+    if (dim_x == 0 || dim_y == 0) return RDF_OK;
+    if (!groups_in || !groups_out) return RDF_ERR_NULL_PTR;
+    if (groups_in == groups_out) return RDF_ERR_BAD_ARG;   // a grow in place would read what it has written
+    hipLaunchKernelGGL(k_grow, grid2d(dim_x, dim_y), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dim_x, dim_y,
+                       groups_in, groups_out);
     return (int)hipGetLastError();
 }
 

@@ -341,6 +341,52 @@ int rdf_make_rgba_from_labels(int dim_x, int dim_y, int num_colors, const uint16
                               const uint8_t *colors_rgba, uint8_t *image_rgba, void *stream);
 
 /*
+ * ---- the hand-group image: the host round trip of src/3d_bz.py:213-263, kernel for kernel ----
+ * rdf_shrink_image                          src/cuda/points_ops.cu:376-403  out[y][x] = in[y << level][x << level],
+ *                                           out = [dim_y >> level][dim_x >> level]
+ * rdf_write_pixel_groups_to_stencil_image   :487-503  stencil[c[i][0]][c[i][1]] = c[i][2] for i < num_coords; the stencil is
+ *                                           [stencil_dim_0][stencil_dim_1] (the reference's int2 stencil_dims = (rows, cols));
+ *                                           rows that fall outside it are skipped (the reference asserts)
+ * rdf_grow_groups                           :407-438  out[y][x] = in[y][x] if nonzero, else the first nonzero of left, right,
+ *                                           up, down (outside the image reads 0), else 0
+ */
+int rdf_shrink_image(int dim_x, int dim_y, int mipmap_level, const uint16_t *depth_in, uint16_t *depth_out, void *stream);
+int rdf_write_pixel_groups_to_stencil_image(const int32_t *coords, int num_coords, uint16_t *stencil, int stencil_dim_0,
+                                            int stencil_dim_1, void *stream);
+int rdf_grow_groups(int dim_x, int dim_y, const uint16_t *groups_in, uint16_t *groups_out, void *stream);
+
+/*
+ * Hand groups of n depth frames in one call: shrink_image -> CppGrouping().make_groups -> write_pixel_groups_to_stencil_image ->
+ * grow_groups (src/3d_bz.py:213-263), bit for bit, with no host step.  depth uint16 [n][dim_y][dim_x], 0 = no pixel (the
+ * camera's convention, not the forest's 65535); f = 1 << mipmap_level, Hm = dim_y / f, Wm = dim_x / f.
+ *   shrink      mm[y][x] = depth[y*f][x*f]; foreground = mm != 0                          (points_ops.cu:376-403)
+ *   components  4-connected sets of foreground pixels (no diagonals)                       (grouping.cpp:82-135)
+ *   size filter dropped when (float)size / (float)(Wm*Hm) <= pct_thresh, fp32               (grouping.cpp:139)
+ *   centroid    (float)sum_x / (float)size and (float)sum_y / (float)size, one IEEE divide  (grouping.cpp:141-150)
+ *   side        c_x < Wm / 2.f -> group 1, else (c_x == Wm / 2.f included) group 2         (grouping.cpp:152)
+ *   winner      per side the largest; ties to the smallest minimum raster index y*Wm + x    (grouping.cpp:153-165)
+ *               (the component the reference's raster scan meets first)
+ *   g_info      [n][2][3] float {size, c_x, c_y} of group 1, then group 2.  A side without a winner gets {0, 0, 0}: the
+ *               reference leaves its c_x, c_y uninitialised -- the one deliberate difference  (grouping.cpp:169-183)
+ *   stencil     1 / 2 / 0 by winner membership                                              (points_ops.cu:487-503)
+ *   groups_out  [n][Hm][Wm] uint16: stencil grown once, as rdf_grow_groups                  (points_ops.cu:407-438);
+ *               all zeros when neither side has a winner (3d_bz.py:262)
+ * Optional outputs (skipped when NULL): g_info_out; components_out int32 [n][Hm][Wm] = the pixel's component's minimum
+ * raster index, -1 for background; coords_out int32 [n][Hm*Wm][3] = rows (y, x, group), group 1 then group 2, each in
+ * RASTER order (the reference lists BFS order; its only consumer scatters the list into an image), rows past the two
+ * groups' sizes untouched.
+ * path: 0 = auto, 1 = resident (one workgroup per frame, all in LDS; Hm*Wm <= 16000, else RDF_ERR_BAD_ARG), 2 = global
+ * (tiled, five launches).  workspace: rdf_hand_groups_workspace_bytes(n, dim_x, dim_y, mipmap_level) bytes of device memory,
+ * 8-byte aligned, contents irrelevant; only the global path uses it (may be NULL when the call takes the resident path).
+ * RDF_ERR_TOO_LARGE when Hm*Wm*max(Hm, Wm) >= 2^31 (the integer coordinate sums would not be exact).  Integer atomics only:
+ * the results are the same on every run.  No host synchronisation, allocation or read: the call can be captured.
+ */
+size_t rdf_hand_groups_workspace_bytes(int n, int dim_x, int dim_y, int mipmap_level);
+int rdf_hand_groups(const uint16_t *depth, int n, int dim_x, int dim_y, int mipmap_level, float pct_thresh,
+                    uint16_t *groups_out, float *g_info_out, int32_t *components_out, int32_t *coords_out, void *workspace,
+                    int path, void *stream);
+
+/*
  * ---- training of one tree; kernel parameters as in src/cuda/tree_train.cu ----
  * rdf_train_init            root class counts + nodes_by_pixel = (label > 0 ? 0 : -1): the host-side set-up of
  *                           src/decision_tree.py:452-468, on the device; root_counts[n_classes] must be zero
