@@ -14,27 +14,35 @@ reported (copy-engine peer copies into rank 0's IPC-mapped ring; the kernels' ow
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Rank 0's LAST stdout line is ONE compact JSON object (< 4 KB: the contract's keys, a flat `roofline`, `cpu_baseline`, one
-or two scalars per leg); the FULL result -- everything below -- goes to `bench_full.json` in the current directory
-(--full-json PATH) and, as one line, to stderr.  --dump-outputs DIR also writes the label maps of the last timed step to DIR
-(dump_outputs), so that two builds can be compared output for output.  At N = 1 the same run also measures
+or two scalars per leg); the FULL result goes to `bench_full.json` in the current directory (--full-json PATH) and, as one
+line, to stderr.  --dump-outputs DIR also writes the label maps of the last timed step to DIR (dump_outputs), so that two
+builds can be compared output for output.
+
+At N = 1 a plain run does only what `value` needs: it generates the inputs, tunes the forest, warms up, times the K steps,
+checks the last one against the visit-counter kernel, dumps if asked and prints the line; its `roofline` prices the timed
+launch with the newest committed counters (profiles/).  With --full the same run also measures
   * `cfg2_single_frame` (ONE 848x480 frame per launch), `cfg3_layered_run` (LayeredDecisionForest.run),
   * `cfg5_shard` (config 5's per-GPU shard: 32 dense 1280x720 frames, 8 trees of depth 22, two frames checked against
     the oracle inside the run),
   * `roofline` objects for the headline kernel, config 2 and config 5: a hierarchical roofline (tools/roofline.py) built
     from rocprofv3 counters that THIS run collects -- before it touches the GPU itself it starts itself once per counter
     set as `rocprofv3 --pmc ... -- python3 bench.py --leg <name>` (separate passes, never combined with tracing),
-  * (N > 1 only) `cfg5_all_ranks`: config 5's workload sharded over the same ranks (32 dense 1280x720 frames and the
-    replicated T8/D22 forest per rank: at N = 8 this is BASELINE configs[4] itself), timed without and with an RCCL
-    gather of the label maps to rank 0, barrier + synchronize on both sides, MAX over ranks, gather verified by checksums,
   * `cpu_baseline`: this repo's CPU restatement (oracle/rdf_oracle.c, OpenMP) -- the reference has no CPU path --
-    timed on a bounded sample of the same frames, which also checks the GPU labels of those frames bit for bit.
+    timed on a bounded sample of the same frames, which also checks the GPU labels of those frames bit for bit,
+  * the legs beside the headline kernel (balanced, trained and trainer forests, reference layout, PCIe, hand pipeline,
+    mean shift, training).
+At N > 1 every run also measures `cfg5_all_ranks`: config 5's workload sharded over the same ranks (32 dense 1280x720
+frames and the replicated T8/D22 forest per rank: at N = 8 this is BASELINE configs[4] itself), timed without and with an
+RCCL gather of the label maps to rank 0, barrier + synchronize on both sides, MAX over ranks, gather verified by checksums.
 """
 import argparse
+import atexit
 import contextlib
 import hashlib
 import importlib
 import json
 import os
+import shutil
 import sys
 import time
 
@@ -51,9 +59,15 @@ def _synth_digest():
         return hashlib.sha256(f.read()).hexdigest()[:16]
 
 
-# one directory per version of the input generator: a cache written by another version is never read, so the same arguments
-# give the same inputs from run to run
-CACHE = os.path.join(os.environ.get("RDF_BENCH_CACHE", "/tmp/rdf_bench_cache"), "synth_" + _synth_digest())
+CACHE_ROOT = os.environ.get("RDF_BENCH_CACHE", "/tmp/rdf_bench_cache")
+
+
+def cache_dir():
+    """The input cache of THIS run (RDF_BENCH_RUN_ID, which the --pmc child passes of a --full run inherit and the ranks of an
+    N > 1 run share), or None: a plain N = 1 run generates its inputs in memory.  One directory per run and version of the
+    input generator, removed when the run ends, so that no run reads what an earlier one wrote."""
+    run_id = os.environ.get("RDF_BENCH_RUN_ID")
+    return os.path.join(CACHE_ROOT, "synth_" + _synth_digest(), "run_" + run_id) if run_id else None
 
 
 def parse():
@@ -67,8 +81,12 @@ def parse():
     ap.add_argument("--trees", type=int, default=4)
     ap.add_argument("--depth", type=int, default=20)
     ap.add_argument("--classes", type=int, default=4)
+    ap.add_argument("--full", action="store_true", help="N = 1: measure everything beside `value` too -- the --pmc counter "
+                    "passes and roofline levels, the CPU baseline, the other configs and legs.  Off: set-up, warm-up, the timed "
+                    "steps and the line only (see the module docstring)")
     ap.add_argument("--topology", default="full", choices=["full", "trained", "balanced", "trainer"],
-                    help="synthetic topologies; `trainer` = the forest the cfg2_trainer_forest leg trained and left in the bench cache")
+                    help="synthetic topologies; `trainer` = the forest the cfg2_trainer_forest leg of this --full run trained and "
+                         "left in the run's cache (what its `--leg headline_trainer` child passes evaluate)")
     ap.add_argument("--chunks", type=int, default=0, help="eval/gather pipeline chunks per step (0: one launch per step; at N>1 the gather then overlaps the NEXT step)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -81,8 +99,9 @@ def parse():
     ap.add_argument("--no-pcie", action="store_true", help="skip the host-buffer variant (pinned H2D + kernel + D2H)")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the legs beside the forest kernel (reference-layout "
                     "forest, trained-like topology, per-hand pipeline, mean shift, training)")
-    ap.add_argument("--headline-only", action="store_true", help="only the timed batch (no other legs, no counters): "
-                    "what tools/profile.sh traces so that rocprofv3's per-kernel average is the headline kernel's")
+    ap.add_argument("--headline-only", action="store_true", help="only the timed batch (no other legs, no counters, even with "
+                    "--full) and --deep-from honoured: what tools/profile.sh traces so that rocprofv3's per-kernel average is the "
+                    "headline kernel's")
     ap.add_argument("--no-balanced", action="store_true", help="skip the legs on forests whose deep levels are occupied "
                     "(cfg2_balanced, cfg5_balanced)")
     ap.add_argument("--no-tune", action="store_true", help="do not let DecisionForest.tune choose the deep-level table per forest")
@@ -169,15 +188,19 @@ def host_cores():
 
 
 def cached(name, make):
-    """Synthetic inputs are seeded and deterministic; the --pmc child passes reuse what the first process generated."""
-    path = os.path.join(CACHE, name + ".npy")
+    """Synthetic inputs are seeded and deterministic; the other processes of a run (--pmc child passes, ranks) reuse what its
+    first process generated (cache_dir).  Without a run cache: make()."""
+    cache = cache_dir()
+    if cache is None:
+        return make()
+    path = os.path.join(cache, name + ".npy")
     try:
         return np.load(path, mmap_mode="r")
     except Exception:
         pass
     arr = make()
     try:
-        os.makedirs(CACHE, exist_ok=True)
+        os.makedirs(cache, exist_ok=True)
         tmp = f"{path}.{os.getpid()}.tmp.npy"
         np.save(tmp, arr)
         os.replace(tmp, path)
@@ -448,10 +471,15 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
     multi = world > 1 or a.force_distributed        # the distributed code path (one rank too, with --force-distributed)
-    full_run = not multi and a.leg is None and not a.headline_only
+    full_run = a.full and not multi and a.leg is None and not a.headline_only
+
+    # ---- the input cache of a run of several processes (cache_dir): --full at N = 1 (its --pmc child passes inherit the
+    # name) and N > 1 (the other ranks take rank 0's, below); it goes when the run ends ----
+    if (a.full or multi) and a.leg is None and "RDF_BENCH_RUN_ID" not in os.environ and rank == 0:
+        os.environ["RDF_BENCH_RUN_ID"] = f"{os.getpid()}_{int(time.time())}"
+        atexit.register(shutil.rmtree, cache_dir(), True)
 
     # ---- counters first: the child passes must run before this process touches the GPU ----
-    os.environ.setdefault("RDF_BENCH_RUN_ID", f"{os.getpid()}_{int(time.time())}")      # (inherited by the child passes: tune_forest)
     live = None
     if full_run and not a.no_counters:
         legs = ["headline", "cfg2"] + ([] if a.no_cfg5 else ["cfg5"]) + \
@@ -476,6 +504,10 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", dev_index))
         else:
             dist.init_process_group(a.backend, rank=rank, world_size=world)
+        run_id = [os.environ.get("RDF_BENCH_RUN_ID")]       # one cache for every rank (config 5's forest: rank 0 generates it)
+        dist.broadcast_object_list(run_id, src=0)
+        if run_id[0]:
+            os.environ["RDF_BENCH_RUN_ID"] = run_id[0]
 
     rdf = importlib.import_module("3d-beats_amd")
     dmod = importlib.import_module("3d-beats_amd.distributed")
@@ -501,7 +533,7 @@ def main():
         `key`: ONE choice per forest and bench run -- the --pmc child passes of a leg and this process must walk the same
         table, or a leg's counters describe another kernel than the one it timed (two tables within 2 % of each other, config 5's
         "full" forest, tuned differently from process to process): the first process of the run that tunes a key leaves its
-        choice in the bench cache, the others take it."""
+        choice in the run's cache (cache_dir), the others take it."""
         if a.unpacked or a.no_tune:
             return None
 
@@ -512,8 +544,8 @@ def main():
             return res
         if a.deep_from is not None and a.headline_only:
             return fixed(a.deep_from, "--deep-from")
-        run_id = os.environ.get("RDF_BENCH_RUN_ID")
-        path = os.path.join(CACHE, f"tune_{run_id}_{key}.json") if (run_id and key and not multi) else None
+        cache = cache_dir()
+        path = os.path.join(cache, f"tune_{key}.json") if (cache and key and not multi) else None
         if path and os.path.exists(path):
             try:
                 got = json.load(open(path))
@@ -523,7 +555,7 @@ def main():
         res = forest_obj.tune(sample)
         if path:
             try:
-                os.makedirs(CACHE, exist_ok=True)
+                os.makedirs(cache, exist_ok=True)
                 tmp = f"{path}.{os.getpid()}.tmp"
                 json.dump(res, open(tmp, "w"))
                 os.replace(tmp, path)
@@ -761,7 +793,7 @@ def main():
 
     def make_forest():
         if a.topology == "trainer":
-            raise SystemExit(f"--topology trainer: no forest_T{T}_D{D}_C{C}_trainer in the bench cache (the cfg2_trainer_forest leg of a default run leaves it there)")
+            raise SystemExit(f"--topology trainer: no forest_T{T}_D{D}_C{C}_trainer in this run's cache (the cfg2_trainer_forest leg of a --full run leaves it there for its child passes)")
         return synth.forest(T, D, C, a.topology)
     forest_np = np.asarray(cached(f"forest_T{T}_D{D}_C{C}_{a.topology}", make_forest))
     forest = rdf.DecisionForest.from_numpy(forest_np)
@@ -1430,7 +1462,7 @@ def main():
             if not a.no_balanced and not a.unpacked:
                 def leg_trainer_forest():
                     """A forest from this repo's own trainer on the bench batch (tools/bench_legs.py), and -- round 6 -- its own
-                    counter passes: the trained forest and the table tune() chose go into the bench cache, `--leg
+                    counter passes: the trained forest and the table tune() chose go into the run's cache, `--leg
                     headline_trainer` child processes (one per counter set) evaluate the same batch on it, and the leg gets a
                     roofline of its own like the synthetic topologies."""
                     res, tf_np = bench_legs.trainer_forest(
@@ -1439,10 +1471,10 @@ def main():
                     if C != 4 or a.no_counters or not live:
                         return res
                     try:
-                        os.makedirs(CACHE, exist_ok=True)
-                        np.save(os.path.join(CACHE, f"forest_T{T}_D{D}_C{C}_trainer.npy"), tf_np)
-                        run_id = os.environ.get("RDF_BENCH_RUN_ID")
-                        json.dump(res["tune"], open(os.path.join(CACHE, f"tune_{run_id}_T{T}_D{D}_C{C}_trainer_{H}x{W}_F{F}.json"), "w"))
+                        cache = cache_dir()
+                        os.makedirs(cache, exist_ok=True)
+                        np.save(os.path.join(cache, f"forest_T{T}_D{D}_C{C}_trainer.npy"), tf_np)
+                        json.dump(res["tune"], open(os.path.join(cache, f"tune_T{T}_D{D}_C{C}_trainer_{H}x{W}_F{F}.json"), "w"))
                         ft = rdf.DecisionForest.from_numpy(tf_np)
                         ft.packed(1.0)
                         assert lib.rdf_forest_set_deep_from(ft.packed(1.0).ptr, int(res["tune"]["deep_from"])) == 0

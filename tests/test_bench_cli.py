@@ -1,6 +1,7 @@
-"""bench.py's contract with the driver, rehearsed on the one GPU of the test box: the N = 1 line carries the roofline and
-the legs, and the N > 1 code path (two ranks over gloo sharing the GPU: same control flow as RCCL ranks on distinct
-GPUs) gathers, verifies the gather and reports what a driver needs to check the run."""
+"""bench.py's contract with the driver, rehearsed on the one GPU of the test box: a plain N = 1 run times the headline only,
+the N = 1 line of a --full run carries the roofline and the legs, and the N > 1 code path (two ranks over gloo sharing the
+GPU: same control flow as RCCL ranks on distinct GPUs) gathers, verifies the gather and reports what a driver needs to
+check the run."""
 import json
 import os
 import socket
@@ -51,7 +52,7 @@ def _check_contract(c):
 def test_single_gpu_line_has_roofline_and_legs(tmp_path):
     env = dict(os.environ, RDF_BENCH_CACHE=str(tmp_path))
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--frames", "8",
-                        "--depth", "12", "--no-counters", "--no-cfg5", "--cpu-seconds", "1", "--full-json", str(tmp_path / "full.json")],
+                        "--depth", "12", "--full", "--no-counters", "--no-cfg5", "--cpu-seconds", "1", "--full-json", str(tmp_path / "full.json")],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     c = _last_json(r.stdout)
@@ -93,6 +94,33 @@ def test_single_gpu_line_has_roofline_and_legs(tmp_path):
     assert len(b["distinct_nodes"]["per_level"]) == 12 and b["distinct_nodes"]["share_of_level"][11] > 2 * b["distinct_nodes_full_topology"]["share_of_level"][11]
     ho = d["cfg3_layered_run"]["host_overhead"]
     assert ho["rdf_layered_run_calls"] == 200 and ho["rdf_eval_forest_packed_calls"] == 200 and ho["rdf_eval_forest_packed_us_in_library_before_the_launch"] < 20
+    # the run's input cache went with it: no later run reads it
+    assert not list(tmp_path.glob("synth_*/run_*"))
+
+
+_FULL_ONLY = ("cpu_baseline", "cpu_baseline_numpy", "cfg2_single_frame", "cfg3_layered_run", "cfg5_shard", "cfg5_balanced",
+              "cfg2_balanced", "cfg2_trained", "cfg2_trainer_forest", "unpacked", "pcie_inclusive", "hand_pipeline", "mean_shift",
+              "train", "counter_passes")
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_only(tmp_path):
+    """Without --full: the contract's line, `value` and its roofline (priced with the committed counters), none of the legs,
+    and no input cache written or read."""
+    env = dict(os.environ, RDF_BENCH_CACHE=str(tmp_path / "cache"))
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--frames", "8",
+                        "--depth", "12", "--full-json", str(tmp_path / "full.json")],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    c = _last_json(r.stdout)
+    _check_contract(c)
+    d = _full(c, tmp_path / "full.json")
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["value_is"].startswith("median")
+    assert abs(d["ms_per_step"] * d["value"] - 8 * 480 * 848 / 1e3) < 1e-2 * d["ms_per_step"] * d["value"]
+    assert "roofline.bound" in d["metric"] and d["roofline"]["algorithmic"]["bytes_per_launch"] > 0
+    assert "child passes" not in str(d["roofline"]["counters_source"]) and c["roofline"].get("counters") != "live --pmc passes of this run"
+    assert not [k for k in _FULL_ONLY if k in d]
+    assert not (tmp_path / "cache").exists()
 
 
 @pytest.mark.gpu
@@ -140,6 +168,8 @@ def test_two_ranks_on_one_gpu_rehearse_the_multi_gpu_line(gather, tmp_path):
     assert c5["n_gpus"] == 2 and c5["gather_check"] == "ok" and c5["value"] > 0 and c5["value_kernel_only"] >= c5["value"]
     # ... and once more with every rank's kernel writing straight into rank 0's ring
     assert c5["p2p_direct_stores"]["gather_check"] == "ok" and c5["p2p_direct_stores"]["value"] > 0
+    # the ranks' shared input cache went with the run
+    assert not list(tmp_path.glob("synth_*/run_*"))
 
 
 @pytest.mark.gpu
@@ -394,6 +424,30 @@ def test_two_ranks_dump_every_ranks_labels_as_rank_zero_received_them(rdf, oracl
     got = _load_dump(tmp_path / "dump")
     want = np.concatenate([_oracle_labels(oracle, rdf.synth, 4, 4 * g, 12) for g in range(2)])
     assert np.array_equal(got["labels"], want.astype(np.float32)) and got["labels_index"].tolist() == list(range(8))
+
+
+def test_input_cache_belongs_to_one_full_run(tmp_path, monkeypatch):
+    """No GPU needed: without a run id (a plain N = 1 run) bench.cached only generates; with one (a --full run and its child
+    passes, the ranks of an N > 1 run) the first call generates and writes into that run's own directory, later calls of the
+    run read it, and another run generates afresh."""
+    monkeypatch.setenv("RDF_BENCH_CACHE", str(tmp_path))
+    monkeypatch.delenv("RDF_BENCH_RUN_ID", raising=False)
+    bench = _bench_module()
+    made = []
+
+    def make():
+        made.append(1)
+        return np.arange(6, dtype=np.uint16).reshape(2, 3)
+    assert bench.cache_dir() is None
+    assert np.array_equal(bench.cached("x", make), np.arange(6).reshape(2, 3)) and len(made) == 1
+    assert list(tmp_path.iterdir()) == []
+    made.clear()
+    for run in ("1_1", "2_2"):
+        monkeypatch.setenv("RDF_BENCH_RUN_ID", run)
+        assert bench.cache_dir().startswith(str(tmp_path)) and bench.cache_dir().endswith("run_" + run)
+        for _ in range(2):
+            assert np.array_equal(bench.cached("x", make), np.arange(6).reshape(2, 3))
+    assert len(made) == 2 and len(list(tmp_path.glob("synth_*/run_*/x.npy"))) == 2
 
 
 def test_dump_outputs_samples_within_the_budget(tmp_path):
