@@ -10,23 +10,26 @@ inference path.
 """
 from . import synth  # noqa: F401
 from ._lib import RdfError, library_path  # noqa: F401
+from .calibrated_plane import CalibratedPlane  # noqa: F401
 from .decision_tree import (DecisionForest, DecisionTree, DecisionTreeEvaluator,  # noqa: F401
                             DecisionTreeTrainer, LayeredDecisionForest)
 from .device import DeviceArray, HipRuntime, device_ptr, get_runtime, host_mapped_array, set_runtime, to_device  # noqa: F401
 from .engine.buffer import GpuBuffer  # noqa: F401
+from .frontend import FrameFrontEnd  # noqa: F401
 from .grouping import HandGrouping  # noqa: F401
 from .host_stream import HostFramesEvaluator  # noqa: F401
 from .pipeline import HandPipeline  # noqa: F401
 from .util import MAX_UINT16  # noqa: F401
 
 _REFERENCE_MODULE_NAMES = ("decision_tree", "util", "engine", "engine.buffer", "cuda", "cuda.points_ops", "cuda.mean_shift",
-                           "cuda.py_nvcc_utils")
+                           "cuda.py_nvcc_utils", "calibrated_plane")
 
 
 def install_reference_aliases(force=False):
     """Make the reference's own import lines resolve to this package: after this call `from decision_tree import *`,
     `from cuda.points_ops import *`, `import cuda.py_nvcc_utils as py_nvcc_utils`, `from cuda.mean_shift import *`,
-    `from engine.buffer import GpuBuffer` and `from util import MAX_UINT16` (run_live_layered.py:6-14, 3d_bz.py:1-20) import
+    `from engine.buffer import GpuBuffer`, `from util import MAX_UINT16` and `from calibrated_plane import *`
+    (run_live_layered.py:6-14, 3d_bz.py:1-20) import
     the modules of `3d-beats_amd`.  (The package's modules import each other relatively, so putting its directory on
     `sys.path` is not enough: the names are registered in `sys.modules`.)  A name that is already imported from somewhere else
     is left alone and reported, unless `force`.  Returns the list of names installed."""
@@ -45,6 +48,6 @@ def install_reference_aliases(force=False):
 
 
 __all__ = ["DecisionTree", "DecisionForest", "LayeredDecisionForest", "DecisionTreeEvaluator", "DecisionTreeTrainer",
-           "GpuBuffer", "HandGrouping", "HandPipeline", "HostFramesEvaluator",
+           "GpuBuffer", "CalibratedPlane", "FrameFrontEnd", "HandGrouping", "HandPipeline", "HostFramesEvaluator",
            "DeviceArray", "HipRuntime", "MAX_UINT16", "RdfError", "device_ptr", "get_runtime", "set_runtime",
            "to_device", "host_mapped_array", "library_path", "synth", "install_reference_aliases"]

@@ -1,6 +1,7 @@
-"""ctypes binding of csrc/librdf_hip.so (the C ABI declared in include/rdf_hip.h).
+"""ctypes binding of csrc/librdf_hip.so (the C ABI declared in include/rdf_hip.h) and of csrc/librdf_frontend.so (the
+depth front end, include/rdf_frontend.h).
 
-This is the only place the shared library is opened.  There is no CPU fallback: a missing
+This is the only place the shared libraries are opened.  There is no CPU fallback: a missing
 library, or a machine without a HIP device, raises.
 """
 import ctypes
@@ -178,6 +179,74 @@ def check_build_id(lib, path):
         else:
             raise RdfError(msg)
     return got
+
+
+# name -> (restype, argtypes); every symbol include/rdf_frontend.h declares
+FRONTEND_SIGNATURES = {
+    "rdf_make_plane_candidates": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                           _c_void_p]),
+    "rdf_plane_inliers": (_c_int, [_c_int, _c_float, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "rdf_plane_select": (_c_int, [_c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "rdf_calibrate_plane_workspace_bytes": (_c_size_t, [_c_int]),
+    "rdf_calibrate_plane": (_c_int, [_c_int, _c_float, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                     _c_void_p, _c_void_p]),
+    "rdf_frame_front": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _c_void_p, _c_float,
+                                 _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p]),
+    "rdf_deproject_points": (_c_int, [_c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _c_void_p, _c_void_p, _c_void_p]),
+    "rdf_transform_points": (_c_int, [_c_int, _c_void_p, _c_void_p, _c_void_p]),
+    "rdf_filter_points_by_plane": (_c_int, [_c_int, _c_float, _c_void_p, _c_void_p]),
+    "rdf_remove_missing_3d_points_from_depth_image": (_c_int, [_c_int, _c_void_p, _c_void_p, _c_void_p]),
+    "rdf_gaussian_depth_filter": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "rdf_frontend_abi_version": (_c_int, []),
+    "rdf_frontend_build_id": (ctypes.c_char_p, []),
+    "rdf_frontend_error_string": (ctypes.c_char_p, [_c_int]),
+}
+
+FRONTEND_ABI_VERSION = 1
+_frontend = None
+
+
+def frontend_library_path():
+    return _build.FRONTEND_SO
+
+
+def load_frontend():
+    """Open librdf_frontend.so and type every entry point, as load() does for librdf_hip.so.  Raises if it has not been
+    built, if its ABI number is not the one this binding was written for, or if it was built from other sources."""
+    global _frontend
+    if _frontend is not None:
+        return _frontend
+    path = frontend_library_path()
+    if not os.path.exists(path):
+        raise RdfError(f"{path} is missing: build it first (python __graft_entry__.py build, "
+                       "or python 3d-beats_amd/_build.py). There is no CPU fallback.")
+    lib = ctypes.CDLL(path)
+    for name, (res, args) in FRONTEND_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.rdf_frontend_abi_version() != FRONTEND_ABI_VERSION:
+        raise RdfError(f"librdf_frontend.so ABI {lib.rdf_frontend_abi_version()} != expected {FRONTEND_ABI_VERSION}; rebuild")
+    got = lib.rdf_frontend_build_id()
+    got = got.decode() if isinstance(got, bytes) else str(got)
+    files = _build.FRONTEND_SOURCES + _build.FRONTEND_HEADERS
+    if _build.sources_present(files) and got != _build.frontend_source_id():
+        msg = (f"{path} was built from other sources (build id {got}, sources {_build.frontend_source_id()}): rebuild it "
+               "(python __graft_entry__.py build).")
+        if os.environ.get("RDF_ALLOW_STALE_LIBRARY") == "1":
+            import warnings
+            warnings.warn(msg)
+        else:
+            raise RdfError(msg)
+    _frontend = lib
+    return lib
+
+
+def check_frontend(lib, code, what):
+    if code != 0:
+        msg = lib.rdf_frontend_error_string(int(code))
+        msg = msg.decode() if isinstance(msg, bytes) else str(msg)
+        raise RdfError(f"{what} failed: {msg} (code {code})")
 
 
 def check(lib, code, what):

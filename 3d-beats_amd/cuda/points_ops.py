@@ -3,18 +3,48 @@ apps call their PyCUDA counterparts (/root/reference/src/cuda/points_ops.py:16-4
 src/3d_bz.py:396-456; src/run_live_layered.py:117-122): positional arguments as there, `grid=` and
 `block=` accepted and ignored (launch geometry belongs to the library).  The kernels that
 touch the forest's input and output live here, and the three around the hand grouping (8f-3: shrink_image,
-write_pixel_groups_to_stencil_image, grow_groups); deprojection, plane fitting, filtering and mesh generation
-stay out of scope."""
+write_pixel_groups_to_stencil_image, grow_groups), and the five of the depth front end (deproject_points,
+transform_points, filter_points_by_plane, remove_missing_3d_points_from_depth_image, gaussian_depth_filter; they live in
+librdf_frontend.so, and frontend.FrameFrontEnd fuses them).  Mesh generation stays out of scope."""
 import numpy as np
 
 from .. import _lib
-from ..device import device_ptr, get_runtime
+from ..device import DeviceArray, device_ptr, get_runtime
+
+MAX_FILTER_SIZE = 41
+
+
+def gaussian_kernel(k_size, sigma):
+    """points_ops.py:9-14 without scipy: scipy.stats.norm.pdf(x, 0, sigma) is exp(-((x - 0) / sigma)**2 / 2) / sqrt(2 pi)
+    / sigma in float64, here in that order; the outer product is normalised by its sum and rounded to float32 [k, k]."""
+    assert k_size % 2 == 1, 'kernel must be odd'
+    h = k_size // 2
+    y = (np.linspace(-h, h, k_size) - 0.) / sigma
+    kern1d = np.exp(-y ** 2 / 2.0) / np.sqrt(2 * np.pi) / sigma
+    kern2d = np.outer(kern1d, kern1d)
+    return (kern2d / kern2d.sum()).astype(np.float32)
 
 
 class PointsOps:
     def __init__(self):
         self._rt = get_runtime()
         self._lib = self._rt.lib
+        self._fe = None
+        self.MAX_FILTER_SIZE = MAX_FILTER_SIZE
+        self._gaussian_filter = None
+        self._cached_filter_params = None
+
+    def _frontend(self):
+        if self._fe is None:
+            self._fe = _lib.load_frontend()
+        return self._fe
+
+    def _ok_fe(self, rc, name, *touched):
+        _lib.check_frontend(self._frontend(), rc, name)
+        for t in touched:
+            t = t.cu() if hasattr(t, "cu") else t
+            if hasattr(t, "mark_dirty"):
+                t.mark_dirty()
 
     def _ok(self, rc, name, *touched):
         _lib.check(self._lib, rc, name)
@@ -73,3 +103,51 @@ class PointsOps:
         dim_x, dim_y = (int(v) for v in np.asarray(img_dim).reshape(-1)[:2])
         self._ok(self._lib.rdf_grow_groups(dim_x, dim_y, device_ptr(g_in), device_ptr(g_out), self._rt.stream()),
                  "rdf_grow_groups", g_out)
+
+    # ---- the depth front end, kernel for kernel (3d_bz.py:163-212); frontend.FrameFrontEnd fuses it ----
+    def deproject_points(self, imgs_dim, pp, f, imgs, pts, grid=None, block=None):
+        """imgs_dim = (num_images, dim_x, dim_y, -1) int32, pp = (ppx, ppy) float32 (points_ops.cu:5-36).  Pixels with
+        depth 0 keep what pts held."""
+        n, dim_x, dim_y = (int(v) for v in np.asarray(imgs_dim).reshape(-1)[:3])
+        ppx, ppy = (float(v) for v in np.asarray(pp, np.float32).reshape(-1)[:2])
+        fe = self._frontend()
+        self._ok_fe(fe.rdf_deproject_points(n, dim_x, dim_y, ppx, ppy, float(np.float32(f)), device_ptr(imgs), device_ptr(pts),
+                                            self._rt.stream()),
+                    "rdf_deproject_points", pts)
+
+    def transform_points(self, num_pts, pts, t, grid=None, block=None):
+        """t: the host 4x4 float32 plane, row-major (passed by value, as the reference passes a glm::mat4)."""
+        m = np.ascontiguousarray(np.asarray(t, np.float32).reshape(16))
+        fe = self._frontend()
+        self._ok_fe(fe.rdf_transform_points(int(num_pts), device_ptr(pts), m.ctypes.data, self._rt.stream()),
+                    "rdf_transform_points", pts)
+
+    def filter_points_by_plane(self, num_pts, threshold, pts, grid=None, block=None):
+        fe = self._frontend()
+        self._ok_fe(fe.rdf_filter_points_by_plane(int(num_pts), float(threshold), device_ptr(pts), self._rt.stream()),
+                    "rdf_filter_points_by_plane", pts)
+
+    def remove_missing_3d_points_from_depth_image(self, num_pixels, pts, depth, grid=None, block=None):
+        fe = self._frontend()
+        self._ok_fe(fe.rdf_remove_missing_3d_points_from_depth_image(int(num_pixels), device_ptr(pts), device_ptr(depth),
+                                                                     self._rt.stream()),
+                    "rdf_remove_missing_3d_points_from_depth_image", depth)
+
+    def gaussian_depth_filter(self, d_in, d_out, sigma, k_size=5):
+        """points_ops.py:68-104: one frame of dims d_in.shape[-2:] (the reference passes only dim_x, dim_y, so of a
+        batch only the first frame is filtered).  The weights are computed once per (sigma, k_size) and kept on the device."""
+        assert k_size <= self.MAX_FILTER_SIZE
+        assert len(d_in.shape) in (2, 3)
+        dim_y, dim_x = d_in.shape[-2:]
+        assert tuple(d_in.shape) == tuple(d_out.shape)
+        assert np.dtype(d_in.dtype) == np.uint16 and np.dtype(d_out.dtype) == np.uint16
+        if self._cached_filter_params is None or self._cached_filter_params != (sigma, k_size):
+            if self._gaussian_filter is None:
+                self._gaussian_filter = DeviceArray((self.MAX_FILTER_SIZE * self.MAX_FILTER_SIZE,), np.float32)
+            k = gaussian_kernel(k_size, sigma).reshape(-1)
+            self._gaussian_filter[0:k.shape[0]].set(k)
+            self._cached_filter_params = (sigma, k_size)
+        fe = self._frontend()
+        self._ok_fe(fe.rdf_gaussian_depth_filter(int(dim_x), int(dim_y), int(k_size), self._gaussian_filter.ptr,
+                                                 device_ptr(d_in), device_ptr(d_out), self._rt.stream()),
+                    "rdf_gaussian_depth_filter", d_out)

@@ -208,6 +208,8 @@ class DeviceArray:
         return self
 
     def set(self, ary):
+        if isinstance(ary, DeviceArray):       # GPUArray.set takes a device array too: a device-to-device copy (3d_bz.py:206)
+            return self.copy_from(ary)
         a = np.ascontiguousarray(ary)
         assert a.dtype == self.dtype, f"dtype mismatch: {a.dtype} vs {self.dtype}"
         assert a.size == self.size, f"size mismatch: {a.shape} vs {self.shape}"

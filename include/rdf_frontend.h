@@ -1,0 +1,155 @@
+/*
+ * rdf_frontend.h -- C ABI of librdf_frontend.so: the depth front end of 3d-beats on MI355X (gfx950).  From the camera's raw
+ * depth frame to the table-free depth frame that the hand grouping takes, and the RANSAC plane fit that calibrates it:
+ * the reference's CalibratedPlane (src/calibrated_plane.py, src/cuda/calibrated_plane.cu) and the per-frame chain
+ * deproject_points -> transform_points -> filter_points_by_plane -> remove_missing_3d_points_from_depth_image ->
+ * gaussian_depth_filter of src/3d_bz.py:163-212 (src/cuda/points_ops.cu:5-36, 63-73, 131-146, 327-373).
+ *
+ * It is a library of its own, next to librdf_hip.so, with its own ABI number and build id.  Conventions are those of
+ * rdf_hip.h: every pointer is caller-owned DEVICE memory unless stated; nothing is allocated, freed or synchronised
+ * inside a call (all calls can be captured into a graph); launches are asynchronous on `stream` (a hipStream_t, NULL =
+ * the default stream); the return value is 0, a negative RDF_ERR_* for rejected arguments, or a positive hipError_t, and
+ * rdf_frontend_error_string() names either kind.
+ *
+ * Arithmetic: fp32, round to nearest, no contraction, in the order written below.  Matrices are float [4][4] ROW-major,
+ * p' = M p.  The reference hands numpy's row-major bytes to a glm::mat4 (column-major) and multiplies by its transpose, so
+ * its M is the same matrix.  Where the order comes from glm 0.9.9 it is spelled out:
+ *   mat4 * vec4   p'_i = (M_i0 * x + M_i1 * y) + (M_i2 * z + M_i3 * w)          (Mul0 + Mul1, Mul2 + Mul3, Add0 + Add1)
+ *   dot(v, v)     (v.x * v.x + v.y * v.y) + v.z * v.z
+ *   normalize(v)  v * (1.f / sqrtf(dot(v, v)))                                     (inversesqrt = 1 / sqrt)
+ *   cross(a, b)   (a.y * b.z - b.y * a.z,  a.z * b.x - b.z * a.x,  a.x * b.y - b.x * a.y)
+ * Points are float4 {x, y, z, w}; a point is valid when w == 1.
+ */
+#ifndef RDF_FRONTEND_H
+#define RDF_FRONTEND_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* 1: first version. */
+#define RDF_FRONTEND_ABI_VERSION 1
+
+#define RDF_OK 0
+#define RDF_ERR_BAD_ARG (-1)
+#define RDF_ERR_NULL_PTR (-2)
+#define RDF_ERR_TOO_LARGE (-3)
+
+#define RDF_FRONTEND_MAX_FILTER 41   /* largest Gaussian window (points_ops.py: MAX_FILTER_SIZE) */
+
+/*
+ * Plane candidates, one per random draw row (calibrated_plane.cu:51-90).  rand float [G][32], pts float4 [dim_y][dim_x].
+ * For candidate i, draw j = 0, 1, ... 31: r = floor(((float)rand[i][j] * (float)dim_x) * (float)dim_y) (two fp32
+ * roundings); pts[r] is taken when pts[r].z > 0, until three points P0, P1, P2 are taken.  Then
+ *   v0 = normalize((P1 - P0).xyz), v1 = normalize((P2 - P0).xyz), z = normalize(cross(v0, v1)), x = v0,
+ *   y = normalize(cross(z, x)),
+ *   candidates[i] = | x.x  y.x  z.x  -P0.x |
+ *                   | x.y  y.y  z.y  -P0.y |
+ *                   | x.z  y.z  z.z  -P0.z |
+ *                   | 0    0    0     1    |
+ * so z' = M[2,:] . p takes the z components of the three axes, not the normal, exactly as the reference does.
+ * A duplicate or collinear draw gives NaN axes, and such a candidate counts 0 inliers, as in the reference.
+ * Deviations from the reference:
+ *   - a draw with r < 0 or r >= dim_x * dim_y is a miss.  curand's uniform is (0, 1]: 1.0 gives r = dim_x * dim_y, and
+ *     the reference then reads past the end of pts;
+ *   - a candidate that takes fewer than 3 points is invalid: all 16 entries NaN and counts[i] = -1.  The reference builds
+ *     it from uninitialised registers.
+ * counts int32 [G] (may be NULL): set to 0 for a valid candidate, -1 for an invalid one, ready for rdf_plane_inliers.
+ * start_mat float [16] (may be NULL): written over candidate 0 (valid, count 0), as calibrated_plane.py:62-64 does
+ * before counting, so that a new plane must beat it (it wins ties: the lowest index does).
+ */
+int rdf_make_plane_candidates(int num_candidates, int dim_x, int dim_y, const float *rand, const float *pts,
+                              const float *start_mat, float *candidates, int32_t *counts, void *stream);
+
+/*
+ * Inlier counts (find_plane_ransac, calibrated_plane.cu:3-27): for every point with w == 1 and every candidate,
+ * z' = (M20 * x + M21 * y) + (M22 * z + M23 * w); the point is an inlier when z' < T && z' > -T (|z'| < T, false for NaN).
+ * counts[i] += the number of inliers of candidate i.  Counts are integers: the result does not depend on any order.
+ * A candidate with no inlier is not touched (an invalid one keeps its -1).  n_pts = dim_x * dim_y in the app.
+ */
+int rdf_plane_inliers(int num_candidates, float threshold, int n_pts, const float *pts, const float *candidates,
+                      int32_t *counts, void *stream);
+
+/* The device record rdf_plane_select writes (112 bytes). */
+typedef struct RdfPlaneResult {
+    float plane[16];       /* the recentred plane, row-major; a copy of plane_inout after the call */
+    int32_t best_index;    /* highest count, lowest index on ties (np.argmax) */
+    int32_t best_count;
+    double c[4];           /* float64(M) @ [0, 0, t, 1] of the winner */
+    int32_t status;        /* RDF_PLANE_OK or RDF_PLANE_NONE */
+    int32_t reserved;
+} RdfPlaneResult;
+
+#define RDF_PLANE_OK 0
+#define RDF_PLANE_NONE 1       /* best count <= 0, or |c[2]| >= 0.001 (the reference's assert): plane_inout untouched */
+
+/*
+ * The winner and its recentring (calibrated_plane.py:70-87), one workgroup.  best = np.argmax(counts).  With M the winner,
+ * t = (-M23) / M22 in fp32, c = float64(M) @ [0, 0, t, 1] (M_i2 * t + M_i3, exact product, one double rounding), and
+ * when |c[2]| < 0.001 and the best count > 0: plane = T(-(float)c[0], -(float)c[1], 0) @ M with the translation in
+ * column 3, i.e. M with one fp32 add on each of M[0][3] and M[1][3] (M[0][3] + -(float)c[0]) and rows 2 and 3 unchanged.
+ * plane_inout float [16] is written only then; result (may be NULL) always.
+ */
+int rdf_plane_select(int num_candidates, const float *candidates, const int32_t *counts, float *plane_inout,
+                     RdfPlaneResult *result, void *stream);
+
+/*
+ * The three in sequence: CalibratedPlane.make without its host read.  workspace: rdf_calibrate_plane_workspace_bytes(G)
+ * bytes, 16-byte aligned: candidates float [G][16] at offset 0, then counts int32 [G] (both readable after the call).
+ */
+size_t rdf_calibrate_plane_workspace_bytes(int num_candidates);
+int rdf_calibrate_plane(int num_candidates, float threshold, int dim_x, int dim_y, const float *rand, const float *pts,
+                        const float *start_mat, void *workspace, float *plane_inout, RdfPlaneResult *result, void *stream);
+
+/*
+ * The per-frame chain of 3d_bz.py:163-212 in one launch.  depth uint16 [n][dim_y][dim_x]; the n frames share M =
+ * plane float [16] (device memory, so a plane that rdf_calibrate_plane left on the device feeds it directly).
+ * Per pixel with depth d:
+ *   d == 0                                   -> 0
+ *   p = ((d * (x - ppx)) / f, (d * (y - ppy)) / f, d, 1), with x - ppx and d as float       (points_ops.cu:5-36)
+ *   p' = M p (the order above, all four rows)                                              (points_ops.cu:63-73)
+ *   w' == 1 && z' > -T                       -> 0                                          (calibrated_plane.cu:31-46)
+ *   else w' == 0                             -> 0                                          (points_ops.cu:131-146)
+ *   else                                     -> d
+ * Then, when gauss is not NULL, the Gaussian filter of that cleaned image (points_ops.cu:327-373): weights float [k][k],
+ * k odd, 1 <= k <= 41; for dy then dx, taps outside the frame skipped, w0 += w where the tap is 0, else wn += w and
+ * sum += (float)d * w (a multiply, then an add); out = w0 > wn ? 0 : (uint16)(uint32)floor(sum / wn), where the uint32
+ * conversion saturates (NaN -> 0, as __float2uint_rd) and the cast keeps the low 16 bits.
+ * depth_out uint16 [n][dim_y][dim_x]; may equal depth only when gauss is NULL.
+ * pts_out float4 [n][dim_y][dim_x] (may be NULL): p' where d > 0 and the point was not filtered (so also where w' == 0),
+ * {0, 0, 0, 0} elsewhere -- what the reference's chain leaves in its points buffer.  The reference leaves a
+ * pixel with d == 0 as its points buffer held it from earlier frames (never cleared) and transforms those stale points again
+ * every frame; no depth value depends on them.
+ */
+int rdf_frame_front(const uint16_t *depth, int n, int dim_x, int dim_y, float ppx, float ppy, float f, const float *plane,
+                    float threshold, const float *gauss, int k, uint16_t *depth_out, float *pts_out, void *stream);
+
+/*
+ * Stand-alone kernels with the reference's semantics, for the drop-in (each a thin launch over the device functions of
+ * rdf_frame_front).
+ *   deproject_points: pts[i][y][x] = p for d > 0; pixels with d == 0 untouched (as the reference).
+ *   transform_points: pts[i] = M pts[i] where pts[i].w == 1; M = plane float [16] in HOST memory (passed by value there).
+ *   filter_points_by_plane: pts[i] = 0 where w == 1 and z > -T.
+ *   remove_missing_3d_points_from_depth_image: depth[i] = 0 where pts[i].w == 0.
+ *   gaussian_depth_filter: one frame; weights in device memory as above; d_out must not be d_in.
+ */
+int rdf_deproject_points(int n, int dim_x, int dim_y, float ppx, float ppy, float f, const uint16_t *depth, float *pts,
+                         void *stream);
+int rdf_transform_points(int n_pts, float *pts, const float *plane_host, void *stream);
+int rdf_filter_points_by_plane(int n_pts, float threshold, float *pts, void *stream);
+int rdf_remove_missing_3d_points_from_depth_image(int n_pts, const float *pts, uint16_t *depth, void *stream);
+int rdf_gaussian_depth_filter(int dim_x, int dim_y, int k, const float *gauss, const uint16_t *d_in, uint16_t *d_out,
+                              void *stream);
+
+int rdf_frontend_abi_version(void);
+const char *rdf_frontend_build_id(void);
+const char *rdf_frontend_error_string(int code);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* RDF_FRONTEND_H */

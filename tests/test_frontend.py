@@ -1,0 +1,569 @@
+"""The depth front end (librdf_frontend.so, include/rdf_frontend.h; CalibratedPlane, FrameFrontEnd, the five PointsOps kernels)
+against the float32 restatement in tests/frontend_numpy.py, and the package's gaussian_kernel against the reference's own
+output (tests/golden/frontend_v1.npz, recorded by tests/golden/make_frontend_golden.py).  Every GPU comparison is bit for bit."""
+import ctypes
+import importlib
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import frontend_numpy as fnp
+import grouping_numpy as gnp
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "frontend_v1.npz")
+HEADER = os.path.join(ROOT, "include", "rdf_frontend.h")
+T = 40.
+
+
+def _declared(path):
+    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(rdf_[a-z0-9_]+)\s*\(", text)))
+
+
+def _exported(so):
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or "/opt/rocm/lib/llvm/bin/llvm-nm"
+    out = subprocess.run([nm, "-D", "--defined-only", so], capture_output=True, text=True, check=True).stdout
+    return sorted({l.split()[-1] for l in out.splitlines() if l.split() and l.split()[-1].startswith("rdf_")})
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32) if a.dtype == np.float32 else a
+
+
+def _eq(a, b):
+    return np.array_equal(_bits(np.asarray(a)), _bits(np.asarray(b)))
+
+
+def scene(H, W, f, tilt_deg=20., dist=600., box_h=80., holes=0.03, seed=0, hand_scale=1.):
+    """A table tilted by tilt_deg, `dist` mm from the camera along its normal, and two boxes ("hands") box_h mm above it.
+    Returns (depth uint16 [H, W], hand mask, (f, ppx, ppy))."""
+    ppx, ppy = (W - 1) / 2 + 0.3, (H - 1) / 2 - 0.2
+    t = np.deg2rad(tilt_deg)
+    n = np.array([0., -np.sin(t), np.cos(t)])
+    yy, xx = np.mgrid[:H, :W]
+    ray = np.stack([(xx - ppx) / f, (yy - ppy) / f, np.ones((H, W))], -1) @ n
+    z = dist / ray
+    hand = np.zeros((H, W), bool)
+    for cx in (0.3, 0.7):
+        m = (np.abs(xx - cx * W) < W * 0.08 * hand_scale) & (np.abs(yy - 0.55 * H) < H * 0.12 * hand_scale)
+        for k in range(5):   # fingers
+            m |= (np.abs(xx - (cx + (k - 2) * 0.03) * W) < W * 0.008) & (yy > 0.25 * H) & (yy < 0.55 * H)
+        z[m] = (dist - box_h) / ray[m]
+        hand |= m
+    d = np.round(z).astype(np.uint16)
+    d[np.random.default_rng(seed).random((H, W)) < holes] = 0
+    return d, hand, (f, ppx, ppy)
+
+
+def _plane_for(depth, fpp, G=2000, seed=1):
+    f, ppx, ppy = fpp
+    H, W = depth.shape[-2:]
+    rand = np.random.default_rng(seed).random((G, 32), dtype=np.float32)
+    plane, best, cnt, c, st, cand, counts = fnp.calibrate(rand, fnp.deproject(depth, ppx, ppy, f), W, H, T)
+    assert st == 0
+    return plane.reshape(4, 4), rand
+
+
+# ------------------------------------------------------------------ CPU ------------------------------------------------------
+def test_gaussian_kernel_is_the_references_bit_for_bit():
+    po = importlib.import_module("3d-beats_amd.cuda.points_ops")
+    assert os.path.getsize(GOLDEN) < 100_000
+    z = np.load(GOLDEN, allow_pickle=False)
+    assert len(z["k"]) >= 10 and 41 in z["k"].tolist()
+    for i, (k, s) in enumerate(zip(z["k"].tolist(), z["sigma"].tolist())):
+        w = po.gaussian_kernel(k, s)
+        assert w.dtype == np.float32 and _eq(w, z[f"w{i}"]), (k, s)
+    with pytest.raises(AssertionError):
+        po.gaussian_kernel(4, 1.0)
+
+
+def test_inlier_test_at_the_threshold_and_through_nan():
+    M = np.eye(4, dtype=np.float32).reshape(16)
+    pts = np.array([[0, 0, T, 1], [0, 0, -T, 1], [0, 0, np.nextafter(np.float32(T), 0), 1], [0, 0, -39.5, 1],
+                    [0, 0, 0, 2], [0, 0, 0, 0], [np.nan, 0, 0, 1]], np.float32)
+    # +-T exactly is out (z < T && z > -T), just inside is in, w != 1 and NaN never count
+    assert fnp.plane_inliers(pts, M[None], T).tolist() == [2]
+    # a candidate without inliers keeps its count (-1 for an invalid one)
+    far = M.copy()
+    far[11] = 1e6
+    assert fnp.plane_inliers(pts, np.stack([M, far, far]), T, np.array([0, -1, 0], np.int32)).tolist() == [2, -1, 0]
+
+
+def test_per_pixel_chain_on_hand_derived_cases():
+    # M lifts z by 100 and keeps w; a second M sets w' = 2 (never filtered: kept), a third w' = 0 (removed)
+    d = np.array([[0, 50, 200]], np.uint16)
+    lift = np.eye(4, dtype=np.float32)
+    lift[2, 3] = -100.
+    out, pts = fnp.frame_front(d, 0., 0., 1., lift, T)
+    # z' = d - 100: 50 -> -50 < -T kept; 200 -> 100 > -T filtered; 0 -> 0
+    assert out.tolist() == [[0, 50, 0]] and pts[0, 1].tolist() == [50., 0., -50., 1.] and not pts[0, 2].any()
+    w2 = np.eye(4, dtype=np.float32)
+    w2[3, 3] = 2.
+    out, pts = fnp.frame_front(d, 0., 0., 1., w2, T)
+    assert out.tolist() == [[0, 50, 200]] and pts[0, 2, 3] == 2.
+    w0 = np.eye(4, dtype=np.float32)
+    w0[3, 3] = 0.
+    out, pts = fnp.frame_front(d, 0., 0., 1., w0, T)
+    assert out.tolist() == [[0, 0, 0]] and pts[0, 2].tolist() == [400., 0., 200., 0.]
+    for M in (lift, w2, w0):
+        c_out, c_pts = fnp.chain(d, 0., 0., 1., M, T)
+        f_out, f_pts = fnp.frame_front(d, 0., 0., 1., M, T)
+        assert _eq(c_out, f_out) and _eq(c_pts, f_pts)
+    # deprojection: ((d * (x - ppx)) / f, (d * (y - ppy)) / f, d, 1); d == 0 leaves what pts held
+    held = np.full((1, 3, 4), 7., np.float32)
+    p = fnp.deproject(d, 1.5, -0.5, 2., held)
+    assert p[0, 0].tolist() == [7.] * 4
+    assert p[0, 2].tolist() == [np.float32(200. * (2 - 1.5)) / np.float32(2.), np.float32(200. * 0.5) / np.float32(2.), 200., 1.]
+
+
+def test_gaussian_restatement_ties_corners_and_saturation():
+    w = np.full((3, 3), 1 / 9, np.float32)
+    # a corner sees 4 taps (the rest are outside, skipped): 2 zeros and 2 non-zeros is a tie w0 == wn -> the average
+    d = np.array([[0, 10, 0], [30, 0, 0], [0, 0, 0]], np.uint16)
+    g = fnp.gaussian(d, w)
+    wn = np.float32(1 / 9) + np.float32(1 / 9)
+    assert g[0, 0] == int(np.floor((np.float32(10) * np.float32(1 / 9) + np.float32(30) * np.float32(1 / 9)) / wn))
+    assert g[2, 2] == 0                           # 4 taps, all 0
+    assert g[1, 1] == 0                           # 7 zeros against 2
+    # an all-zero weight window: 0 / 0 is NaN -> __float2uint_rd gives 0
+    assert fnp.gaussian(np.array([[5]], np.uint16), np.zeros((1, 1), np.float32)).tolist() == [[0]]
+    assert fnp.float2uint_rd(np.array([np.nan, -3.5, 65536.7, 1e20], np.float32)).tolist() == [0, 0, 65536, 4294967295]
+    # uint32 -> uint16 keeps the low bits: a quotient that rounds up to 65536 wraps to 0
+    assert fnp.gaussian(np.array([[65535]], np.uint16), np.array([[np.float32(1.0000001)]], np.float32)).dtype == np.uint16
+
+
+def test_candidate_draws_misses_duplicates_and_start_mat():
+    H, W = 4, 5
+    pts = np.zeros((H, W, 4), np.float32)
+    pts[..., 3] = 1
+    pts[..., 0] = np.arange(W)[None, :]
+    pts[..., 1] = np.arange(H)[:, None]
+    pts[..., 2] = 100.
+    pts[0, 0, 2] = 0.                         # z == 0: never taken
+    u = lambda r: np.float32((r + 0.5) / (W * H))     # noqa: E731 -- a draw that lands on raster index r
+    assert fnp.draw_index(np.float32(1.0), W, H) == -1          # r == N: a miss, not an out-of-bounds read
+    assert fnp.draw_index(u(7), W, H) == 7
+    rand = np.zeros((4, 32), np.float32)
+    rand[0, :4] = [1.0, u(1), u(7), u(11)]     # the miss is skipped
+    rand[1, :3] = [u(2), u(2), u(9)]           # a duplicate point: NaN axes
+    rand[2, :] = 1.0                           # nothing but misses: invalid
+    rand[3, :4] = [u(0), u(1), u(7), u(11)]    # z == 0 skipped: the same three as candidate 0
+    cand, counts = fnp.plane_candidates(rand, pts, W, H)
+    assert counts.tolist() == [0, 0, -1, 0]
+    assert np.isfinite(cand[0]).all() and _eq(cand[0], cand[3])
+    assert cand[0][12:].tolist() == [0, 0, 0, 1] and cand[0][[3, 7, 11]].tolist() == [-1., -0., -100.]
+    assert np.isnan(cand[1][:3]).all() and np.isnan(cand[2]).all()
+    counts = fnp.plane_inliers(pts, cand, T, counts)
+    assert counts[1] == 0 and counts[2] == -1
+    # start_mat replaces candidate 0 and wins a tie (np.argmax: the lowest index)
+    start = cand[3].reshape(4, 4) * 1
+    c2, k2 = fnp.plane_candidates(rand, pts, W, H, start_mat=start)
+    k2 = fnp.plane_inliers(pts, c2, T, k2)
+    assert k2[0] == k2[3] > 0 and fnp.plane_select(c2, k2)[1] == 0
+
+
+def test_ransac_restatement_finds_the_table_in_a_synthetic_scene():
+    H, W = 120, 212
+    depth, hand, fpp = scene(H, W, 105.)
+    plane, _ = _plane_for(depth, fpp)
+    z = fnp.transform(fnp.deproject(depth, *fpp[1:], fpp[0]), plane)[..., 2]
+    ok = depth > 0
+    assert (np.abs(z[ok & ~hand]) < T).mean() > 0.99
+    assert (z[ok & hand] < -T).all()
+    out, _ = fnp.frame_front(depth, fpp[1], fpp[2], fpp[0], plane, T)
+    assert (out[ok & hand] > 0).all() and (out[~hand] == 0).mean() > 0.99
+    # recentring: the camera's z axis meets the plane at its new origin (x', y' ~ 0 there)
+    q = fnp.transform_xyzw(plane, np.float32(0), np.float32(0), np.float32(600), np.float32(1))
+    assert abs(q[0]) < 400 and abs(q[1]) < 400
+
+
+def test_frontend_library_exports_its_header(rdf):
+    _lib = importlib.import_module("3d-beats_amd._lib")
+    _build = importlib.import_module("3d-beats_amd._build")
+    _build.build()
+    names = _declared(HEADER)
+    assert sorted(_lib.FRONTEND_SIGNATURES) == names
+    assert _exported(_build.FRONTEND_SO) == names
+    # the main library is not touched: it exports exactly what rdf_hip.h declares, and nothing of the front end
+    assert _exported(_build.SO) == sorted(_lib.SIGNATURES)
+    assert not set(names) & set(_lib.SIGNATURES)
+    lib = _lib.load_frontend()
+    assert lib.rdf_frontend_abi_version() == _lib.FRONTEND_ABI_VERSION
+    assert lib.rdf_frontend_build_id().decode() == _build.frontend_source_id()
+    assert lib.rdf_calibrate_plane_workspace_bytes(25000) == 25000 * 64 + 100000
+    assert lib.rdf_calibrate_plane_workspace_bytes(3) == 3 * 64 + 16
+    assert lib.rdf_calibrate_plane_workspace_bytes(0) == 0
+    assert b"NULL" in lib.rdf_frontend_error_string(-2)
+    blob = open(_build.FRONTEND_SO, "rb").read()
+    assert b"gfx950" in blob
+
+
+def test_frontend_header_is_plain_c(tmp_path):
+    gcc = shutil.which("gcc")
+    if gcc is None:
+        pytest.skip("no gcc")
+    src = tmp_path / "t.c"
+    src.write_text('#include "rdf_hip.h"\n#include "rdf_frontend.h"\n'
+                   'int main(void) { return rdf_frontend_abi_version() > 0 && sizeof(RdfPlaneResult) == 112 ? 0 : 1; }\n')
+    subprocess.check_call([gcc, "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-I",
+                           os.path.join(ROOT, "include"), str(src)])
+
+
+def test_device_array_set_takes_a_device_array(rdf, host_runtime):
+    """3d_bz.py:206 copies one depth buffer into another with `.cu().set(other.cu())`, as PyCUDA's GPUArray.set allows."""
+    a = rdf.DeviceArray((3, 5), np.uint16).set(np.arange(15, dtype=np.uint16).reshape(3, 5))
+    b = rdf.DeviceArray((3, 5), np.uint16).fill(0)
+    assert b.set(a) is b
+    assert np.array_equal(b.get(), np.arange(15).reshape(3, 5))
+    with pytest.raises(AssertionError):
+        rdf.DeviceArray((4, 5), np.uint16).set(a)
+
+
+def test_reference_alias_for_calibrated_plane(rdf):
+    assert "calibrated_plane" in rdf._REFERENCE_MODULE_NAMES
+    mod = importlib.import_module("3d-beats_amd.calibrated_plane")
+    assert rdf.CalibratedPlane is mod.CalibratedPlane
+    for name in ("is_set", "get_mat", "make", "make_async", "make_plane_candidates", "find_plane_ransac",
+                 "filter_points_by_plane"):
+        assert callable(getattr(mod.CalibratedPlane, name)), name
+    po = importlib.import_module("3d-beats_amd.cuda.points_ops").PointsOps
+    for name in ("deproject_points", "transform_points", "filter_points_by_plane",
+                 "remove_missing_3d_points_from_depth_image", "gaussian_depth_filter"):
+        assert callable(getattr(po, name)), name
+
+
+# ------------------------------------------------------------------ GPU ------------------------------------------------------
+def _fe():
+    return importlib.import_module("3d-beats_amd._lib").load_frontend()
+
+
+def _po():
+    return importlib.import_module("3d-beats_amd.cuda.points_ops").PointsOps()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,H,W", [(1, 480, 848), (3, 37, 61)])
+def test_stand_alone_kernels_match_the_restatement(n, H, W, rdf, gpu_runtime):
+    po = _po()
+    frames = [scene(H, W, W / 2., tilt_deg=15 + 5 * i, seed=i)[0] for i in range(n)]
+    depth = np.stack(frames)
+    fpp = (np.float32(W / 2.), np.float32(W / 2 - 0.7), np.float32(H / 2 + 0.3))
+    plane, _ = _plane_for(frames[0], fpp, G=500)
+    d = rdf.to_device(depth)
+    held = np.full(depth.shape + (4,), 3.25, np.float32)
+    pts = rdf.to_device(held)
+    po.deproject_points(np.array([n, W, H, -1], np.int32), np.array(fpp[1:], np.float32), fpp[0], d, pts,
+                        grid=(1, 1, 1), block=(1, 32, 32))
+    want = fnp.deproject(depth, fpp[1], fpp[2], fpp[0], held)
+    assert _eq(pts.get(), want)
+    want = fnp.deproject(depth, fpp[1], fpp[2], fpp[0])
+    pts.set(want)
+    po.transform_points(np.int32(n * H * W), pts, plane)
+    want = fnp.transform(want, plane)
+    assert _eq(pts.get(), want)
+    po.filter_points_by_plane(np.int32(n * H * W), np.float32(T), pts)
+    want = fnp.filter_by_plane(want, T)
+    assert _eq(pts.get(), want)
+    po.remove_missing_3d_points_from_depth_image(np.int32(n * H * W), pts, d)
+    want_d = fnp.remove_missing(want, depth)
+    assert _eq(d.get(), want_d)
+    for sigma, k in ((2.0, 5), (2.0, 41), (0.7, 3)):
+        out = rdf.GpuBuffer(depth.shape[1:], np.uint16)
+        src = rdf.GpuBuffer(depth.shape[1:], np.uint16, want_d[0])
+        po.gaussian_depth_filter(src, out, sigma=sigma, k_size=k)
+        w = importlib.import_module("3d-beats_amd.cuda.points_ops").gaussian_kernel(k, sigma)
+        assert _eq(out.cu().get(), fnp.gaussian(want_d[0], w)), (sigma, k)
+
+
+def _inliers_on_device(rdf, pts_np, cand_np, init):
+    fe = _fe()
+    s = rdf.get_runtime().stream()
+    pts, cand = rdf.to_device(pts_np), rdf.to_device(cand_np)
+    counts = rdf.to_device(init)
+    G = cand_np.shape[0]
+    assert fe.rdf_plane_inliers(G, T, pts_np.size // 4, pts.ptr, cand.ptr, counts.ptr, s) == 0
+    return counts.get()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("G,H,W", [(25000, 480, 848), (1, 7, 9), (67, 37, 61), (1001, 121, 211)])
+def test_candidates_counts_and_plane_match_the_restatement(G, H, W, rdf, gpu_runtime):
+    fe = _fe()
+    s = gpu_runtime.stream()
+    depth, hand, fpp = scene(H, W, W / 2.)
+    pts_np = fnp.deproject(depth, fpp[1], fpp[2], fpp[0])
+    rng = np.random.default_rng(G)
+    rand_np = rng.random((G, 32), dtype=np.float32)
+    rand_np[rng.random((G, 32)) < 0.02] = 1.0               # draws that would read past the end
+    if G > 2:
+        rand_np[2, :] = 1.0                                  # an invalid candidate
+        rand_np[1, 1] = rand_np[1, 0]                        # a duplicate draw
+    pts, rand = rdf.to_device(pts_np), rdf.to_device(rand_np)
+    cand = rdf.DeviceArray((G, 16), np.float32).fill(7)
+    counts = rdf.DeviceArray((G,), np.int32).fill(-7)
+    assert fe.rdf_make_plane_candidates(G, W, H, rand.ptr, pts.ptr, None, cand.ptr, counts.ptr, s) == 0
+    want_c, want_k = fnp.plane_candidates(rand_np, pts_np, W, H)
+    assert _eq(cand.get(), want_c) and np.array_equal(counts.get(), want_k)
+    assert fe.rdf_plane_inliers(G, T, H * W, pts.ptr, cand.ptr, counts.ptr, s) == 0
+    want_k = fnp.plane_inliers(pts_np, want_c, T, want_k)
+    assert np.array_equal(counts.get(), want_k)
+    plane = rdf.to_device(np.full(16, 5., np.float32))
+    res = rdf.DeviceArray((112,), np.uint8)
+    assert fe.rdf_plane_select(G, cand.ptr, counts.ptr, plane.ptr, res.ptr, s) == 0
+    rec = res.get().view(importlib.import_module("3d-beats_amd.calibrated_plane").RESULT_DTYPE)[0]
+    wp, wb, wc, c, st = fnp.plane_select(want_c, want_k, np.full(16, 5., np.float32))
+    assert (int(rec["best_index"]), int(rec["best_count"]), int(rec["status"])) == (wb, wc, st)
+    assert np.array_equal(rec["c"].view(np.uint64), c.view(np.uint64))
+    assert _eq(plane.get(), wp) and _eq(rec["plane"], wp)
+    # the one-call form, with a start matrix that wins its tie
+    ws = rdf.DeviceArray((int(fe.rdf_calibrate_plane_workspace_bytes(G)),), np.uint8)
+    start = rdf.to_device(want_c[wb].copy())
+    assert fe.rdf_calibrate_plane(G, T, W, H, rand.ptr, pts.ptr, start.ptr, ws.ptr, plane.ptr, res.ptr, s) == 0
+    rec = res.get().view(importlib.import_module("3d-beats_amd.calibrated_plane").RESULT_DTYPE)[0]
+    wc2, wk2 = fnp.plane_candidates(rand_np, pts_np, W, H, start_mat=want_c[wb])
+    wk2 = fnp.plane_inliers(pts_np, wc2, T, wk2)
+    assert np.array_equal(ws.get()[G * 64:G * 68].view(np.int32), wk2)
+    assert int(rec["best_index"]) == int(np.argmax(wk2)) and (G == 1 or wk2[0] == wk2.max()) and int(rec["best_index"]) == 0
+
+
+@pytest.mark.gpu
+def test_inlier_kernel_edge_points(rdf, gpu_runtime):
+    M = np.eye(4, dtype=np.float32).reshape(16)
+    pts = np.array([[0, 0, T, 1], [0, 0, -T, 1], [0, 0, np.nextafter(np.float32(T), 0), 1], [0, 0, -39.5, 1],
+                    [0, 0, 0, 2], [0, 0, 0, 0], [np.nan, 0, 0, 1], [0, np.inf, 0, 1]], np.float32)
+    far = M.copy()
+    far[11] = 1e6
+    nan = np.full(16, np.nan, np.float32)
+    cand = np.stack([M, far, nan, M])
+    init = np.array([0, 5, -1, 3], np.int32)
+    got = _inliers_on_device(rdf, pts, cand, init)
+    assert got.tolist() == fnp.plane_inliers(pts, cand, T, init).tolist() == [2, 5, -1, 5]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 3])
+def test_frame_front_matches_the_chain_and_the_restatement(n, rdf, gpu_runtime):
+    H, W = 480, 848
+    po = _po()
+    pom = importlib.import_module("3d-beats_amd.cuda.points_ops")
+    fe = _fe()
+    s = gpu_runtime.stream()
+    frames = [scene(H, W, 420., tilt_deg=20 + 2 * i, box_h=90 + 20 * i, seed=10 + i)[0] for i in range(n)]
+    depth = np.stack(frames)
+    _, _, fpp = scene(H, W, 420.)
+    plane, _ = _plane_for(frames[0], fpp, G=2000)
+    d = rdf.to_device(depth)
+    M = rdf.to_device(plane)
+    for sigma, k in ((None, 0), (2.0, 5), (2.0, 41)):
+        w = None if sigma is None else pom.gaussian_kernel(k, sigma)
+        wd = None if w is None else rdf.to_device(w)
+        out = rdf.DeviceArray(depth.shape, np.uint16).fill(1)
+        pts = rdf.DeviceArray(depth.shape + (4,), np.float32).fill(9)
+        assert fe.rdf_frame_front(d.ptr, n, W, H, fpp[1], fpp[2], fpp[0], M.ptr, T, None if wd is None else wd.ptr, k,
+                                  out.ptr, pts.ptr, s) == 0
+        want_d, want_p = fnp.frame_front(depth, fpp[1], fpp[2], fpp[0], plane, T, w)
+        got_d, got_p = out.get(), pts.get()
+        assert _eq(got_d, want_d) and _eq(got_p, want_p), (sigma, k)
+        assert (got_d > 0).sum() > 1000
+        # the five stand-alone launches in sequence, frame by frame (the Gaussian is a one-frame kernel)
+        for i in range(n):
+            di = rdf.to_device(depth[i])
+            pi = rdf.DeviceArray((H, W, 4), np.float32).fill(0)
+            po.deproject_points(np.array([1, W, H, -1], np.int32), np.array(fpp[1:], np.float32), fpp[0], di, pi)
+            po.transform_points(np.int32(H * W), pi, plane)
+            po.filter_points_by_plane(np.int32(H * W), np.float32(T), pi)
+            po.remove_missing_3d_points_from_depth_image(np.int32(H * W), pi, di)
+            if w is not None:                              # 3d_bz.py:205-211: copy to depth_image_2, filter back
+                d2 = rdf.DeviceArray((H, W), np.uint16).copy_from(di)
+                po.gaussian_depth_filter(d2, di, sigma=sigma, k_size=k)
+            assert _eq(di.get(), got_d[i]) and _eq(pi.get(), got_p[i]), (sigma, k, i)
+    # without the points output, and in place when the Gaussian is off
+    out = rdf.DeviceArray(depth.shape, np.uint16)
+    assert fe.rdf_frame_front(d.ptr, n, W, H, fpp[1], fpp[2], fpp[0], M.ptr, T, None, 0, d.ptr, None, s) == 0
+    assert _eq(d.get(), fnp.frame_front(depth, fpp[1], fpp[2], fpp[0], plane, T)[0])
+    assert fe.rdf_frame_front(d.ptr, n, W, H, fpp[1], fpp[2], fpp[0], M.ptr, T, wd.ptr, 41, d.ptr, None, s) == -1
+    assert fe.rdf_frame_front(d.ptr, n, W, H, fpp[1], fpp[2], fpp[0], M.ptr, T, wd.ptr, 43, out.ptr, None, s) == -1
+    assert fe.rdf_frame_front(None, n, W, H, fpp[1], fpp[2], fpp[0], M.ptr, T, None, 0, out.ptr, None, s) == -2
+
+
+@pytest.mark.gpu
+def test_calibrated_plane_make_as_the_reference_calls_it(rdf, gpu_runtime):
+    H, W = 480, 848
+    depth, hand, fpp = scene(H, W, 420.)
+    G = 25000
+    cp = rdf.CalibratedPlane(G, T, seed=3)
+    assert not cp.is_set()
+    pts = rdf.GpuBuffer((H, W, 4), np.float32, fnp.deproject(depth, fpp[1], fpp[2], fpp[0]))
+    rand = np.random.default_rng(4).random((G, 32), dtype=np.float32)
+    plane = cp.make(pts, (W, H), rand=rand)
+    want = fnp.calibrate(rand, pts.cu().get(), W, H, T)
+    assert _eq(plane.reshape(16), want[0]) and cp.is_set() and _eq(cp.get_mat(), plane)
+    # drawn on the device: a seeded generator repeats itself, and the plane separates the scene
+    a = rdf.CalibratedPlane(G, T, seed=11)
+    b = rdf.CalibratedPlane(G, T, seed=11)
+    pa, pb = a.make(pts, (W, H)), b.make(pts, (W, H))
+    assert _eq(pa, pb) and _eq(a.rand_cu.get(), b.rand_cu.get())
+    r = a.rand_cu.get()
+    assert (r >= 0).all() and (r < 1).all()
+    z = fnp.transform(pts.cu().get(), pa)[..., 2]
+    ok = depth > 0
+    assert (np.abs(z[ok & ~hand]) < T).mean() > 0.98 and (z[ok & hand] < -T).mean() > 0.98
+    # recalibration from the current plane (3d_bz.py:172-175): it competes as candidate 0
+    again = a.make(pts, (W, H), a.get_mat())
+    assert _eq(a.candidate_planes_cu.get()[0].reshape(16), pa.reshape(16))
+    assert int(a.result()["best_count"]) >= int(a.num_inliers_cu.get()[0]) > 0 and again is a.plane
+    # no plane at all: the reference's assert, and .plane stays
+    empty = rdf.GpuBuffer((H, W, 4), np.float32)
+    empty.cu().fill(0)
+    before = a.plane.copy()
+    with pytest.raises(AssertionError):
+        a.make(empty, (W, H))
+    assert _eq(a.plane, before) and _eq(a.plane_cu.get(), before)
+    # the three kernel attributes, with the reference's arguments
+    cand = rdf.DeviceArray((G, 4, 4), np.float32)
+    n_in = rdf.DeviceArray((G,), np.int32).fill(0)
+    rd = rdf.to_device(rand)
+    cp.make_plane_candidates(np.int32(G), np.int32(W), np.int32(H), rd, pts.cu(), cand, grid=(G // 32 + 1, 1, 1),
+                             block=(32, 1, 1))
+    wc, wk = fnp.plane_candidates(rand, pts.cu().get(), W, H)
+    assert _eq(cand.get().reshape(G, 16), wc)
+    cp.find_plane_ransac(np.int32(G), np.float32(T), np.int32(W * H), pts.cu(), cand, n_in, grid=(1, 1, 1), block=(1024, 1, 1))
+    assert np.array_equal(n_in.get(), fnp.plane_inliers(pts.cu().get(), wc, T))
+
+
+def _two_hands(H=480, W=848):
+    return scene(H, W, 420., tilt_deg=25., box_h=90., holes=0.01, seed=21, hand_scale=1.6)
+
+
+@pytest.mark.gpu
+def test_calibrate_and_front_end_replay_from_a_captured_graph(rdf, gpu_runtime):
+    import torch
+    H, W, G = 480, 848, 4000
+    depth, _, fpp = _two_hands()
+    fe = rdf.FrameFrontEnd((H, W), fpp, T, gauss_sigma=2.0, k_size=5, num_random_guesses=G, seed=5)
+    dbuf = rdf.GpuBuffer((H, W), np.uint16, depth)
+    out = rdf.GpuBuffer((H, W), np.uint16)
+    rand = rdf.to_device(np.random.default_rng(6).random((G, 32), dtype=np.float32))
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        fe.calibrate_async(dbuf, rand)                              # warm-up
+        fe.run(dbuf, out)
+    side.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        fe.calibrate_async(dbuf, rand)
+        fe.run(dbuf, out)
+    w = importlib.import_module("3d-beats_amd.cuda.points_ops").gaussian_kernel(5, 2.0)
+    for k in range(2):
+        frame, _, _ = scene(H, W, 420., tilt_deg=22. + 4 * k, box_h=70. + 10 * k, holes=0.01, seed=30 + k, hand_scale=1.6)
+        dbuf.cu().set(frame)
+        out.cu().fill(3)
+        graph.replay()
+        torch.cuda.synchronize()
+        plane = fnp.calibrate(rand.get(), fnp.deproject(frame, fpp[1], fpp[2], fpp[0]), W, H, T)[0]
+        assert _eq(fe.calibrated_plane.plane_cu.get().reshape(16), plane)
+        assert _eq(out.cu().get(), fnp.frame_front(frame, fpp[1], fpp[2], fpp[0], plane, T, w)[0])
+    del graph
+
+
+@pytest.mark.gpu
+def test_raw_depth_to_fingertip_heights_on_the_device(rdf, gpu_runtime):
+    """synthetic raw depth -> CalibratedPlane.make -> FrameFrontEnd.run -> HandGrouping -> HandPipeline, against the same
+    chain built from the restatements (frontend_numpy, grouping_numpy) feeding the same pipeline."""
+    H, W, R, L = 480, 848, 2, 3
+    pl = importlib.import_module("3d-beats_amd.pipeline")
+    pom = importlib.import_module("3d-beats_amd.cuda.points_ops")
+    synth = rdf.synth
+    depth, hand, fpp = _two_hands()
+    G = 25000
+    fe = rdf.FrameFrontEnd((H, W), fpp, T, gauss_sigma=2.0, k_size=5, num_random_guesses=G, seed=7)
+    rand = np.random.default_rng(8).random((G, 32), dtype=np.float32)
+    dbuf = rdf.GpuBuffer((H, W), np.uint16, depth)
+    plane = fe.calibrate(dbuf, rand=rand)
+    want_plane = fnp.calibrate(rand, fnp.deproject(depth, fpp[1], fpp[2], fpp[0]), W, H, T)[0]
+    assert _eq(plane.reshape(16), want_plane)
+    clean = rdf.GpuBuffer((H, W), np.uint16)
+    fe.run(dbuf, clean)
+    want_clean = fnp.frame_front(depth, fpp[1], fpp[2], fpp[0], want_plane, T, pom.gaussian_kernel(5, 2.0))[0]
+    hg = rdf.HandGrouping((H, W), L, 0.06)
+    groups = rdf.GpuBuffer((H >> L, W >> L), np.uint16)
+    hg.make_group_image(clean, groups)
+    want_groups, want_gi, _, _ = gnp.hand_groups(want_clean, L, 0.06)
+    assert want_gi[0, 0] > 0 and want_gi[1, 0] > 0
+    assert _eq(clean.cu().get(), want_clean) and _eq(groups.cu().get(), want_groups)
+    f0, f1 = synth.forest(3, 9, 4, "trained", 60), synth.forest(3, 10, 5, "trained", 70)
+    cfg = {"layers": [{"model": rdf.DecisionForest.from_numpy(f0)},
+                      {"model": rdf.DecisionForest.from_numpy(f1), "filter_model": 0, "filter_model_class": 3}],
+           "conditions": [[0, 1], [0, 2], [1, 3], [0, 3], [0, 4], [0, 5], [0, 6], [0, 7]],
+           "label_colors": [[10 * i, 255 - 10 * i, i, 255] for i in range(1, 8)]}
+    lf = rdf.LayeredDecisionForest(cfg, (H, W), R)
+    pipe = pl.HandPipeline(lf, (H, W), R, 0.75, 5, np.linspace(20., 60., 7).astype(np.float32), [3, 4, 5, 6, 7],
+                           (fpp[0], fpp[0], fpp[1], fpp[2]), plane, depth_mm_level=L)
+    ref_clean = rdf.GpuBuffer((H, W), np.uint16, want_clean)
+    ref_groups = rdf.GpuBuffer((H >> L, W >> L), np.uint16, want_groups)
+    for g_id, flip in ((1, False), (2, True)):
+        means, heights = pipe.run(clean, groups, g_id, flip)
+        labels = pipe.labels_image.cu().get()
+        means_ref, heights_ref = pipe.run(ref_clean, ref_groups, g_id, flip)
+        assert np.array_equal(labels, pipe.labels_image.cu().get())
+        assert (labels != 65535).sum() > 500
+        assert np.array_equal(means.view(np.uint64), means_ref.view(np.uint64))
+        assert np.array_equal(heights.view(np.uint64), heights_ref.view(np.uint64))
+
+
+@pytest.mark.gpu
+def test_the_apps_front_end_calls_run_on_the_aliased_modules(rdf, gpu_runtime):
+    """The call sequence of the app's tick() from the depth upload to the Gaussian (3d_bz.py:163-212), made the way the
+    app makes it, through the names `from cuda.points_ops import *`, `from calibrated_plane import *`,
+    `from engine.buffer import GpuBuffer` and `from util import make_grid` resolve to after install_reference_aliases()."""
+    import sys
+    names = rdf._REFERENCE_MODULE_NAMES
+    before = {n: sys.modules.get(n) for n in names}
+    try:
+        rdf.install_reference_aliases(force=True)
+        cp_mod, po_mod = importlib.import_module("calibrated_plane"), importlib.import_module("cuda.points_ops")
+        GpuBuffer, make_grid = importlib.import_module("engine.buffer").GpuBuffer, importlib.import_module("util").make_grid
+        DIM_Y, DIM_X, T_ = 480, 848, 40.
+        depth_np, _, (focal, ppx, ppy) = _two_hands()
+        FOCAL, PP = focal, np.array([ppx, ppy], dtype=np.float32)
+        points_ops, calibrated_plane = po_mod.PointsOps(), cp_mod.CalibratedPlane(25000, T_, seed=11)
+        pts_cu = GpuBuffer((DIM_Y, DIM_X, 4), dtype=np.float32)
+        pts_cu.cu().fill(0)
+        depth_image = GpuBuffer((DIM_Y, DIM_X), dtype=np.uint16)
+        depth_image_2 = GpuBuffer((DIM_Y, DIM_X), dtype=np.uint16)
+        depth_image.cu().set(depth_np)
+        block_dim = (1, 32, 32)
+        points_ops.deproject_points(np.array([1, DIM_X, DIM_Y, -1], dtype=np.int32), PP, np.float32(FOCAL), depth_image.cu(),
+                                    pts_cu.cu(), grid=make_grid((1, DIM_X, DIM_Y), block_dim), block=block_dim)
+        assert not calibrated_plane.is_set()
+        calibrated_plane.make(pts_cu, (DIM_X, DIM_Y))
+        rand = calibrated_plane.rand_cu.get()
+        block_dim2 = (1024, 1, 1)
+        grid_dim2 = make_grid((DIM_X * DIM_Y, 1, 1), block_dim2)
+        points_ops.transform_points(np.int32(DIM_X * DIM_Y), pts_cu.cu(), calibrated_plane.get_mat(), grid=grid_dim2,
+                                    block=block_dim2)
+        calibrated_plane.filter_points_by_plane(np.int32(DIM_X * DIM_Y), np.float32(T_), pts_cu.cu(), grid=grid_dim2,
+                                                block=block_dim2)
+        points_ops.remove_missing_3d_points_from_depth_image(np.int32(DIM_X * DIM_Y), pts_cu.cu(), depth_image.cu(),
+                                                             grid=grid_dim2, block=block_dim2)
+        depth_image_2.cu().set(depth_image.cu())
+        points_ops.gaussian_depth_filter(depth_image_2, depth_image, sigma=2.0, k_size=5)
+        plane = fnp.calibrate(rand, fnp.deproject(depth_np, PP[0], PP[1], np.float32(FOCAL)), DIM_X, DIM_Y, T_)[0]
+        assert _eq(calibrated_plane.get_mat().reshape(16), plane)
+        w = po_mod.gaussian_kernel(5, 2.0)
+        want_d, want_p = fnp.chain(depth_np, PP[0], PP[1], np.float32(FOCAL), plane, T_, w)
+        assert _eq(depth_image.cu().get(), want_d) and _eq(pts_cu.cu().get(), want_p)
+        assert _eq(want_d, fnp.frame_front(depth_np, PP[0], PP[1], np.float32(FOCAL), plane, T_, w)[0])
+        assert (want_d > 0).sum() > 10000
+    finally:
+        for n, m in before.items():
+            if m is None:
+                sys.modules.pop(n, None)
+            else:
+                sys.modules[n] = m
