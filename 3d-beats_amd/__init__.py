@@ -11,6 +11,8 @@ inference path.
 from . import synth  # noqa: F401
 from ._lib import RdfError, library_path  # noqa: F401
 from .calibrated_plane import CalibratedPlane  # noqa: F401
+from .color_labels import ColorLabeler  # noqa: F401
+from .data_convert import RecordingConverter  # noqa: F401
 from .decision_tree import (DecisionForest, DecisionTree, DecisionTreeEvaluator,  # noqa: F401
                             DecisionTreeTrainer, LayeredDecisionForest)
 from .device import DeviceArray, HipRuntime, device_ptr, get_runtime, host_mapped_array, set_runtime, to_device  # noqa: F401
@@ -48,6 +50,6 @@ def install_reference_aliases(force=False):
 
 
 __all__ = ["DecisionTree", "DecisionForest", "LayeredDecisionForest", "DecisionTreeEvaluator", "DecisionTreeTrainer",
-           "GpuBuffer", "CalibratedPlane", "FrameFrontEnd", "HandGrouping", "HandPipeline", "HostFramesEvaluator",
+           "GpuBuffer", "CalibratedPlane", "ColorLabeler", "RecordingConverter", "FrameFrontEnd", "HandGrouping", "HandPipeline", "HostFramesEvaluator",
            "DeviceArray", "HipRuntime", "MAX_UINT16", "RdfError", "device_ptr", "get_runtime", "set_runtime",
            "to_device", "host_mapped_array", "library_path", "synth", "install_reference_aliases"]

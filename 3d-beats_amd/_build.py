@@ -1,4 +1,5 @@
-"""Builds csrc/librdf_hip.so and csrc/librdf_frontend.so for gfx950 with hipcc (cross-compiles without a GPU)."""
+"""Builds csrc/librdf_hip.so, csrc/librdf_frontend.so and csrc/librdf_labels.so for gfx950 with hipcc (cross-compiles
+without a GPU)."""
 import hashlib
 import os
 import shutil
@@ -14,6 +15,10 @@ SO = os.path.join(HERE, "csrc", "librdf_hip.so")
 FRONTEND_SOURCES = [os.path.join(HERE, "csrc", "frontend_hip.hip")]
 FRONTEND_HEADERS = [os.path.join(HERE, "..", "include", "rdf_frontend.h")]
 FRONTEND_SO = os.path.join(HERE, "csrc", "librdf_frontend.so")
+# glove-colour recordings to training labels (include/rdf_labels.h): the third library, on the same terms
+LABELS_SOURCES = [os.path.join(HERE, "csrc", "labels_hip.hip")]
+LABELS_HEADERS = [os.path.join(HERE, "..", "include", "rdf_labels.h")]
+LABELS_SO = os.path.join(HERE, "csrc", "librdf_labels.so")
 
 # No -ffast-math, no -fgpu-flush-denormals-to-zero: the fp32 divide must stay IEEE-correct
 # and denormals must be kept for bit-exact parity (see rdf_hip.hip header).
@@ -44,6 +49,10 @@ def source_id(files=None):
 
 def frontend_source_id():
     return source_id(FRONTEND_SOURCES + FRONTEND_HEADERS)
+
+
+def labels_source_id():
+    return source_id(LABELS_SOURCES + LABELS_HEADERS)
 
 
 def built_id(path=None):
@@ -77,6 +86,13 @@ def frontend_is_stale():
     return sources_present(FRONTEND_SOURCES + FRONTEND_HEADERS) and built_id(FRONTEND_SO) != frontend_source_id()
 
 
+def labels_is_stale():
+    """The same for csrc/librdf_labels.so."""
+    if not os.path.exists(LABELS_SO):
+        return True
+    return sources_present(LABELS_SOURCES + LABELS_HEADERS) and built_id(LABELS_SO) != labels_source_id()
+
+
 def _compile(so, sources, sid, verbose):
     cmd = [hipcc()] + HIPCC_FLAGS + [f'-DRDF_BUILD_ID="{sid}"', "-o", so + ".tmp"] + sources
     if verbose:
@@ -86,11 +102,13 @@ def _compile(so, sources, sid, verbose):
 
 
 def build(force=False, verbose=False):
-    """Compile both HIP libraries in-tree (each only when stale).  Returns the path of the main one, librdf_hip.so."""
+    """Compile the three HIP libraries in-tree (each only when stale).  Returns the path of the main one, librdf_hip.so."""
     if force or is_stale():
         _compile(SO, SOURCES, source_id(), verbose)
     if force or frontend_is_stale():
         _compile(FRONTEND_SO, FRONTEND_SOURCES, frontend_source_id(), verbose)
+    if force or labels_is_stale():
+        _compile(LABELS_SO, LABELS_SOURCES, labels_source_id(), verbose)
     return SO
 
 

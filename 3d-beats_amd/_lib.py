@@ -1,5 +1,5 @@
-"""ctypes binding of csrc/librdf_hip.so (the C ABI declared in include/rdf_hip.h) and of csrc/librdf_frontend.so (the
-depth front end, include/rdf_frontend.h).
+"""ctypes binding of csrc/librdf_hip.so (the C ABI declared in include/rdf_hip.h), of csrc/librdf_frontend.so (the
+depth front end, include/rdf_frontend.h) and of csrc/librdf_labels.so (glove colours to labels, include/rdf_labels.h).
 
 This is the only place the shared libraries are opened.  There is no CPU fallback: a missing
 library, or a machine without a HIP device, raises.
@@ -245,6 +245,68 @@ def load_frontend():
 def check_frontend(lib, code, what):
     if code != 0:
         msg = lib.rdf_frontend_error_string(int(code))
+        msg = msg.decode() if isinstance(msg, bytes) else str(msg)
+        raise RdfError(f"{what} failed: {msg} (code {code})")
+
+
+# name -> (restype, argtypes); every symbol include/rdf_labels.h declares
+LABELS_SIGNATURES = {
+    "rdf_split_pixels_by_nearest_color": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "rdf_apply_point_mapping": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
+    "rdf_depths_from_points": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
+    "rdf_color_mapping_workspace_bytes": (_c_size_t, [_c_int, _c_int]),
+    "rdf_make_color_mapping": (_c_int, [_c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                        _c_void_p]),
+    "rdf_label_frame": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p,
+                                 _c_void_p, _c_void_p]),
+    "rdf_mask_color_image": (_c_int, [_c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p]),
+    "rdf_labels_abi_version": (_c_int, []),
+    "rdf_labels_build_id": (ctypes.c_char_p, []),
+    "rdf_labels_error_string": (ctypes.c_char_p, [_c_int]),
+}
+
+LABELS_ABI_VERSION = 1
+_labels = None
+
+
+def labels_library_path():
+    return _build.LABELS_SO
+
+
+def load_labels():
+    """Open librdf_labels.so and type every entry point, on the terms of load_frontend()."""
+    global _labels
+    if _labels is not None:
+        return _labels
+    path = labels_library_path()
+    if not os.path.exists(path):
+        raise RdfError(f"{path} is missing: build it first (python __graft_entry__.py build, "
+                       "or python 3d-beats_amd/_build.py). There is no CPU fallback.")
+    lib = ctypes.CDLL(path)
+    for name, (res, args) in LABELS_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    if lib.rdf_labels_abi_version() != LABELS_ABI_VERSION:
+        raise RdfError(f"librdf_labels.so ABI {lib.rdf_labels_abi_version()} != expected {LABELS_ABI_VERSION}; rebuild")
+    got = lib.rdf_labels_build_id()
+    got = got.decode() if isinstance(got, bytes) else str(got)
+    files = _build.LABELS_SOURCES + _build.LABELS_HEADERS
+    if _build.sources_present(files) and got != _build.labels_source_id():
+        msg = (f"{path} was built from other sources (build id {got}, sources {_build.labels_source_id()}): rebuild it "
+               "(python __graft_entry__.py build).")
+        if os.environ.get("RDF_ALLOW_STALE_LIBRARY") == "1":
+            import warnings
+            warnings.warn(msg)
+        else:
+            raise RdfError(msg)
+    _labels = lib
+    return lib
+
+
+def check_labels(lib, code, what):
+    if code != 0:
+        msg = lib.rdf_labels_error_string(int(code))
         msg = msg.decode() if isinstance(msg, bytes) else str(msg)
         raise RdfError(f"{what} failed: {msg} (code {code})")
 

@@ -5,7 +5,9 @@ src/3d_bz.py:396-456; src/run_live_layered.py:117-122): positional arguments as 
 touch the forest's input and output live here, and the three around the hand grouping (8f-3: shrink_image,
 write_pixel_groups_to_stencil_image, grow_groups), and the five of the depth front end (deproject_points,
 transform_points, filter_points_by_plane, remove_missing_3d_points_from_depth_image, gaussian_depth_filter; they live in
-librdf_frontend.so, and frontend.FrameFrontEnd fuses them).  Mesh generation stays out of scope."""
+librdf_frontend.so, and frontend.FrameFrontEnd fuses them), and the three of the glove-colour converter
+(split_pixels_by_nearest_color, apply_point_mapping, depths_from_points; librdf_labels.so, fused by
+color_labels.ColorLabeler).  Mesh generation stays out of scope."""
 import numpy as np
 
 from .. import _lib
@@ -30,6 +32,7 @@ class PointsOps:
         self._rt = get_runtime()
         self._lib = self._rt.lib
         self._fe = None
+        self._lb = None
         self.MAX_FILTER_SIZE = MAX_FILTER_SIZE
         self._gaussian_filter = None
         self._cached_filter_params = None
@@ -41,6 +44,18 @@ class PointsOps:
 
     def _ok_fe(self, rc, name, *touched):
         _lib.check_frontend(self._frontend(), rc, name)
+        for t in touched:
+            t = t.cu() if hasattr(t, "cu") else t
+            if hasattr(t, "mark_dirty"):
+                t.mark_dirty()
+
+    def _labels(self):
+        if self._lb is None:
+            self._lb = _lib.load_labels()
+        return self._lb
+
+    def _ok_lb(self, rc, name, *touched):
+        _lib.check_labels(self._labels(), rc, name)
         for t in touched:
             t = t.cu() if hasattr(t, "cu") else t
             if hasattr(t, "mark_dirty"):
@@ -151,3 +166,26 @@ class PointsOps:
         self._ok_fe(fe.rdf_gaussian_depth_filter(int(dim_x), int(dim_y), int(k_size), self._gaussian_filter.ptr,
                                                  device_ptr(d_in), device_ptr(d_out), self._rt.stream()),
                     "rdf_gaussian_depth_filter", d_out)
+
+    # ---- glove colours to labels, kernel for kernel (live_data_convert.py:179-187, 377-382, 434-441); ColorLabeler fuses it ----
+    def split_pixels_by_nearest_color(self, dim_x, dim_y, num_colors, colors, color_image, pixel_counts_per_group, grid=None,
+                                      block=None):
+        """Adds onto pixel_counts_per_group uint64 [K, 5] = (pixels, sum r, sum g, sum b, sum cost as a float64)."""
+        lb = self._labels()
+        self._ok_lb(lb.rdf_split_pixels_by_nearest_color(int(dim_x), int(dim_y), int(num_colors), device_ptr(colors),
+                                                         device_ptr(color_image), device_ptr(pixel_counts_per_group),
+                                                         self._rt.stream()),
+                    "rdf_split_pixels_by_nearest_color", pixel_counts_per_group)
+
+    def apply_point_mapping(self, dim_x, dim_y, num_colors, colors, color_image, grid=None, block=None):
+        lb = self._labels()
+        self._ok_lb(lb.rdf_apply_point_mapping(int(dim_x), int(dim_y), int(num_colors), device_ptr(colors),
+                                               device_ptr(color_image), self._rt.stream()),
+                    "rdf_apply_point_mapping", color_image)
+
+    def depths_from_points(self, imgs_dim, imgs, pts, grid=None, block=None):
+        """imgs_dim = (num_images, dim_x, dim_y, -1) int32 (points_ops.cu:39-63): depth = (uint16)z where w > 0."""
+        n, dim_x, dim_y = (int(v) for v in np.asarray(imgs_dim).reshape(-1)[:3])
+        lb = self._labels()
+        self._ok_lb(lb.rdf_depths_from_points(n, dim_x, dim_y, device_ptr(imgs), device_ptr(pts), self._rt.stream()),
+                    "rdf_depths_from_points", imgs)

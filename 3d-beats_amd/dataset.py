@@ -120,8 +120,8 @@ class DecisionTreeDatasetConfig:
 
 
 def write_dataset(dataset_dir, depth, labels, id_to_color):
-    """Writes a dataset directory in the layout above (used by tests and tools; the reference's writer is
-    its GL data generator).  depth, labels: uint16 [N, H, W]; id_to_color: {id: [r, g, b, a]} without id 0."""
+    """Writes a dataset directory in the layout above (used by tests and tools; data_convert.RecordingConverter
+    writes the same layout from a recording, as the reference's live_data_convert.py does).  depth, labels: uint16 [N, H, W]; id_to_color: {id: [r, g, b, a]} without id 0."""
     from PIL import Image
     os.makedirs(dataset_dir, exist_ok=True)
     n, h, w = depth.shape

@@ -1,0 +1,531 @@
+"""Glove colours to labels (librdf_labels.so, include/rdf_labels.h; PointsOps.split_pixels_by_nearest_color /
+apply_point_mapping / depths_from_points, ColorLabeler, RecordingConverter) against the integer restatement in
+tests/labels_numpy.py.  The CPU tests pin the restatement to cases worked by hand from the reference's text; every GPU
+comparison is bit for bit, with no pixel or case left out.
+
+The stand-in runtime of tests/fake_runtime.py answers librdf_hip.so's entry points from the CPU oracle and has none of this
+library's, so PointsOps' new methods and ColorLabeler are exercised by the GPU tests only."""
+import importlib
+import json
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import frontend_numpy as fnp
+import labels_numpy as lnp
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "rdf_labels.h")
+PALETTE8 = np.array([[220, 40, 40], [40, 200, 60], [50, 60, 230], [230, 220, 50], [200, 50, 210], [40, 210, 220],
+                     [250, 140, 30], [120, 120, 120]], np.uint8)
+
+
+def _declared(path):
+    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(rdf_[a-z0-9_]+)\s*\(", text)))
+
+
+def _exported(so):
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or "/opt/rocm/lib/llvm/bin/llvm-nm"
+    out = subprocess.run([nm, "-D", "--defined-only", so], capture_output=True, text=True, check=True).stdout
+    return sorted({l.split()[-1] for l in out.splitlines() if l.split() and l.split()[-1].startswith("rdf_")})
+
+
+def _px(*rows):
+    return np.array(rows, np.uint8).reshape(1, -1, 3)
+
+
+# ------------------------------------------------------------------ CPU ------------------------------------------------------
+def test_ties_go_to_the_lower_index_and_only_black_is_skipped():
+    colors = np.array([[10, 0, 0], [30, 0, 0], [20, 100, 0]], np.uint8)
+    # (20, 0, 0) is 100 from colours 0 and 1: the first stands.  (0, 0, 0) is skipped, (1, 0, 0) is not.
+    img = _px([20, 0, 0], [0, 0, 0], [1, 0, 0])
+    best, cost = lnp.nearest_int(colors, img[0])
+    assert best.tolist() == [0, 0, 0] and cost.tolist() == [100, 100, 81]
+    assert lnp.skipped(img[0]).tolist() == [False, True, False]
+    assert lnp.split_counts(colors, img).tolist() == [[2, 21, 0, 0, 181], [0] * 5, [0] * 5]
+    assert lnp.apply_point_mapping(colors, img)[0].tolist() == [[10, 0, 0], [0, 0, 0], [10, 0, 0]]
+    # with the tied colours swapped the tie still goes to index 0 (the other two pixels are nearer to (10, 0, 0), now index 1)
+    assert lnp.nearest_int(colors[[1, 0, 2]], img[0])[0].tolist() == [0, 1, 1]
+
+
+def test_update_truncates_and_an_empty_group_becomes_black():
+    counts = np.array([[3, 10, 20, 767, 5], [0, 0, 0, 0, 0], [2, 509, 1, 2, 0]], np.int64)
+    assert lnp.update(counts).tolist() == [[3, 6, 255], [0, 0, 0], [254, 0, 1]]
+    # the reference's own expression on this machine: the fp64 quotient, NaN for 0 / 0, cast to uint8
+    with np.errstate(all="ignore"):
+        ref = (counts[:, 1:4].T / counts[:, 0]).T.astype(np.uint8)
+    assert ref.tolist() == lnp.update(counts).tolist()
+
+
+def test_cost_of_a_try_is_its_last_assignment_against_the_colours_before_the_update():
+    # two pixels, one colour at (10, 0, 0): distances 10^2 and 30^2 -> cost 1000; the colour returned is their mean (30, 0, 0),
+    # against which the cost would have been 200
+    img = _px([20, 0, 0], [40, 0, 0])
+    best, bt, costs, finals = lnp.make_color_mapping(img, np.array([[[10, 0, 0]]], np.uint8), 1)
+    assert best.tolist() == [[30, 0, 0]] and bt == 0 and costs.tolist() == [1000.]
+    # a second iteration measures against (30, 0, 0)
+    assert lnp.make_color_mapping(img, np.array([[[10, 0, 0]]], np.uint8), 2)[2].tolist() == [200.]
+
+
+def test_best_try_first_of_equals_and_a_later_strictly_cheaper_one():
+    img = _px([20, 0, 0], [40, 0, 0])
+    init = np.array([[[10, 0, 0]], [[50, 0, 0]], [[10, 0, 0]]], np.uint8)        # costs 1000, 1000, 1000
+    best, bt, costs, _ = lnp.make_color_mapping(img, init, 1)
+    assert costs.tolist() == [1000., 1000., 1000.] and bt == 0
+    init = np.array([[[10, 0, 0]], [[50, 0, 0]], [[30, 0, 0]], [[30, 0, 0]]], np.uint8)   # 1000, 1000, 200, 200
+    best, bt, costs, _ = lnp.make_color_mapping(img, init, 1)
+    assert costs.tolist() == [1000., 1000., 200., 200.] and bt == 2 and best.tolist() == [[30, 0, 0]]
+
+
+def test_duplicate_mapping_colours_take_the_highest_label_and_a_black_entry_labels_the_background():
+    mapping = np.array([[200, 0, 0], [0, 200, 0], [200, 0, 0], [0, 0, 0]], np.uint8)
+    img = _px([190, 5, 0], [0, 0, 0], [10, 190, 0], [3, 3, 3])
+    snapped, labels, rgba, _ = lnp.label_frame(mapping, img)
+    # the snap picks index 0 of the duplicates, the label is 3; black -- background, and (3, 3, 3) snapped to the black
+    # entry -- carries label 4
+    assert snapped[0].tolist() == [[200, 0, 0], [0, 0, 0], [0, 200, 0], [0, 0, 0]]
+    assert labels[0].tolist() == [3, 4, 2, 4]
+    assert rgba[0].tolist() == [[200, 0, 0, 255], [0, 0, 0, 0], [0, 200, 0, 255], [0, 0, 0, 0]]
+    # without a black entry the background is 0
+    assert lnp.label_frame(mapping[:3], img)[1][0].tolist() == [3, 0, 2, 3]
+
+
+def test_mask_keeps_only_the_mask_label_and_depth_zero_becomes_maxuint():
+    mapping = np.array([[200, 0, 0], [0, 200, 0]], np.uint8)
+    img = _px([190, 5, 0], [10, 190, 0], [180, 0, 0])
+    mask = np.array([[3, 2, 3]], np.uint16)
+    depth = np.array([[0, 700, 65535]], np.uint16)
+    snapped, labels, rgba, d = lnp.label_frame(mapping, img, depth, mask, 3)
+    assert labels[0].tolist() == [1, 0, 1] and snapped[0, 1].tolist() == [0, 0, 0] and rgba[0, 1].tolist() == [0, 0, 0, 0]
+    assert d[0].tolist() == [65535, 700, 65535]
+    # a mask map that the forest left at its pre-fill of 0 blacks the frame out
+    assert not lnp.label_frame(mapping, img, depth, np.zeros((1, 3), np.uint16), 3)[1].any()
+
+
+def test_depths_from_points_restatement():
+    pts = np.array([[[0, 0, 500, 0], [0, 0, 500, 2], [0, 0, 12.9, 1], [0, 0, 7, -1], [0, 0, -3.5, 1], [0, 0, 1e6, 1],
+                     [0, 0, np.nan, 1], [0, 0, 9, np.nan]]], np.float32)
+    depth = np.full((1, 8), 77, np.uint16)
+    assert lnp.depths_from_points(depth, pts)[0].tolist() == [77, 500, 12, 77, 0, 65535, 0, 77]
+
+
+def test_integer_and_fp32_nearest_colour_agree_on_every_pixel_value():
+    """The reference computes the distance in fp32 (points_ops.cu:232-236); all 256^3 pixel values against a fixed table
+    with a duplicate and near-ties give the same winner and the same distance in integers."""
+    table = np.array([[0, 0, 0], [255, 255, 255], [128, 127, 129], [127, 128, 129], [128, 127, 129], [1, 254, 3],
+                      [200, 13, 77], [64, 64, 64]], np.uint8)
+    g, b = np.meshgrid(np.arange(256, dtype=np.uint8), np.arange(256, dtype=np.uint8), indexing="ij")
+    for r in range(256):
+        px = np.stack([np.full_like(g, r), g, b], -1).reshape(-1, 3)
+        bi, ci = lnp.nearest_int(table, px)
+        bf, cf = lnp.nearest_f32(table, px)
+        assert np.array_equal(bi, bf) and np.array_equal(ci.astype(np.float32), cf), r
+
+
+def test_labels_library_exports_its_header(rdf):
+    _lib = importlib.import_module("3d-beats_amd._lib")
+    _build = importlib.import_module("3d-beats_amd._build")
+    _build.build()
+    names = _declared(HEADER)
+    assert sorted(_lib.LABELS_SIGNATURES) == names
+    assert _exported(_build.LABELS_SO) == names
+    for must in ("rdf_split_pixels_by_nearest_color", "rdf_apply_point_mapping", "rdf_depths_from_points",
+                 "rdf_color_mapping_workspace_bytes", "rdf_make_color_mapping", "rdf_label_frame", "rdf_labels_abi_version",
+                 "rdf_labels_build_id", "rdf_labels_error_string"):
+        assert must in names
+    # the other two libraries are not touched
+    assert _exported(_build.SO) == sorted(_lib.SIGNATURES)
+    assert _exported(_build.FRONTEND_SO) == sorted(_lib.FRONTEND_SIGNATURES)
+    assert not set(names) & (set(_lib.SIGNATURES) | set(_lib.FRONTEND_SIGNATURES))
+    lib = _lib.load_labels()
+    assert lib.rdf_labels_abi_version() == _lib.LABELS_ABI_VERSION == 1
+    assert lib.rdf_labels_build_id().decode() == _build.labels_source_id() == _build.built_id(_build.LABELS_SO)
+    assert _build.built_id(_build.SO) == _build.source_id() and _build.built_id(_build.FRONTEND_SO) == _build.frontend_source_id()
+    assert lib.rdf_color_mapping_workspace_bytes(8, 4) == 96 + 8 * 4 * 40
+    assert lib.rdf_color_mapping_workspace_bytes(1, 1) == 8 + 40
+    assert lib.rdf_color_mapping_workspace_bytes(9, 4) == 0 and lib.rdf_color_mapping_workspace_bytes(8, 17) == 0
+    assert lib.rdf_color_mapping_workspace_bytes(8, 16) > 0
+    assert b"NULL" in lib.rdf_labels_error_string(-2)
+    assert b"gfx950" in open(_build.LABELS_SO, "rb").read()
+    # rejected arguments launch nothing, so they can be checked without a device
+    assert lib.rdf_split_pixels_by_nearest_color(4, 4, 0, None, None, None, None) == -1
+    assert lib.rdf_split_pixels_by_nearest_color(4, 4, 17, None, None, None, None) == -1
+    assert lib.rdf_split_pixels_by_nearest_color(4, 4, 3, None, None, None, None) == -2
+    assert lib.rdf_make_color_mapping(16, None, 9, 1, 3, None, None, None, None, None) == -1
+    assert lib.rdf_make_color_mapping(16, None, 8, 0, 3, None, None, None, None, None) == -1
+    assert lib.rdf_make_color_mapping(16, None, 8, 1, 3, None, None, None, None, None) == -2
+    assert lib.rdf_label_frame(4, 4, 0, None, None, None, 0, None, None, None, None) == -1
+    assert lib.rdf_label_frame(4, 4, 2, None, None, None, 0, None, None, None, None) == -2
+    assert lib.rdf_apply_point_mapping(4, 4, 0, None, None, None) == -1
+    assert lib.rdf_depths_from_points(1, 4, 4, None, None, None) == -2
+
+
+def test_labels_header_is_plain_c(tmp_path):
+    gcc = shutil.which("gcc")
+    if gcc is None:
+        pytest.skip("no gcc")
+    src = tmp_path / "t.c"
+    src.write_text('#include "rdf_hip.h"\n#include "rdf_frontend.h"\n#include "rdf_labels.h"\n'
+                   'int main(void) { return rdf_labels_abi_version() > 0 && sizeof(RdfColorMappingResult) == 80 ? 0 : 1; }\n')
+    subprocess.check_call([gcc, "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-I",
+                           os.path.join(ROOT, "include"), str(src)])
+    src.write_text('#include "rdf_labels.h"\nint main(void) { return RDF_LABELS_MAX_COLORS >= 16 && RDF_LABELS_MAX_TRIES >= 8 ? 0 : 1; }\n')
+    subprocess.check_call([gcc, "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-I",
+                           os.path.join(ROOT, "include"), str(src)])
+
+
+def test_the_new_names_are_public(rdf):
+    po = importlib.import_module("3d-beats_amd.cuda.points_ops").PointsOps
+    for name in ("split_pixels_by_nearest_color", "apply_point_mapping", "depths_from_points"):
+        assert callable(getattr(po, name)), name
+    for name in ("make_color_mapping", "make_color_mapping_async", "is_set", "label_frame", "id_to_color"):
+        assert callable(getattr(rdf.ColorLabeler, name)), name
+    assert callable(rdf.RecordingConverter.convert) and {"ColorLabeler", "RecordingConverter"} <= set(rdf.__all__)
+    cl = importlib.import_module("3d-beats_amd.color_labels")
+    assert cl.RESULT_DTYPE.itemsize == 80 and (cl.MAX_COLORS, cl.MAX_TRIES) == (16, 8)
+
+
+def _truth_scene(H=120, W=212, K=4, noise=8, seed=3):
+    palette = PALETTE8[:K]
+    d = np.sqrt(((palette[:, None].astype(np.int64) - palette[None].astype(np.int64)) ** 2).sum(-1))
+    D = d[~np.eye(K, dtype=bool)].min()
+    assert 2 * noise * np.sqrt(3) < D
+    img, painted = lnp.glove_scene(H, W, palette, noise, seed)
+    return palette, img, painted
+
+
+def test_restatement_recovers_a_painted_glove_scene():
+    """Palette colours pairwise further apart than twice the noise radius, one try started at the palette: the restatement
+    alone gives back the painted classes (the mapping keeps the palette's order, so the permutation is the identity)."""
+    palette, img, painted = _truth_scene()
+    assert all((painted == k + 1).sum() > 100 for k in range(len(palette)))
+    mapping, bt, costs, _ = lnp.make_color_mapping(img, palette[None], 32)
+    assert np.abs(mapping.astype(int) - palette.astype(int)).max() <= 2
+    _, labels, rgba, _ = lnp.label_frame(mapping, img)
+    assert np.array_equal(labels, painted)
+    assert np.array_equal(rgba[..., 3] == 255, painted > 0)
+
+
+# ------------------------------------------------------------------ GPU ------------------------------------------------------
+def _lb():
+    return importlib.import_module("3d-beats_amd._lib").load_labels()
+
+
+def _po():
+    return importlib.import_module("3d-beats_amd.cuda.points_ops").PointsOps()
+
+
+def _frame(H, W, K, seed, black=0.5):
+    """Random colours near K centres, `black` of the pixels exactly black, a few pixels with a single 1."""
+    rng = np.random.default_rng(seed)
+    centres = rng.integers(0, 256, (K, 3))
+    img = np.clip(centres[rng.integers(0, K, (H, W))] + rng.integers(-40, 41, (H, W, 3)), 0, 255).astype(np.uint8)
+    img[rng.random((H, W)) < black] = 0
+    img[rng.random((H, W)) < 0.02] = (0, 0, 1)
+    return img
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K", [1, 3, 8, 16])
+@pytest.mark.parametrize("H,W", [(1, 1), (5, 7), (120, 212), (480, 848), (3, 1021)])
+def test_single_step_counts_match_the_restatement(K, H, W, rdf, gpu_runtime):
+    po = _po()
+    rng = np.random.default_rng(K * 1000 + W)
+    colors = rng.integers(0, 256, (K, 3)).astype(np.uint8)
+    if K >= 3:
+        colors[2] = colors[0]                      # a duplicate: never chosen
+    onto = np.zeros((K, 5), np.uint64)
+    onto[:, :4] = rng.integers(0, 1 << 40, (K, 4))
+    onto[:, 4] = rng.integers(0, 1 << 30, K).astype(np.float64).view(np.uint64)
+    for img, start in ((_frame(H, W, K, W + K), None), (np.zeros((H, W, 3), np.uint8), None), (_frame(H, W, K, 7, 0.0), onto)):
+        counts = rdf.DeviceArray((K, 5), np.uint64)
+        counts.set(start) if start is not None else counts.fill(np.uint64(0))
+        po.split_pixels_by_nearest_color(np.int32(W), np.int32(H), np.int32(K), rdf.to_device(colors), rdf.to_device(img), counts,
+                                         grid=(W // 32 + 1, H // 32 + 1, 1), block=(32, 32, 1))
+        want = lnp.counts_as_reference(lnp.split_counts(colors, img), start)
+        assert np.array_equal(counts.get(), want), (K, H, W)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tries", [1, 8])
+@pytest.mark.parametrize("iterations", [1, 2, 32])
+def test_make_color_mapping_matches_the_restatement(tries, iterations, rdf, gpu_runtime):
+    cl = importlib.import_module("3d-beats_amd.color_labels")
+    for K, (H, W) in ((4, (120, 212)), (16, (37, 61)), (3, (1, 3))):
+        img = _frame(H, W, K, 100 + K, 0.6)
+        rng = np.random.default_rng(tries * 100 + iterations + K)
+        init = np.stack([rng.uniform(0, 255, (K, 3)).astype(np.uint8) for _ in range(tries)])
+        lit = img[img.sum(-1) > 0]
+        if len(lit):
+            init[0, 0] = lit[0]                        # try 0 starts with one colour on a pixel
+        lab = rdf.ColorLabeler(K, tries, iterations)
+        got = lab.make_color_mapping(rdf.to_device(img), init)
+        best, bt, costs, finals = lnp.make_color_mapping(img, init, iterations)
+        assert np.array_equal(got, best) and lab.best_try == bt, (K, tries, iterations)
+        assert np.array_equal(lab.costs.view(np.uint64), costs.view(np.uint64))
+        assert np.array_equal(lab.try_colors_cu.get(), finals) and np.array_equal(lab.color_mapping_gpu.get(), best)
+        r = lab.result()
+        assert int(r["tries"]) == tries and float(r["best_cost"]) == costs[bt] and not r["cost"][tries:].any()
+        assert r.dtype == cl.RESULT_DTYPE
+    # an init that leaves a group empty on purpose: the group turns (0, 0, 0) and stays empty
+    img = np.zeros((8, 8, 3), np.uint8)
+    img[:4] = (200, 10, 10)
+    init = np.tile(np.array([[[190, 0, 0], [0, 0, 250]]], np.uint8), (tries, 1, 1))
+    lab = rdf.ColorLabeler(2, tries, iterations)
+    got = lab.make_color_mapping(img, init)
+    best, bt, costs, _ = lnp.make_color_mapping(img, init, iterations)
+    assert got.tolist() == best.tolist() == [[200, 10, 10], [0, 0, 0]] and lab.best_try == bt == 0
+    assert np.array_equal(lab.costs, costs)
+    # an all-black frame: every group empty, cost 0
+    lab = rdf.ColorLabeler(3, tries, iterations)
+    assert not lab.make_color_mapping(np.zeros((5, 9, 3), np.uint8)).any() and not lab.costs.any() and lab.best_try == 0
+
+
+@pytest.mark.gpu
+def test_device_recovers_the_painted_glove_scene(rdf, gpu_runtime):
+    palette, img, painted = _truth_scene()
+    K = len(palette)
+    lab = rdf.ColorLabeler(K, 1, 32)
+    mapping = lab.make_color_mapping(rdf.to_device(img), palette[None])
+    want_map, _, want_costs, _ = lnp.make_color_mapping(img, palette[None], 32)
+    assert np.array_equal(mapping, want_map) and np.array_equal(lab.costs, want_costs)
+    labels, rgba = lab.label_frame(rdf.to_device(img))
+    _, want_labels, want_rgba, _ = lnp.label_frame(want_map, img)
+    assert np.array_equal(labels.get(), want_labels) and np.array_equal(rgba.get(), want_rgba)
+    assert np.array_equal(labels.get(), painted)
+    assert lab.id_to_color() == {"0": [0, 0, 0, 0], **{str(k + 1): [int(v) for v in mapping[k]] + [255] for k in range(K)}}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("H,W", [(480, 848), (5, 7), (1, 1), (3, 1021)])
+def test_label_frame_matches_the_restatement(H, W, rdf, gpu_runtime):
+    po, lb, s = _po(), _lb(), gpu_runtime.stream()
+    rng = np.random.default_rng(H * W)
+    for K in (1, 4, 16):
+        img = _frame(H, W, K, K + W, 0.4)
+        mapping = rng.integers(0, 256, (K, 3)).astype(np.uint8)
+        if K >= 4:
+            mapping[3] = mapping[1]                   # duplicates: the label is the higher index
+            mapping[2] = 0                            # an empty group: it labels the background
+        depth = rng.integers(0, 3, (H, W)).astype(np.uint16) * 400
+        depth[rng.random((H, W)) < 0.1] = 65535
+        mask = rng.integers(0, 3, (H, W)).astype(np.uint16)
+        lab = rdf.ColorLabeler(K)
+        lab.set_color_mapping(mapping)
+        # in-place colour image == apply_point_mapping
+        a = rdf.to_device(img)
+        po.apply_point_mapping(np.int32(W), np.int32(H), np.int32(K), lab.color_mapping_gpu, a, grid=(1, 1, 1), block=(32, 32, 1))
+        assert np.array_equal(a.get(), lnp.apply_point_mapping(mapping, img))
+        # everything at once, with a mask
+        c, d, m = rdf.to_device(img), rdf.to_device(depth), rdf.to_device(mask)
+        labels, rgba = lab.label_frame(c, d, m, 2)
+        ws, wl, wr, wd = lnp.label_frame(mapping, img, depth, mask, 2)
+        assert np.array_equal(c.get(), ws) and np.array_equal(labels.get(), wl) and np.array_equal(rgba.get(), wr)
+        assert np.array_equal(d.get(), wd)
+        # without mask and depth, into the caller's buffers; no RGBA through the C entry point
+        c = rdf.to_device(img)
+        mine = rdf.DeviceArray((H, W), np.uint16).fill(9)
+        out_l, out_r = lab.label_frame(c, labels=mine)
+        ws, wl, wr, _ = lnp.label_frame(mapping, img)
+        assert out_l is mine and np.array_equal(mine.get(), wl) and np.array_equal(out_r.get(), wr) and np.array_equal(c.get(), ws)
+        assert np.array_equal(c.get(), a.get())
+        c = rdf.to_device(img)
+        mine.fill(9)
+        assert lb.rdf_label_frame(W, H, K, lab.color_mapping_gpu.ptr, c.ptr, None, 0, None, mine.ptr, None, s) == 0
+        assert np.array_equal(mine.get(), wl) and np.array_equal(c.get(), ws)
+        # the mask step alone
+        c = rdf.to_device(img)
+        lab.mask_color_image(c, m, 1)
+        want = img.copy()
+        want[mask != 1] = 0
+        assert np.array_equal(c.get(), want)
+    assert lb.rdf_label_frame(W, H, 17, lab.color_mapping_gpu.ptr, c.ptr, None, 0, None, mine.ptr, None, s) == -1
+    assert lb.rdf_label_frame(W, H, 4, lab.color_mapping_gpu.ptr, c.ptr, None, 0, None, None, None, s) == -2
+
+
+@pytest.mark.gpu
+def test_depths_from_points_matches_the_restatement(rdf, gpu_runtime):
+    po = _po()
+    n, H, W = 2, 37, 61
+    rng = np.random.default_rng(5)
+    pts = rng.normal(0, 1, (n, H, W, 4)).astype(np.float32)
+    pts[..., 2] = rng.uniform(-100, 70000, (n, H, W)).astype(np.float32)
+    pts[..., 3] = rng.choice(np.array([0, 1, 2, -1, 0.5], np.float32), (n, H, W))
+    pts[0, 0, :4, 2] = [12.9, np.nan, 65535.5, 65534.9]
+    pts[0, 0, :4, 3] = 1
+    pts[0, 1, 0] = [0, 0, 5, np.nan]
+    depth = rng.integers(0, 65536, (n, H, W)).astype(np.uint16)
+    d = rdf.to_device(depth)
+    po.depths_from_points(np.array([n, W, H, -1], np.int32), d, rdf.to_device(pts), grid=(1, 2, 2), block=(1, 32, 32))
+    want = lnp.depths_from_points(depth, pts)
+    assert np.array_equal(d.get(), want) and want[0, 0, :4].tolist() == [12, 0, 65535, 65534] and want[0, 1, 0] == depth[0, 1, 0]
+
+
+@pytest.mark.gpu
+def test_mapping_and_labelling_replay_from_a_captured_graph(rdf, gpu_runtime):
+    import torch
+    H, W, K, tries, iterations = 120, 212, 4, 8, 8
+    lab = rdf.ColorLabeler(K, tries, iterations)
+    img = rdf.DeviceArray((H, W, 3), np.uint8).set(_frame(H, W, K, 1))
+    init = rdf.DeviceArray((tries, K, 3), np.uint8)
+    depth = rdf.DeviceArray((H, W), np.uint16).fill(0)
+    labels, rgba = rdf.DeviceArray((H, W), np.uint16), rdf.DeviceArray((H, W, 4), np.uint8)
+    init.set(np.zeros((tries, K, 3), np.uint8))
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):                       # warm-up
+        lab.make_color_mapping_async(img, init)
+        lab.label_frame(img, depth, labels=labels, labels_rgba=rgba)
+    side.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):          # one stream, one chain
+        lab.make_color_mapping_async(img, init)
+        lab.label_frame(img, depth, labels=labels, labels_rgba=rgba)
+    for k in range(2):
+        frame = _frame(H, W, K, 50 + k, 0.5)
+        d_np = np.random.default_rng(k).integers(0, 2, (H, W)).astype(np.uint16) * 900
+        i_np = np.random.default_rng(60 + k).integers(0, 256, (tries, K, 3)).astype(np.uint8)
+        img.set(frame)
+        init.set(i_np)
+        depth.set(d_np)
+        labels.fill(7)
+        graph.replay()
+        torch.cuda.synchronize()
+        best, bt, costs, _ = lnp.make_color_mapping(frame, i_np, iterations)
+        r = lab.result()
+        assert np.array_equal(lab.color_mapping_gpu.get(), best) and int(r["best_try"]) == bt
+        assert np.array_equal(np.array(r["cost"][:tries]), costs)
+        ws, wl, wr, wd = lnp.label_frame(best, frame, d_np)
+        assert np.array_equal(labels.get(), wl) and np.array_equal(rgba.get(), wr) and np.array_equal(img.get(), ws)
+        assert np.array_equal(depth.get(), wd)
+    del graph
+
+
+def _recording(n, H, W, K):
+    """n (depth, colour) pairs: the tilted table with two raised "hands" of tests/test_frontend.py, the hands painted in K
+    vertical stripes of the palette (with noise), the rest of the colour image black."""
+    from test_frontend import scene
+    frames = []
+    for i in range(n):
+        depth, hand, fpp = scene(H, W, W / 2., tilt_deg=18. + 0.3 * i, box_h=80. + i, holes=0.02, seed=40 + i, hand_scale=1.5)
+        rng = np.random.default_rng(900 + i)
+        stripe = (np.arange(W)[None, :] * K // W + i) % K
+        color = np.clip(PALETTE8[:K].astype(np.int64)[np.broadcast_to(stripe, (H, W))] + rng.integers(-8, 9, (H, W, 3)), 0, 255)
+        color[~hand] = 0
+        frames.append((depth, color.astype(np.uint8)))
+    return frames, fpp
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("gaussian", [0., 1.5])
+def test_recording_converter_end_to_end(gaussian, rdf, gpu_runtime, tmp_path):
+    from PIL import Image
+    ds_mod = importlib.import_module("3d-beats_amd.dataset")
+    pom = importlib.import_module("3d-beats_amd.cuda.points_ops")
+    n, H, W, K, T, G = 24, 60, 106, 3, 40., 600
+    frames, fpp = _recording(n, H, W, K)
+    out = tmp_path / "converted"
+    conv = rdf.RecordingConverter(str(out), (H, W), fpp, K, T, gaussian_noise=gaussian, max_images=n,
+                                  num_random_guesses=G, seed=12)
+    fits = []
+    make = conv.calibrated_plane.make
+
+    def recording_make(*a, **kw):
+        plane = make(*a, **kw)
+        fits.append((conv.frame_count, conv.calibrated_plane.rand_cu.get(), plane.copy()))
+        return plane
+    conv.calibrated_plane.make = recording_make
+    init = np.random.default_rng(2).integers(0, 256, (8, K, 3)).astype(np.uint8)
+    init[3] = PALETTE8[:K]
+    assert conv.convert(frames + frames[:2], init) == n           # max_images stops it
+    assert [f[0] for f in fits] == [1, 20]                        # the first frame, and the refit on the 20th
+
+    # the restatement chain
+    f, ppx, ppy = np.float32(fpp[0]), np.float32(fpp[1]), np.float32(fpp[2])
+    w15 = pom.gaussian_kernel(15, gaussian) if gaussian > 0.1 else None
+    plane, mapping, want_depth, want_labels = None, None, [], []
+    for i, (depth, color) in enumerate(frames):
+        pts = fnp.deproject(depth, ppx, ppy, f)
+        fit = [x for x in fits if x[0] == i + 1]
+        if fit:
+            plane = fnp.calibrate(fit[0][1], pts, W, H, T)[0].reshape(4, 4)
+            assert np.array_equal(plane.view(np.uint32), fit[0][2].view(np.uint32))
+        pts = fnp.transform(fnp.filter_by_plane(fnp.transform(pts, plane), T), np.linalg.inv(plane))
+        d = lnp.depths_from_points(np.zeros((H, W), np.uint16), pts)
+        if w15 is not None:
+            d = fnp.gaussian(d, w15)
+        if mapping is None:
+            mapping, bt, costs, _ = lnp.make_color_mapping(color, init, 32)
+            assert np.array_equal(conv.color_mapping, mapping) and conv.labeler.best_try == bt
+        _, labels, rgba, d = lnp.label_frame(mapping, color, d)
+        want_depth.append(d)
+        want_labels.append(labels)
+        assert np.array_equal(np.array(Image.open(out / f"{i:08d}_labels.png")).astype(np.uint16), labels), i
+        assert np.array_equal(np.array(Image.open(out / f"{i:08d}_depth.png")).astype(np.uint16), d), i
+        assert np.array_equal(np.array(Image.open(out / f"{i:08d}_labels_rgba.png")), rgba), i
+    want_depth, want_labels = np.stack(want_depth), np.stack(want_labels)
+    assert ((want_depth != 65535).sum(axis=(1, 2)) > 100).all() and len(np.unique(want_labels)) == K + 1
+
+    cfg = json.load(open(out / "config.json"))
+    assert cfg["img_dims"] == [W, H] and cfg["num_images"] == n
+    assert cfg["id_to_color"] == {"0": [0, 0, 0, 0], **{str(k + 1): [int(v) for v in mapping[k]] + [255] for k in range(K)}}
+    ds = ds_mod.DecisionTreeDatasetConfig(str(out), num_images=n, imgs_name="test", shuffle=False)
+    assert ds.images_shape() == (n, H, W) and ds.num_classes() == K + 1
+    assert np.array_equal(ds.get_block_cpu(0, "depth"), want_depth) and np.array_equal(ds.get_block_cpu(0, "labels"), want_labels)
+
+    if gaussian:
+        return
+    # training on the converted directory is training on the same arrays written by write_dataset
+    plain = tmp_path / "plain"
+    ds_mod.write_dataset(str(plain), want_depth, want_labels, {k + 1: [int(v) for v in mapping[k]] + [255] for k in range(K)})
+    results = []
+    for d in (out, plain):
+        model = tmp_path / f"forest_{d.name}.npy"
+        forest, pct = ds_mod.train_forest(str(d), 16, 8, 32, 16, 2, 6, str(model), trees_to_try=3, log=lambda *_: None,
+                                          tree_seed=77)
+        np.random.seed(78)
+        results.append((forest, pct, ds_mod.evaluate_saved_model(str(model), str(d), n)))
+    assert np.array_equal(results[0][0].view(np.uint32), results[1][0].view(np.uint32))
+    assert results[0][1:] == results[1][1:]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mask_label", [1, 2])
+def test_recording_converter_with_a_mask_forest(mask_label, rdf, gpu_runtime, oracle, tmp_path):
+    """The mask branch of tick() (live_data_convert.py:413-423): the forest runs on the rebuilt depth with 0 -> 65535 over
+    labels pre-filled with 0, the colour is blacked where its label is not mask_label -- on the first frame before the
+    mapping is fitted -- and the depth saved is the same image."""
+    from PIL import Image
+    n, H, W, K, T, G = 2, 60, 106, 3, 40., 600
+    frames, fpp = _recording(n, H, W, K)
+    forest_np = rdf.synth.forest(2, 6, 3, "trained", 5)
+    out = tmp_path / "masked"
+    conv = rdf.RecordingConverter(str(out), (H, W), fpp, K, T, mask_model=rdf.DecisionForest.from_numpy(forest_np),
+                                  mask_label=mask_label, num_random_guesses=G, seed=3)
+    init = np.random.default_rng(4).integers(0, 256, (8, K, 3)).astype(np.uint8)
+    init[0] = PALETTE8[:K]
+    assert conv.convert(frames, init) == n
+    plane = conv.calibrated_plane.get_mat()
+    f, ppx, ppy = np.float32(fpp[0]), np.float32(fpp[1]), np.float32(fpp[2])
+    mapping = None
+    for i, (depth, color) in enumerate(frames):
+        pts = fnp.deproject(depth, ppx, ppy, f)
+        pts = fnp.transform(fnp.filter_by_plane(fnp.transform(pts, plane), T), np.linalg.inv(plane))
+        d = lnp.depths_from_points(np.zeros((H, W), np.uint16), pts)
+        d[d == 0] = 65535
+        mask = np.zeros((1, H, W), np.uint16)
+        oracle.eval_forest(d[None], forest_np, mask)
+        print(f"frame {i}: mask labels {np.unique(mask, return_counts=True)}")
+        if mapping is None:
+            masked = color.copy()
+            masked[mask[0] != mask_label] = 0
+            mapping = lnp.make_color_mapping(masked, init, 32)[0]
+            assert np.array_equal(conv.color_mapping, mapping)
+        _, labels, rgba, d = lnp.label_frame(mapping, color, d, mask[0], mask_label)
+        assert np.array_equal(np.array(Image.open(out / f"{i:08d}_labels.png")).astype(np.uint16), labels), i
+        assert np.array_equal(np.array(Image.open(out / f"{i:08d}_depth.png")).astype(np.uint16), d), i
+        assert np.array_equal(np.array(Image.open(out / f"{i:08d}_labels_rgba.png")), rgba), i
