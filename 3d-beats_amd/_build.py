@@ -1,9 +1,10 @@
-"""Builds csrc/librdf_hip.so, csrc/librdf_frontend.so and csrc/librdf_labels.so for gfx950 with hipcc (cross-compiles
-without a GPU)."""
+"""Builds the package's native libraries for gfx950 with hipcc (cross-compiles without a GPU).  LIBRARIES describes each
+one once -- its .so, sources, headers and symbol prefix; everything below, and _lib.py's loader, goes by that table."""
 import hashlib
 import os
 import shutil
 import subprocess
+from typing import NamedTuple
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "rdf_hip.hip")
@@ -11,14 +12,26 @@ SOURCES = [SRC, os.path.join(HERE, "csrc", "mean_shift_hip.hip"), os.path.join(H
            os.path.join(HERE, "csrc", "tree_train_hip.hip"), os.path.join(HERE, "csrc", "grouping_hip.hip")]
 HEADERS = [os.path.join(HERE, "..", "include", "rdf_hip.h"), os.path.join(HERE, "csrc", "rdf_device.hpp")]
 SO = os.path.join(HERE, "csrc", "librdf_hip.so")
-# the depth front end (include/rdf_frontend.h): a library of its own, with its own sources and build id
-FRONTEND_SOURCES = [os.path.join(HERE, "csrc", "frontend_hip.hip")]
-FRONTEND_HEADERS = [os.path.join(HERE, "..", "include", "rdf_frontend.h")]
-FRONTEND_SO = os.path.join(HERE, "csrc", "librdf_frontend.so")
-# glove-colour recordings to training labels (include/rdf_labels.h): the third library, on the same terms
-LABELS_SOURCES = [os.path.join(HERE, "csrc", "labels_hip.hip")]
-LABELS_HEADERS = [os.path.join(HERE, "..", "include", "rdf_labels.h")]
-LABELS_SO = os.path.join(HERE, "csrc", "librdf_labels.so")
+
+
+class Library(NamedTuple):
+    key: str
+    so: str
+    sources: list
+    headers: list      # the public header (include/) first
+    prefix: str        # of its <prefix>abi_version / <prefix>build_id / <prefix>error_string
+
+
+# Each library has its own sources and build id, so adding one leaves the others' binaries as they were.
+LIBRARIES = {lib.key: lib for lib in (
+    Library("hip", SO, SOURCES, HEADERS, "rdf_"),
+    # the depth front end
+    Library("frontend", os.path.join(HERE, "csrc", "librdf_frontend.so"), [os.path.join(HERE, "csrc", "frontend_hip.hip")],
+            [os.path.join(HERE, "..", "include", "rdf_frontend.h")], "rdf_frontend_"),
+    # glove-colour recordings to training labels
+    Library("labels", os.path.join(HERE, "csrc", "librdf_labels.so"), [os.path.join(HERE, "csrc", "labels_hip.hip")],
+            [os.path.join(HERE, "..", "include", "rdf_labels.h")], "rdf_labels_"),
+)}
 
 # No -ffast-math, no -fgpu-flush-denormals-to-zero: the fp32 divide must stay IEEE-correct
 # and denormals must be kept for bit-exact parity (see rdf_hip.hip header).
@@ -33,26 +46,18 @@ def hipcc():
 BUILD_ID_MARKER = b"rdf-build-id:"
 
 
-def source_id(files=None):
+def source_id(lib="hip"):
     """16 hex digits of a SHA-256 over everything the library is built from: the sources, the headers, the compiler flags.
-    Baked into the library (rdf_build_id) -- file times say nothing about a .so that travelled with a snapshot.
-    `files`: another library's sources and headers (frontend_source_id)."""
+    Baked into the library (<prefix>build_id) -- file times say nothing about a .so that travelled with a snapshot."""
+    lib = LIBRARIES[lib]
     h = hashlib.sha256()
-    for p in sorted(files or SOURCES + HEADERS, key=os.path.basename):
+    for p in sorted(lib.sources + lib.headers, key=os.path.basename):
         h.update(os.path.basename(p).encode() + b"\0")
         with open(p, "rb") as f:
             h.update(f.read())
         h.update(b"\0")
     h.update(" ".join(HIPCC_FLAGS).encode())
     return h.hexdigest()[:16]
-
-
-def frontend_source_id():
-    return source_id(FRONTEND_SOURCES + FRONTEND_HEADERS)
-
-
-def labels_source_id():
-    return source_id(LABELS_SOURCES + LABELS_HEADERS)
 
 
 def built_id(path=None):
@@ -68,47 +73,27 @@ def built_id(path=None):
     return blob[at + len(BUILD_ID_MARKER):at + len(BUILD_ID_MARKER) + 16].decode("ascii", "replace")
 
 
-def sources_present(files=None):
-    return all(os.path.exists(p) for p in (files or SOURCES + HEADERS))
+def sources_present(lib="hip"):
+    return all(os.path.exists(p) for p in LIBRARIES[lib].sources + LIBRARIES[lib].headers)
 
 
-def is_stale():
-    """True when csrc/librdf_hip.so is missing or was built from other sources than the ones next to it."""
-    if not os.path.exists(SO):
+def is_stale(lib="hip"):
+    """True when the library's .so is missing or was built from other sources than the ones next to it."""
+    so = LIBRARIES[lib].so
+    if not os.path.exists(so):
         return True
-    return sources_present() and built_id() != source_id()
-
-
-def frontend_is_stale():
-    """The same for csrc/librdf_frontend.so."""
-    if not os.path.exists(FRONTEND_SO):
-        return True
-    return sources_present(FRONTEND_SOURCES + FRONTEND_HEADERS) and built_id(FRONTEND_SO) != frontend_source_id()
-
-
-def labels_is_stale():
-    """The same for csrc/librdf_labels.so."""
-    if not os.path.exists(LABELS_SO):
-        return True
-    return sources_present(LABELS_SOURCES + LABELS_HEADERS) and built_id(LABELS_SO) != labels_source_id()
-
-
-def _compile(so, sources, sid, verbose):
-    cmd = [hipcc()] + HIPCC_FLAGS + [f'-DRDF_BUILD_ID="{sid}"', "-o", so + ".tmp"] + sources
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
-    os.replace(so + ".tmp", so)
+    return sources_present(lib) and built_id(so) != source_id(lib)
 
 
 def build(force=False, verbose=False):
-    """Compile the three HIP libraries in-tree (each only when stale).  Returns the path of the main one, librdf_hip.so."""
-    if force or is_stale():
-        _compile(SO, SOURCES, source_id(), verbose)
-    if force or frontend_is_stale():
-        _compile(FRONTEND_SO, FRONTEND_SOURCES, frontend_source_id(), verbose)
-    if force or labels_is_stale():
-        _compile(LABELS_SO, LABELS_SOURCES, labels_source_id(), verbose)
+    """Compile the HIP libraries in-tree (each only when stale).  Returns the path of the main one, librdf_hip.so."""
+    for lib in LIBRARIES.values():
+        if force or is_stale(lib.key):
+            cmd = [hipcc()] + HIPCC_FLAGS + [f'-DRDF_BUILD_ID="{source_id(lib.key)}"', "-o", lib.so + ".tmp"] + lib.sources
+            if verbose:
+                print(" ".join(cmd))
+            subprocess.check_call(cmd)
+            os.replace(lib.so + ".tmp", lib.so)
     return SO
 
 

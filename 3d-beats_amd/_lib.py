@@ -1,11 +1,12 @@
-"""ctypes binding of csrc/librdf_hip.so (the C ABI declared in include/rdf_hip.h), of csrc/librdf_frontend.so (the
-depth front end, include/rdf_frontend.h) and of csrc/librdf_labels.so (glove colours to labels, include/rdf_labels.h).
+"""ctypes binding of the native libraries that _build.LIBRARIES describes: the C ABIs declared in include/rdf_hip.h,
+include/rdf_frontend.h (the depth front end) and include/rdf_labels.h (glove colours to labels).
 
 This is the only place the shared libraries are opened.  There is no CPU fallback: a missing
 library, or a machine without a HIP device, raises.
 """
 import ctypes
 import os
+import warnings
 
 from . import _build
 
@@ -128,191 +129,108 @@ SIGNATURES = {
 }
 
 ABI_VERSION = 5
-_lib = None
+
+# library (a key of _build.LIBRARIES) -> (the ABI number this binding was written for, name -> (restype, argtypes) of every
+# symbol its header declares)
+BINDINGS = {
+    "hip": (ABI_VERSION, SIGNATURES),
+    "frontend": (1, {
+        "rdf_make_plane_candidates": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                               _c_void_p]),
+        "rdf_plane_inliers": (_c_int, [_c_int, _c_float, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+        "rdf_plane_select": (_c_int, [_c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+        "rdf_calibrate_plane_workspace_bytes": (_c_size_t, [_c_int]),
+        "rdf_calibrate_plane": (_c_int, [_c_int, _c_float, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                         _c_void_p, _c_void_p]),
+        "rdf_frame_front": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _c_void_p, _c_float,
+                                     _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p]),
+        "rdf_deproject_points": (_c_int, [_c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _c_void_p, _c_void_p, _c_void_p]),
+        "rdf_transform_points": (_c_int, [_c_int, _c_void_p, _c_void_p, _c_void_p]),
+        "rdf_filter_points_by_plane": (_c_int, [_c_int, _c_float, _c_void_p, _c_void_p]),
+        "rdf_remove_missing_3d_points_from_depth_image": (_c_int, [_c_int, _c_void_p, _c_void_p, _c_void_p]),
+        "rdf_gaussian_depth_filter": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+        "rdf_frontend_abi_version": (_c_int, []),
+        "rdf_frontend_build_id": (ctypes.c_char_p, []),
+        "rdf_frontend_error_string": (ctypes.c_char_p, [_c_int]),
+    }),
+    "labels": (1, {
+        "rdf_split_pixels_by_nearest_color": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+        "rdf_apply_point_mapping": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
+        "rdf_depths_from_points": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
+        "rdf_color_mapping_workspace_bytes": (_c_size_t, [_c_int, _c_int]),
+        "rdf_make_color_mapping": (_c_int, [_c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                            _c_void_p]),
+        "rdf_label_frame": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p,
+                                     _c_void_p, _c_void_p]),
+        "rdf_mask_color_image": (_c_int, [_c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p]),
+        "rdf_labels_abi_version": (_c_int, []),
+        "rdf_labels_build_id": (ctypes.c_char_p, []),
+        "rdf_labels_error_string": (ctypes.c_char_p, [_c_int]),
+    }),
+}
+_loaded = {}
 
 
 class RdfError(RuntimeError):
     pass
 
 
-def library_path():
-    # RDF_HIP_LIBRARY: alternate build of the same ABI (kernel timing experiments); default in-tree .so
-    return os.environ.get("RDF_HIP_LIBRARY") or _build.SO
+def _alternate(name):
+    # RDF_HIP_LIBRARY: an alternate build of the same ABI for timing experiments on the forest kernel, so it redirects the
+    # main library only, and being built from other sources on purpose it is exempt from the build-id check
+    return os.environ.get("RDF_HIP_LIBRARY") if name == "hip" else None
 
 
-def load():
-    """Open librdf_hip.so and type every entry point.  Raises if it has not been built."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    path = library_path()
+def library_path(name="hip"):
+    return _alternate(name) or _build.LIBRARIES[name].so
+
+
+def load(name="hip"):
+    """Open one of the libraries (librdf_hip.so by default) and type every entry point; once per process.  Raises if it has
+    not been built, if its ABI number is not the one this binding was written for, or if it was built from other sources."""
+    if name in _loaded:
+        return _loaded[name]
+    prefix = _build.LIBRARIES[name].prefix
+    path = library_path(name)
     if not os.path.exists(path):
         raise RdfError(f"{path} is missing: build it first (python __graft_entry__.py build, "
                        "or python 3d-beats_amd/_build.py). There is no CPU fallback.")
     lib = ctypes.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the symbol is not exported
+    abi, signatures = BINDINGS[name]
+    for symbol, (res, args) in signatures.items():
+        fn = getattr(lib, symbol)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
-    if lib.rdf_abi_version() != ABI_VERSION:
-        raise RdfError(f"librdf_hip.so ABI {lib.rdf_abi_version()} != expected {ABI_VERSION}; rebuild")
-    check_build_id(lib, path)
-    _lib = lib
+    got = getattr(lib, prefix + "abi_version")()
+    if got != abi:
+        raise RdfError(f"{os.path.basename(path)} ABI {got} != expected {abi}; rebuild")
+    check_build_id(lib, path, name)
+    lib.error_string = getattr(lib, prefix + "error_string")    # for check()
+    _loaded[name] = lib
     return lib
 
 
-def check_build_id(lib, path):
+def check_build_id(lib, path, name="hip"):
     """The library must have been built from the sources that sit next to it: same ABI number, yesterday's kernels would
-    otherwise pass every check.  RDF_HIP_LIBRARY (an alternate build for a timing experiment) and a deployment without
-    sources are exempt; RDF_ALLOW_STALE_LIBRARY=1 turns the refusal into a warning."""
-    got = lib.rdf_build_id()
+    otherwise pass every check.  RDF_HIP_LIBRARY and a deployment without sources are exempt; RDF_ALLOW_STALE_LIBRARY=1
+    turns the refusal into a warning."""
+    got = getattr(lib, _build.LIBRARIES[name].prefix + "build_id")()
     got = got.decode() if isinstance(got, bytes) else str(got)
-    if os.environ.get("RDF_HIP_LIBRARY") or not _build.sources_present():
+    if _alternate(name) or not _build.sources_present(name):
         return got
-    want = _build.source_id()
+    want = _build.source_id(name)
     if got != want:
         msg = (f"{path} was built from other sources (build id {got}, sources {want}): rebuild it "
                "(python __graft_entry__.py build).")
-        if os.environ.get("RDF_ALLOW_STALE_LIBRARY") == "1":
-            import warnings
-            warnings.warn(msg)
-        else:
+        if os.environ.get("RDF_ALLOW_STALE_LIBRARY") != "1":
             raise RdfError(msg)
+        warnings.warn(msg)
     return got
-
-
-# name -> (restype, argtypes); every symbol include/rdf_frontend.h declares
-FRONTEND_SIGNATURES = {
-    "rdf_make_plane_candidates": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                                           _c_void_p]),
-    "rdf_plane_inliers": (_c_int, [_c_int, _c_float, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
-    "rdf_plane_select": (_c_int, [_c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
-    "rdf_calibrate_plane_workspace_bytes": (_c_size_t, [_c_int]),
-    "rdf_calibrate_plane": (_c_int, [_c_int, _c_float, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                                     _c_void_p, _c_void_p]),
-    "rdf_frame_front": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _c_void_p, _c_float,
-                                 _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p]),
-    "rdf_deproject_points": (_c_int, [_c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _c_void_p, _c_void_p, _c_void_p]),
-    "rdf_transform_points": (_c_int, [_c_int, _c_void_p, _c_void_p, _c_void_p]),
-    "rdf_filter_points_by_plane": (_c_int, [_c_int, _c_float, _c_void_p, _c_void_p]),
-    "rdf_remove_missing_3d_points_from_depth_image": (_c_int, [_c_int, _c_void_p, _c_void_p, _c_void_p]),
-    "rdf_gaussian_depth_filter": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
-    "rdf_frontend_abi_version": (_c_int, []),
-    "rdf_frontend_build_id": (ctypes.c_char_p, []),
-    "rdf_frontend_error_string": (ctypes.c_char_p, [_c_int]),
-}
-
-FRONTEND_ABI_VERSION = 1
-_frontend = None
-
-
-def frontend_library_path():
-    return _build.FRONTEND_SO
-
-
-def load_frontend():
-    """Open librdf_frontend.so and type every entry point, as load() does for librdf_hip.so.  Raises if it has not been
-    built, if its ABI number is not the one this binding was written for, or if it was built from other sources."""
-    global _frontend
-    if _frontend is not None:
-        return _frontend
-    path = frontend_library_path()
-    if not os.path.exists(path):
-        raise RdfError(f"{path} is missing: build it first (python __graft_entry__.py build, "
-                       "or python 3d-beats_amd/_build.py). There is no CPU fallback.")
-    lib = ctypes.CDLL(path)
-    for name, (res, args) in FRONTEND_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    if lib.rdf_frontend_abi_version() != FRONTEND_ABI_VERSION:
-        raise RdfError(f"librdf_frontend.so ABI {lib.rdf_frontend_abi_version()} != expected {FRONTEND_ABI_VERSION}; rebuild")
-    got = lib.rdf_frontend_build_id()
-    got = got.decode() if isinstance(got, bytes) else str(got)
-    files = _build.FRONTEND_SOURCES + _build.FRONTEND_HEADERS
-    if _build.sources_present(files) and got != _build.frontend_source_id():
-        msg = (f"{path} was built from other sources (build id {got}, sources {_build.frontend_source_id()}): rebuild it "
-               "(python __graft_entry__.py build).")
-        if os.environ.get("RDF_ALLOW_STALE_LIBRARY") == "1":
-            import warnings
-            warnings.warn(msg)
-        else:
-            raise RdfError(msg)
-    _frontend = lib
-    return lib
-
-
-def check_frontend(lib, code, what):
-    if code != 0:
-        msg = lib.rdf_frontend_error_string(int(code))
-        msg = msg.decode() if isinstance(msg, bytes) else str(msg)
-        raise RdfError(f"{what} failed: {msg} (code {code})")
-
-
-# name -> (restype, argtypes); every symbol include/rdf_labels.h declares
-LABELS_SIGNATURES = {
-    "rdf_split_pixels_by_nearest_color": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
-    "rdf_apply_point_mapping": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
-    "rdf_depths_from_points": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
-    "rdf_color_mapping_workspace_bytes": (_c_size_t, [_c_int, _c_int]),
-    "rdf_make_color_mapping": (_c_int, [_c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                                        _c_void_p]),
-    "rdf_label_frame": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p,
-                                 _c_void_p, _c_void_p]),
-    "rdf_mask_color_image": (_c_int, [_c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p]),
-    "rdf_labels_abi_version": (_c_int, []),
-    "rdf_labels_build_id": (ctypes.c_char_p, []),
-    "rdf_labels_error_string": (ctypes.c_char_p, [_c_int]),
-}
-
-LABELS_ABI_VERSION = 1
-_labels = None
-
-
-def labels_library_path():
-    return _build.LABELS_SO
-
-
-def load_labels():
-    """Open librdf_labels.so and type every entry point, on the terms of load_frontend()."""
-    global _labels
-    if _labels is not None:
-        return _labels
-    path = labels_library_path()
-    if not os.path.exists(path):
-        raise RdfError(f"{path} is missing: build it first (python __graft_entry__.py build, "
-                       "or python 3d-beats_amd/_build.py). There is no CPU fallback.")
-    lib = ctypes.CDLL(path)
-    for name, (res, args) in LABELS_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    if lib.rdf_labels_abi_version() != LABELS_ABI_VERSION:
-        raise RdfError(f"librdf_labels.so ABI {lib.rdf_labels_abi_version()} != expected {LABELS_ABI_VERSION}; rebuild")
-    got = lib.rdf_labels_build_id()
-    got = got.decode() if isinstance(got, bytes) else str(got)
-    files = _build.LABELS_SOURCES + _build.LABELS_HEADERS
-    if _build.sources_present(files) and got != _build.labels_source_id():
-        msg = (f"{path} was built from other sources (build id {got}, sources {_build.labels_source_id()}): rebuild it "
-               "(python __graft_entry__.py build).")
-        if os.environ.get("RDF_ALLOW_STALE_LIBRARY") == "1":
-            import warnings
-            warnings.warn(msg)
-        else:
-            raise RdfError(msg)
-    _labels = lib
-    return lib
-
-
-def check_labels(lib, code, what):
-    if code != 0:
-        msg = lib.rdf_labels_error_string(int(code))
-        msg = msg.decode() if isinstance(msg, bytes) else str(msg)
-        raise RdfError(f"{what} failed: {msg} (code {code})")
 
 
 def check(lib, code, what):
     if code != 0:
-        msg = lib.rdf_error_string(int(code))
+        # a handle from load() names its library's error strings; anything else offers rdf_error_string
+        msg = (getattr(lib, "error_string", None) or lib.rdf_error_string)(int(code))
         msg = msg.decode() if isinstance(msg, bytes) else str(msg)
         raise RdfError(f"{what} failed: {msg} (code {code})")

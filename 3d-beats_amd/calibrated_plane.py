@@ -29,7 +29,7 @@ class CalibratedPlane:
     def __init__(self, num_random_guesses, plane_z_outlier_threshold, seed=None):
         import torch
         self._rt = get_runtime()
-        self._fe = _lib.load_frontend()
+        self._fe = _lib.load("frontend")
         self.num_random_guesses = int(num_random_guesses)
         self.plane_z_outlier_threshold = float(plane_z_outlier_threshold)
         G = self.num_random_guesses
@@ -86,7 +86,7 @@ class CalibratedPlane:
         rc = self._fe.rdf_calibrate_plane(self.num_random_guesses, self.plane_z_outlier_threshold, dim_x, dim_y,
                                           device_ptr(rand), device_ptr(pts_gpu), start_ptr, self._ws.ptr, self.plane_cu.ptr,
                                           self.result_cu.ptr, self._rt.stream())
-        _lib.check_frontend(self._fe, rc, "rdf_calibrate_plane")
+        _lib.check(self._fe, rc, "rdf_calibrate_plane")
         for a in (self._ws, self.plane_cu, self.result_cu):
             a.mark_dirty()
         return self.result_cu
@@ -109,19 +109,19 @@ class CalibratedPlane:
     def make_plane_candidates(self, num_candidates, dim_x, dim_y, rand, pts, plane_candidates, grid=None, block=None):
         rc = self._fe.rdf_make_plane_candidates(int(num_candidates), int(dim_x), int(dim_y), device_ptr(rand),
                                                 device_ptr(pts), None, device_ptr(plane_candidates), None, self._rt.stream())
-        _lib.check_frontend(self._fe, rc, "rdf_make_plane_candidates")
+        _lib.check(self._fe, rc, "rdf_make_plane_candidates")
         _touch(plane_candidates)
 
     def find_plane_ransac(self, num_candidates, threshold, num_pts, pts, candidate_planes, num_inliers, grid=None,
                           block=None):
         rc = self._fe.rdf_plane_inliers(int(num_candidates), float(threshold), int(num_pts), device_ptr(pts),
                                         device_ptr(candidate_planes), device_ptr(num_inliers), self._rt.stream())
-        _lib.check_frontend(self._fe, rc, "rdf_plane_inliers")
+        _lib.check(self._fe, rc, "rdf_plane_inliers")
         _touch(num_inliers)
 
     def filter_points_by_plane(self, num_pts, threshold, pts, grid=None, block=None):
         rc = self._fe.rdf_filter_points_by_plane(int(num_pts), float(threshold), device_ptr(pts), self._rt.stream())
-        _lib.check_frontend(self._fe, rc, "rdf_filter_points_by_plane")
+        _lib.check(self._fe, rc, "rdf_filter_points_by_plane")
         _touch(pts)
 
 

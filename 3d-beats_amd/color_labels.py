@@ -38,7 +38,7 @@ class ColorLabeler:
         """num_colors = --colors of the reference (1..16); num_tries, num_iterations = its COLOR_EM_NUM_TRIES (<= 8) and
         COLOR_EM_ITERATIONS."""
         self._rt = get_runtime()
-        self._lb = _lib.load_labels()
+        self._lb = _lib.load("labels")
         self.num_colors, self.num_tries, self.num_iterations = int(num_colors), int(num_tries), int(num_iterations)
         assert 1 <= self.num_colors <= MAX_COLORS and 1 <= self.num_tries <= MAX_TRIES and self.num_iterations >= 1
         K, T = self.num_colors, self.num_tries
@@ -89,7 +89,7 @@ class ColorLabeler:
         rc = self._lb.rdf_make_color_mapping(int(img.shape[0]) * int(img.shape[1]), device_ptr(img), T, self.num_iterations, K,
                                              device_ptr(init), self._ws.ptr, self.color_mapping_gpu.ptr, self.result_cu.ptr,
                                              self._rt.stream())
-        _lib.check_labels(self._lb, rc, "rdf_make_color_mapping")
+        _lib.check(self._lb, rc, "rdf_make_color_mapping")
         _touch(self._ws, self.color_mapping_gpu, self.result_cu)
         self._on_device = True
         return self.color_mapping_gpu
@@ -120,7 +120,7 @@ class ColorLabeler:
         img = _arr(color_image)
         rc = self._lb.rdf_mask_color_image(int(img.shape[1]), int(img.shape[0]), device_ptr(img), device_ptr(mask_labels),
                                            int(mask_label), self._rt.stream())
-        _lib.check_labels(self._lb, rc, "rdf_mask_color_image")
+        _lib.check(self._lb, rc, "rdf_mask_color_image")
         _touch(img)
 
     def label_frame(self, color_image, depth=None, mask_labels=None, mask_label=None, labels=None, labels_rgba=None):
@@ -147,7 +147,7 @@ class ColorLabeler:
         rc = self._lb.rdf_label_frame(W, H, self.num_colors, self.color_mapping_gpu.ptr, device_ptr(img),
                                       device_ptr(mask_labels), int(mask_label or 0), device_ptr(depth), device_ptr(labels),
                                       device_ptr(labels_rgba), self._rt.stream())
-        _lib.check_labels(self._lb, rc, "rdf_label_frame")
+        _lib.check(self._lb, rc, "rdf_label_frame")
         _touch(img, labels, labels_rgba, *([depth] if depth is not None else []))
         return labels, labels_rgba
 

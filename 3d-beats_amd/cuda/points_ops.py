@@ -31,39 +31,16 @@ class PointsOps:
     def __init__(self):
         self._rt = get_runtime()
         self._lib = self._rt.lib
-        self._fe = None
-        self._lb = None
         self.MAX_FILTER_SIZE = MAX_FILTER_SIZE
         self._gaussian_filter = None
         self._cached_filter_params = None
 
-    def _frontend(self):
-        if self._fe is None:
-            self._fe = _lib.load_frontend()
-        return self._fe
-
-    def _ok_fe(self, rc, name, *touched):
-        _lib.check_frontend(self._frontend(), rc, name)
+    def _ok(self, rc, name, *touched, lib=None):
+        """lib: the front-end or labels library the call went to.  The methods below open those on first use (_lib.load keeps
+        them for the process), so a process that only evaluates forests never needs them."""
+        _lib.check(lib or self._lib, rc, name)
         for t in touched:
             t = t.cu() if hasattr(t, "cu") else t
-            if hasattr(t, "mark_dirty"):
-                t.mark_dirty()
-
-    def _labels(self):
-        if self._lb is None:
-            self._lb = _lib.load_labels()
-        return self._lb
-
-    def _ok_lb(self, rc, name, *touched):
-        _lib.check_labels(self._labels(), rc, name)
-        for t in touched:
-            t = t.cu() if hasattr(t, "cu") else t
-            if hasattr(t, "mark_dirty"):
-                t.mark_dirty()
-
-    def _ok(self, rc, name, *touched):
-        _lib.check(self._lib, rc, name)
-        for t in touched:
             if hasattr(t, "mark_dirty"):
                 t.mark_dirty()
 
@@ -125,28 +102,28 @@ class PointsOps:
         depth 0 keep what pts held."""
         n, dim_x, dim_y = (int(v) for v in np.asarray(imgs_dim).reshape(-1)[:3])
         ppx, ppy = (float(v) for v in np.asarray(pp, np.float32).reshape(-1)[:2])
-        fe = self._frontend()
-        self._ok_fe(fe.rdf_deproject_points(n, dim_x, dim_y, ppx, ppy, float(np.float32(f)), device_ptr(imgs), device_ptr(pts),
-                                            self._rt.stream()),
-                    "rdf_deproject_points", pts)
+        fe = _lib.load("frontend")
+        self._ok(fe.rdf_deproject_points(n, dim_x, dim_y, ppx, ppy, float(np.float32(f)), device_ptr(imgs), device_ptr(pts),
+                                         self._rt.stream()),
+                 "rdf_deproject_points", pts, lib=fe)
 
     def transform_points(self, num_pts, pts, t, grid=None, block=None):
         """t: the host 4x4 float32 plane, row-major (passed by value, as the reference passes a glm::mat4)."""
         m = np.ascontiguousarray(np.asarray(t, np.float32).reshape(16))
-        fe = self._frontend()
-        self._ok_fe(fe.rdf_transform_points(int(num_pts), device_ptr(pts), m.ctypes.data, self._rt.stream()),
-                    "rdf_transform_points", pts)
+        fe = _lib.load("frontend")
+        self._ok(fe.rdf_transform_points(int(num_pts), device_ptr(pts), m.ctypes.data, self._rt.stream()),
+                 "rdf_transform_points", pts, lib=fe)
 
     def filter_points_by_plane(self, num_pts, threshold, pts, grid=None, block=None):
-        fe = self._frontend()
-        self._ok_fe(fe.rdf_filter_points_by_plane(int(num_pts), float(threshold), device_ptr(pts), self._rt.stream()),
-                    "rdf_filter_points_by_plane", pts)
+        fe = _lib.load("frontend")
+        self._ok(fe.rdf_filter_points_by_plane(int(num_pts), float(threshold), device_ptr(pts), self._rt.stream()),
+                 "rdf_filter_points_by_plane", pts, lib=fe)
 
     def remove_missing_3d_points_from_depth_image(self, num_pixels, pts, depth, grid=None, block=None):
-        fe = self._frontend()
-        self._ok_fe(fe.rdf_remove_missing_3d_points_from_depth_image(int(num_pixels), device_ptr(pts), device_ptr(depth),
-                                                                     self._rt.stream()),
-                    "rdf_remove_missing_3d_points_from_depth_image", depth)
+        fe = _lib.load("frontend")
+        self._ok(fe.rdf_remove_missing_3d_points_from_depth_image(int(num_pixels), device_ptr(pts), device_ptr(depth),
+                                                                  self._rt.stream()),
+                 "rdf_remove_missing_3d_points_from_depth_image", depth, lib=fe)
 
     def gaussian_depth_filter(self, d_in, d_out, sigma, k_size=5):
         """points_ops.py:68-104: one frame of dims d_in.shape[-2:] (the reference passes only dim_x, dim_y, so of a
@@ -162,30 +139,30 @@ class PointsOps:
             k = gaussian_kernel(k_size, sigma).reshape(-1)
             self._gaussian_filter[0:k.shape[0]].set(k)
             self._cached_filter_params = (sigma, k_size)
-        fe = self._frontend()
-        self._ok_fe(fe.rdf_gaussian_depth_filter(int(dim_x), int(dim_y), int(k_size), self._gaussian_filter.ptr,
-                                                 device_ptr(d_in), device_ptr(d_out), self._rt.stream()),
-                    "rdf_gaussian_depth_filter", d_out)
+        fe = _lib.load("frontend")
+        self._ok(fe.rdf_gaussian_depth_filter(int(dim_x), int(dim_y), int(k_size), self._gaussian_filter.ptr,
+                                              device_ptr(d_in), device_ptr(d_out), self._rt.stream()),
+                 "rdf_gaussian_depth_filter", d_out, lib=fe)
 
     # ---- glove colours to labels, kernel for kernel (live_data_convert.py:179-187, 377-382, 434-441); ColorLabeler fuses it ----
     def split_pixels_by_nearest_color(self, dim_x, dim_y, num_colors, colors, color_image, pixel_counts_per_group, grid=None,
                                       block=None):
         """Adds onto pixel_counts_per_group uint64 [K, 5] = (pixels, sum r, sum g, sum b, sum cost as a float64)."""
-        lb = self._labels()
-        self._ok_lb(lb.rdf_split_pixels_by_nearest_color(int(dim_x), int(dim_y), int(num_colors), device_ptr(colors),
-                                                         device_ptr(color_image), device_ptr(pixel_counts_per_group),
-                                                         self._rt.stream()),
-                    "rdf_split_pixels_by_nearest_color", pixel_counts_per_group)
+        lb = _lib.load("labels")
+        self._ok(lb.rdf_split_pixels_by_nearest_color(int(dim_x), int(dim_y), int(num_colors), device_ptr(colors),
+                                                      device_ptr(color_image), device_ptr(pixel_counts_per_group),
+                                                      self._rt.stream()),
+                 "rdf_split_pixels_by_nearest_color", pixel_counts_per_group, lib=lb)
 
     def apply_point_mapping(self, dim_x, dim_y, num_colors, colors, color_image, grid=None, block=None):
-        lb = self._labels()
-        self._ok_lb(lb.rdf_apply_point_mapping(int(dim_x), int(dim_y), int(num_colors), device_ptr(colors),
-                                               device_ptr(color_image), self._rt.stream()),
-                    "rdf_apply_point_mapping", color_image)
+        lb = _lib.load("labels")
+        self._ok(lb.rdf_apply_point_mapping(int(dim_x), int(dim_y), int(num_colors), device_ptr(colors),
+                                            device_ptr(color_image), self._rt.stream()),
+                 "rdf_apply_point_mapping", color_image, lib=lb)
 
     def depths_from_points(self, imgs_dim, imgs, pts, grid=None, block=None):
         """imgs_dim = (num_images, dim_x, dim_y, -1) int32 (points_ops.cu:39-63): depth = (uint16)z where w > 0."""
         n, dim_x, dim_y = (int(v) for v in np.asarray(imgs_dim).reshape(-1)[:3])
-        lb = self._labels()
-        self._ok_lb(lb.rdf_depths_from_points(n, dim_x, dim_y, device_ptr(imgs), device_ptr(pts), self._rt.stream()),
-                    "rdf_depths_from_points", imgs)
+        lb = _lib.load("labels")
+        self._ok(lb.rdf_depths_from_points(n, dim_x, dim_y, device_ptr(imgs), device_ptr(pts), self._rt.stream()),
+                 "rdf_depths_from_points", imgs, lib=lb)

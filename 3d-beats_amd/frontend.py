@@ -21,7 +21,7 @@ class FrameFrontEnd:
         plane_z_threshold = PLANE_Z_OUTLIER_THRESHOLD (40 in the app), used both to fit the plane and to cut the table;
         gauss_sigma <= 0.1 turns the Gaussian off, as the app's `if self.gauss_sigma > 0.1` does; k_size odd, <= 41."""
         self._rt = get_runtime()
-        self._fe = _lib.load_frontend()
+        self._fe = _lib.load("frontend")
         self.DIM_Y, self.DIM_X = int(depth_dims[0]), int(depth_dims[1])
         self.focal, self.ppx, self.ppy = (float(v) for v in np.asarray(intrinsics, np.float64).reshape(-1)[:3])
         self.plane_z_threshold = float(plane_z_threshold)
@@ -43,7 +43,7 @@ class FrameFrontEnd:
         self.pts_cu.fill(0)
         rc = self._fe.rdf_deproject_points(1, self.DIM_X, self.DIM_Y, self.ppx, self.ppy, self.focal, device_ptr(d),
                                            self.pts_cu.ptr, self._rt.stream())
-        _lib.check_frontend(self._fe, rc, "rdf_deproject_points")
+        _lib.check(self._fe, rc, "rdf_deproject_points")
 
     def calibrate(self, depth, start_mat=None, rand=None):
         """Fit the table plane to the (first) frame of `depth`, as the app does on its first frame and on "recalibrate
@@ -83,7 +83,7 @@ class FrameFrontEnd:
                                       self.calibrated_plane.plane_cu.ptr, self.plane_z_threshold,
                                       None if w is None else w.ptr, self.k_size if w is not None else 0, device_ptr(o),
                                       device_ptr(pts_out), self._rt.stream())
-        _lib.check_frontend(self._fe, rc, "rdf_frame_front")
+        _lib.check(self._fe, rc, "rdf_frame_front")
         for b in (o, pts_out):
             b = b.cu() if hasattr(b, "cu") else b
             if hasattr(b, "mark_dirty"):

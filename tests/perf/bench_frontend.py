@@ -43,7 +43,7 @@ def main():
     _lib = importlib.import_module("3d-beats_amd._lib")
     pom = importlib.import_module("3d-beats_amd.cuda.points_ops")
     torch.cuda.set_device(0)
-    fe = _lib.load_frontend()
+    fe = _lib.load("frontend")
     s = rdf.get_runtime().stream()
     out = {}
 
@@ -56,7 +56,7 @@ def main():
     res = rdf.DeviceArray((112,), np.uint8)
 
     def calib():
-        _lib.check_frontend(fe, fe.rdf_calibrate_plane(G, T, W, H, rand.ptr, pts.ptr, None, ws.ptr, plane.ptr, res.ptr, s),
+        _lib.check(fe, fe.rdf_calibrate_plane(G, T, W, H, rand.ptr, pts.ptr, None, ws.ptr, plane.ptr, res.ptr, s),
                             "rdf_calibrate_plane")
     for _ in range(3):
         calib()
@@ -65,7 +65,7 @@ def main():
     counts = rdf.DeviceArray((G,), np.int32).fill(0)     # zeroed once: after k calls it holds k x the counts
 
     def inliers():
-        _lib.check_frontend(fe, fe.rdf_plane_inliers(G, T, H * W, pts.ptr, cand, counts.ptr, s), "rdf_plane_inliers")
+        _lib.check(fe, fe.rdf_plane_inliers(G, T, H * W, pts.ptr, cand, counts.ptr, s), "rdf_plane_inliers")
     inliers()
     ms = _events(torch, inliers, 20)
     once = np.maximum(ws.get()[G * 64:G * 68].view(np.int32), 0)     # calibrate's counts (-1 = invalid, never added to)

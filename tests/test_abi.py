@@ -1,18 +1,39 @@
-"""The C-ABI library builds for gfx950, loads, and exports every symbol include/rdf_hip.h declares.
-No compute calls (no GPU here)."""
+"""The C-ABI libraries build for gfx950, load, and export exactly the symbols their headers declare.  What holds for each
+library alike is tested once, for every entry of _build.LIBRARIES; what only one library has (sizes, return codes, structs)
+is with that library's tests.  No compute calls (no GPU here)."""
 import ctypes
 import os
-import re
+import shutil
+import subprocess
+from importlib import import_module
 
 import pytest
 
+from abi_helpers import declared, exported
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIBS = ("hip", "frontend", "labels")
+C99 = ["-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include")]
 
 
 def _declared():
-    text = open(os.path.join(ROOT, "include", "rdf_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(rdf_[a-z0-9_]+)\s*\(", text)))
+    return declared(os.path.join(ROOT, "include", "rdf_hip.h"))
+
+
+def _modules():
+    return import_module("3d-beats_amd._build"), import_module("3d-beats_amd._lib")
+
+
+def _copy_with_another_id(build, so, tmp_path):
+    """The same library with another id baked in (as if built before the last edit of a kernel)."""
+    blob = bytearray(open(so, "rb").read())
+    at = blob.find(build.BUILD_ID_MARKER) + len(build.BUILD_ID_MARKER)
+    assert at >= len(build.BUILD_ID_MARKER) and blob.count(build.BUILD_ID_MARKER) == 1
+    blob[at:at + 16] = b"0123456789abcdef"
+    stale = tmp_path / os.path.basename(so).replace(".so", "_stale.so")
+    stale.write_bytes(bytes(blob))
+    assert build.built_id(str(stale)) == "0123456789abcdef"
+    return str(stale)
 
 
 def test_header_declares_the_three_reference_kernels():
@@ -22,7 +43,6 @@ def test_header_declares_the_three_reference_kernels():
 
 
 def test_library_builds_and_exports_every_declared_symbol(rdf):
-    from importlib import import_module
     build = import_module("3d-beats_amd._build")
     so = build.build()
     assert os.path.exists(so)
@@ -32,7 +52,6 @@ def test_library_builds_and_exports_every_declared_symbol(rdf):
 
 
 def test_binding_table_matches_header(rdf):
-    from importlib import import_module
     _lib = import_module("3d-beats_amd._lib")
     assert sorted(_lib.SIGNATURES) == _declared()
     lib = _lib.load()
@@ -61,10 +80,42 @@ def test_binding_table_matches_header(rdf):
     assert b"2^31" in lib.rdf_error_string(-3)
 
 
-def test_code_object_targets_gfx950(rdf):
-    from importlib import import_module
-    so = import_module("3d-beats_amd._build").SO
-    blob = open(so, "rb").read()
+def test_the_library_table_is_these_three(rdf):
+    build, _lib = _modules()
+    assert tuple(build.LIBRARIES) == tuple(_lib.BINDINGS) == LIBS
+    assert [build.LIBRARIES[k].prefix for k in LIBS] == ["rdf_", "rdf_frontend_", "rdf_labels_"]
+    assert build.LIBRARIES["hip"][1:4] == (build.SO, build.SOURCES, build.HEADERS)
+    assert len({build.LIBRARIES[k].so for k in LIBS}) == 3
+
+
+@pytest.mark.parametrize("name", LIBS)
+def test_library_binding_header_and_sources_agree(name, rdf):
+    """Binding table == the header's declarations == the .so's exported rdf_* symbols, none of them another library's; the
+    ABI number is the binding's; the id baked into the file is the one of the sources next to it."""
+    build, _lib = _modules()
+    build.build()
+    rec = build.LIBRARIES[name]
+    names = declared(rec.headers[0])
+    assert sorted(_lib.BINDINGS[name][1]) == names
+    assert exported(rec.so) == names
+    for what in ("abi_version", "build_id", "error_string"):
+        assert rec.prefix + what in names
+    for other in LIBS:
+        if other != name:
+            assert not set(names) & (set(_lib.BINDINGS[other][1]) | set(exported(build.LIBRARIES[other].so))), other
+    lib = _lib.load(name)
+    assert lib is _lib.load(name)
+    assert getattr(lib, rec.prefix + "abi_version")() == _lib.BINDINGS[name][0]
+    got = getattr(lib, rec.prefix + "build_id")().decode()
+    assert len(got) == 16 and got == build.source_id(name) == build.built_id(rec.so)
+    assert build.sources_present(name) and not build.is_stale(name)
+
+
+@pytest.mark.parametrize("name", LIBS)
+def test_code_object_targets_gfx950(name, rdf):
+    build = import_module("3d-beats_amd._build")
+    build.build()
+    blob = open(build.LIBRARIES[name].so, "rb").read()
     assert b"gfx950" in blob
 
 
@@ -73,7 +124,6 @@ def test_code_object_stays_small(rdf, tmp_path):
     ones launches really take.  Fewer than 75 of them (16 walk the deep blocks, 4 count visits and lines), and a library under 1.9 MB."""
     import shutil
     import subprocess
-    from importlib import import_module
     so = import_module("3d-beats_amd._build").build()
     assert os.path.getsize(so) < 1_900_000, os.path.getsize(so)
     objdump = shutil.which("llvm-objdump") or "/opt/rocm/lib/llvm/bin/llvm-objdump"
@@ -115,17 +165,28 @@ def test_package_never_imports_the_oracle():
                 assert "import oracle" not in src and "from oracle" not in src and "librdf_oracle" not in src, f
 
 
-def test_header_is_plain_c(tmp_path):
-    """include/rdf_hip.h is what a C (or cgo / JNI / N-API) binding would include: it must compile as pedantic C99."""
-    import shutil
-    import subprocess
+@pytest.mark.parametrize("name", LIBS)
+def test_header_is_plain_c(name, rdf, tmp_path):
+    """A public header is what a C (or cgo / JNI / N-API) binding would include: it must compile as pedantic C99, on its own."""
     gcc = shutil.which("gcc")
     if gcc is None:
         pytest.skip("no gcc")
+    rec = import_module("3d-beats_amd._build").LIBRARIES[name]
     src = tmp_path / "t.c"
-    src.write_text('#include "rdf_hip.h"\nint main(void) { return rdf_abi_version() > 0 ? 0 : 1; }\n')
-    inc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
-    subprocess.check_call([gcc, "-std=c99", "-pedantic", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-I", inc, str(src)])
+    src.write_text(f'#include "{os.path.basename(rec.headers[0])}"\n'
+                   f'int main(void) {{ return {rec.prefix}abi_version() > 0 ? 0 : 1; }}\n')
+    subprocess.check_call([gcc] + C99 + [str(src)])
+
+
+def test_headers_are_plain_c_together(rdf, tmp_path):
+    gcc = shutil.which("gcc")
+    if gcc is None:
+        pytest.skip("no gcc")
+    recs = import_module("3d-beats_amd._build").LIBRARIES.values()
+    src = tmp_path / "t.c"
+    src.write_text("".join(f'#include "{os.path.basename(r.headers[0])}"\n' for r in recs)
+                   + "int main(void) { return " + " && ".join(f"{r.prefix}abi_version() > 0" for r in recs) + " ? 0 : 1; }\n")
+    subprocess.check_call([gcc] + C99 + [str(src)])
 
 
 @pytest.mark.gpu
@@ -148,35 +209,75 @@ def test_plain_c_consumer_of_the_shared_library(rdf, gpu_runtime, tmp_path):
     assert out.returncode == 0 and "PASS" in out.stdout, (out.returncode, out.stdout, out.stderr)
 
 
-def test_a_library_built_from_other_sources_is_refused(rdf, tmp_path, monkeypatch):
-    """Build identity: librdf_hip.so carries a hash of the sources it was built from (rdf_build_id); the binding recomputes it
-    from csrc/ + include/ and refuses a mismatch -- a library with today's ABI number and yesterday's kernels passes every
+@pytest.mark.parametrize("name", LIBS)
+def test_a_library_built_from_other_sources_is_refused(name, rdf, tmp_path, monkeypatch):
+    """Build identity: each library carries a hash of the sources it was built from (<prefix>build_id); the binding recomputes
+    it from csrc/ + include/ and refuses a mismatch -- a library with today's ABI number and yesterday's kernels passes every
     other check (the .so is git-ignored and travels to the GPU box with the snapshot; file times mean nothing there)."""
-    import shutil
-    from importlib import import_module
-    build = import_module("3d-beats_amd._build")
-    _lib = import_module("3d-beats_amd._lib")
-    so = build.build()
-    assert build.built_id() == build.source_id() and not build.is_stale()
-    lib = ctypes.CDLL(so)
-    lib.rdf_build_id.restype = ctypes.c_char_p
-    assert _lib.check_build_id(lib, so) == build.source_id()
-    # the same library with another id baked in (as if built before the last edit of a kernel)
-    blob = bytearray(open(so, "rb").read())
-    at = blob.find(build.BUILD_ID_MARKER) + len(build.BUILD_ID_MARKER)
-    assert at >= len(build.BUILD_ID_MARKER) and blob.count(build.BUILD_ID_MARKER) == 1
-    blob[at:at + 16] = b"0123456789abcdef"
-    stale = tmp_path / "librdf_hip_stale.so"
-    stale.write_bytes(bytes(blob))
-    assert build.built_id(str(stale)) == "0123456789abcdef"
-    old = ctypes.CDLL(str(stale))
-    old.rdf_build_id.restype = ctypes.c_char_p
+    build, _lib = _modules()
+    monkeypatch.delenv("RDF_HIP_LIBRARY", raising=False)
+    monkeypatch.delenv("RDF_ALLOW_STALE_LIBRARY", raising=False)
+    build.build()
+    rec = build.LIBRARIES[name]
+    assert build.built_id(rec.so) == build.source_id(name) and not build.is_stale(name)
+    if name == "hip":
+        assert build.built_id() == build.source_id() and not build.is_stale()
+    lib = ctypes.CDLL(rec.so)
+    getattr(lib, rec.prefix + "build_id").restype = ctypes.c_char_p
+    assert _lib.check_build_id(lib, rec.so, name) == build.source_id(name)
+    stale = _copy_with_another_id(build, rec.so, tmp_path)
+    old = ctypes.CDLL(stale)
+    getattr(old, rec.prefix + "build_id").restype = ctypes.c_char_p
     with pytest.raises(_lib.RdfError, match="built from other sources"):
-        _lib.check_build_id(old, str(stale))
+        _lib.check_build_id(old, stale, name)
+    # ... and load() is what refuses it, when that file is the library's
+    monkeypatch.setattr(_lib, "_loaded", {})
+    monkeypatch.setitem(build.LIBRARIES, name, rec._replace(so=stale))
+    with pytest.raises(_lib.RdfError, match="built from other sources"):
+        _lib.load(name)
     monkeypatch.setenv("RDF_ALLOW_STALE_LIBRARY", "1")
     with pytest.warns(UserWarning, match="built from other sources"):
-        _lib.check_build_id(old, str(stale))
+        _lib.check_build_id(old, stale, name)
+    with pytest.warns(UserWarning, match="built from other sources"):
+        assert getattr(_lib.load(name), rec.prefix + "build_id")() == b"0123456789abcdef"
     monkeypatch.delenv("RDF_ALLOW_STALE_LIBRARY")
+    monkeypatch.setitem(build.LIBRARIES, name, rec)
     # is_stale() sees an edited source without looking at file times
     monkeypatch.setattr(build, "HIPCC_FLAGS", build.HIPCC_FLAGS + ["-DSOMETHING_ELSE"])
-    assert build.is_stale()
+    assert build.is_stale(name)
+
+
+def test_rdf_hip_library_redirects_the_main_library_only(rdf, tmp_path, monkeypatch):
+    """RDF_HIP_LIBRARY is for timing other builds of the forest kernel: it names the file load() opens as the main library and
+    exempts it from the build-id check; the front-end and labels libraries cannot be pointed elsewhere and stay checked."""
+    build, _lib = _modules()
+    monkeypatch.delenv("RDF_ALLOW_STALE_LIBRARY", raising=False)
+    build.build()
+    alt = _copy_with_another_id(build, build.SO, tmp_path)
+    monkeypatch.setenv("RDF_HIP_LIBRARY", alt)
+    monkeypatch.setattr(_lib, "_loaded", {})
+    assert _lib.library_path() == _lib.library_path("hip") == alt
+    lib = _lib.load()
+    assert lib.rdf_build_id() == b"0123456789abcdef" and lib.rdf_abi_version() == _lib.ABI_VERSION
+    assert alt in open("/proc/self/maps").read()
+    for name in ("frontend", "labels"):
+        rec = build.LIBRARIES[name]
+        assert _lib.library_path(name) == rec.so
+        assert getattr(_lib.load(name), rec.prefix + "build_id")().decode() == build.source_id(name)
+        stale = _copy_with_another_id(build, rec.so, tmp_path)
+        monkeypatch.setitem(build.LIBRARIES, name, rec._replace(so=stale))
+        monkeypatch.setattr(_lib, "_loaded", {})
+        with pytest.raises(_lib.RdfError, match="built from other sources"):
+            _lib.load(name)
+
+
+@pytest.mark.parametrize("name", LIBS)
+def test_a_missing_library_names_its_path_and_the_build_command(name, rdf, tmp_path, monkeypatch):
+    build, _lib = _modules()
+    monkeypatch.delenv("RDF_HIP_LIBRARY", raising=False)
+    gone = str(tmp_path / os.path.basename(build.LIBRARIES[name].so))
+    monkeypatch.setitem(build.LIBRARIES, name, build.LIBRARIES[name]._replace(so=gone))
+    monkeypatch.setattr(_lib, "_loaded", {})
+    with pytest.raises(_lib.RdfError, match="is missing: build it first") as e:
+        _lib.load(name)
+    assert gone in str(e.value) and "python __graft_entry__.py build" in str(e.value)

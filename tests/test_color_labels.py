@@ -8,7 +8,6 @@ library's, so PointsOps' new methods and ColorLabeler are exercised by the GPU t
 import importlib
 import json
 import os
-import re
 import shutil
 import subprocess
 
@@ -17,22 +16,12 @@ import pytest
 
 import frontend_numpy as fnp
 import labels_numpy as lnp
+from abi_helpers import declared
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "rdf_labels.h")
 PALETTE8 = np.array([[220, 40, 40], [40, 200, 60], [50, 60, 230], [230, 220, 50], [200, 50, 210], [40, 210, 220],
                      [250, 140, 30], [120, 120, 120]], np.uint8)
-
-
-def _declared(path):
-    text = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(rdf_[a-z0-9_]+)\s*\(", text)))
-
-
-def _exported(so):
-    nm = shutil.which("nm") or shutil.which("llvm-nm") or "/opt/rocm/lib/llvm/bin/llvm-nm"
-    out = subprocess.run([nm, "-D", "--defined-only", so], capture_output=True, text=True, check=True).stdout
-    return sorted({l.split()[-1] for l in out.splitlines() if l.split() and l.split()[-1].startswith("rdf_")})
 
 
 def _px(*rows):
@@ -128,30 +117,22 @@ def test_integer_and_fp32_nearest_colour_agree_on_every_pixel_value():
 
 
 def test_labels_library_exports_its_header(rdf):
+    """What only this library has; that it exports exactly its header, its ABI number, build id and target are
+    test_abi.py's, for every library alike."""
     _lib = importlib.import_module("3d-beats_amd._lib")
-    _build = importlib.import_module("3d-beats_amd._build")
-    _build.build()
-    names = _declared(HEADER)
-    assert sorted(_lib.LABELS_SIGNATURES) == names
-    assert _exported(_build.LABELS_SO) == names
+    importlib.import_module("3d-beats_amd._build").build()
+    names = declared(HEADER)
     for must in ("rdf_split_pixels_by_nearest_color", "rdf_apply_point_mapping", "rdf_depths_from_points",
                  "rdf_color_mapping_workspace_bytes", "rdf_make_color_mapping", "rdf_label_frame", "rdf_labels_abi_version",
                  "rdf_labels_build_id", "rdf_labels_error_string"):
         assert must in names
-    # the other two libraries are not touched
-    assert _exported(_build.SO) == sorted(_lib.SIGNATURES)
-    assert _exported(_build.FRONTEND_SO) == sorted(_lib.FRONTEND_SIGNATURES)
-    assert not set(names) & (set(_lib.SIGNATURES) | set(_lib.FRONTEND_SIGNATURES))
-    lib = _lib.load_labels()
-    assert lib.rdf_labels_abi_version() == _lib.LABELS_ABI_VERSION == 1
-    assert lib.rdf_labels_build_id().decode() == _build.labels_source_id() == _build.built_id(_build.LABELS_SO)
-    assert _build.built_id(_build.SO) == _build.source_id() and _build.built_id(_build.FRONTEND_SO) == _build.frontend_source_id()
+    lib = _lib.load("labels")
+    assert lib.rdf_labels_abi_version() == _lib.BINDINGS["labels"][0] == 1
     assert lib.rdf_color_mapping_workspace_bytes(8, 4) == 96 + 8 * 4 * 40
     assert lib.rdf_color_mapping_workspace_bytes(1, 1) == 8 + 40
     assert lib.rdf_color_mapping_workspace_bytes(9, 4) == 0 and lib.rdf_color_mapping_workspace_bytes(8, 17) == 0
     assert lib.rdf_color_mapping_workspace_bytes(8, 16) > 0
     assert b"NULL" in lib.rdf_labels_error_string(-2)
-    assert b"gfx950" in open(_build.LABELS_SO, "rb").read()
     # rejected arguments launch nothing, so they can be checked without a device
     assert lib.rdf_split_pixels_by_nearest_color(4, 4, 0, None, None, None, None) == -1
     assert lib.rdf_split_pixels_by_nearest_color(4, 4, 17, None, None, None, None) == -1
@@ -213,7 +194,7 @@ def test_restatement_recovers_a_painted_glove_scene():
 
 # ------------------------------------------------------------------ GPU ------------------------------------------------------
 def _lb():
-    return importlib.import_module("3d-beats_amd._lib").load_labels()
+    return importlib.import_module("3d-beats_amd._lib").load("labels")
 
 
 def _po():
