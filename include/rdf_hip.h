@@ -547,7 +547,7 @@ int rdf_event_destroy(void *event);
 int rdf_stream_synchronize(void *stream);
 
 int rdf_abi_version(void);
-/* Identity of the build: 16 hex digits of a SHA-256 over the library's sources (the four .hip files, rdf_device.hpp, this
+/* Identity of the build: 16 hex digits of a SHA-256 over the library's sources (the five .hip files, rdf_device.hpp, this
  * header) and its compiler flags, baked in at compile time (3d-beats_amd/_build.py).  The Python binding recomputes it from
  * the sources next to the library and refuses a library built from other sources (an ABI number cannot tell yesterday's
  * kernels from today's).  "unknown" for a build that did not define it. */
