@@ -108,3 +108,130 @@ def test_prepare_hand_depth_equals_the_chain_it_replaces(rdf, gpu_runtime):
     d = rdf.to_device(np.ones((4, 8), np.uint16))
     rc = gpu_runtime.lib.rdf_prepare_hand_depth(8, 4, 0, 1, d.ptr, d.ptr, d.ptr, 1, gpu_runtime.stream())
     assert rc == -1      # a flip in place is refused
+
+
+# ---- the branches no 16-byte-aligned, camera-sized input reaches ----
+
+def _ops():
+    return importlib.import_module("3d-beats_amd.cuda.points_ops").PointsOps()
+
+
+def _at_offset(rdf, flat, k, shape=None):
+    """`flat` on the device inside a larger buffer, starting k elements (2k bytes) past a 16-byte boundary: (the whole
+    buffer, the view of `flat`)."""
+    whole = rdf.to_device(np.concatenate([np.zeros(8 + k, np.uint16), flat.reshape(-1), np.zeros(8, np.uint16)]))
+    view = whole.view(np.uint16)[8 + k:8 + k + flat.size]
+    assert view.ptr % 16 == 2 * k
+    return whole, view.reshape(shape) if shape else view
+
+
+@pytest.mark.gpu
+def test_convert_0s_short_ranges_at_every_alignment(rdf, gpu_runtime):
+    """n = 1 .. 17 at every element offset 0 .. 7 from a 16-byte boundary: ranges shorter than the unaligned head (head > n),
+    head only, head + one vector, head + vector + tail.  Every element of the range starts as 0 in one pass and as a mix in
+    the other; the zeros on both sides of the range stay zero."""
+    ops = _ops()
+    rng = np.random.default_rng(41)
+    for n in (1, 2, 3, 7, 8, 9, 15, 16, 17):
+        for k in range(8):
+            for data in (np.zeros(n, np.uint16), rng.choice(np.array([0, 0, 1, 77, 65535], np.uint16), size=n)):
+                whole, view = _at_offset(rdf, data, k)
+                ops.convert_0s_to_maxuint(n, view)
+                want = np.concatenate([np.zeros(8 + k, np.uint16), po_np.convert_0s_to_maxuint(data.copy()),
+                                       np.zeros(8, np.uint16)])
+                assert np.array_equal(whole.get(), want), (n, k, whole.get(), want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [0, 1])
+def test_convert_0s_second_trip_of_the_grid_stride_loops(rdf, gpu_runtime, k):
+    """More vectors than the 2048 x 256 lanes of the capped grid: 2048 * 256 + 256 vectors plus a 5-element tail, aligned
+    and one element off (a 7-element head)."""
+    n = 2048 * 256 * 8 + 8 * 256 + 5
+    rng = np.random.default_rng(42 + k)
+    data = rng.integers(0, 4, size=n).astype(np.uint16) * np.uint16(21845)      # 0, 21845, 43690, 65535; a quarter zeros
+    data[[0, 1, 6, 7, 8, n - 6, n - 5, n - 1, 2048 * 256 * 8, 2048 * 256 * 8 + 7]] = 0
+    whole, view = _at_offset(rdf, data, k)
+    _ops().convert_0s_to_maxuint(n, view)
+    got = whole.get()
+    assert not got[:8 + k].any() and not got[-8:].any()
+    assert np.array_equal(got[8 + k:-8], po_np.convert_0s_to_maxuint(data.copy()))
+
+
+@pytest.mark.gpu
+def test_prepare_hand_depth_misaligned_pointers_at_vector_widths(rdf, gpu_runtime):
+    """Widths that are multiples of 8 (one lane, two lanes, one block row of 512, one lane and one block more) take the
+    16-byte path only when both pointers allow it: the input, the output, then both one element off a 16-byte boundary must
+    give the bytes of the aligned call -- the chain fill(0) -> stencil -> flip or copy -> convert_0s -- and leave the rows
+    before and after the output as they were."""
+    ops = _ops()
+    rng = np.random.default_rng(43)
+    for w in (8, 16, 512, 520, 1032):
+        for h in (1, 4, 5):
+            depth = rng.integers(0, 4, size=(h, w)).astype(np.uint16) * rng.integers(1, 16384, size=(h, w)).astype(np.uint16)
+            assert (depth == 0).any()
+            ins = [_at_offset(rdf, depth, k, (h, w))[1] for k in (0, 1)]
+            for level in (0, 1, 3):
+                f = 1 << level
+                gw, gh = max(w // f, 1), max(h // f, 1)
+                groups = rng.integers(0, 3, size=(gh, gw)).astype(np.uint16)
+                g_host = groups if w // f and h // f else groups[:0]
+                d_groups = rdf.to_device(groups)
+                for flip in (False, True):
+                    want = po_np.stencil_depth_image_by_group(w, h, level, 1, g_host, depth, np.zeros((h, w), np.uint16))
+                    want = want[:, ::-1].copy() if flip else want
+                    po_np.convert_0s_to_maxuint(want)
+                    for k_in, k_out in ((0, 0), (1, 0), (0, 1), (1, 1)):
+                        frame = np.full((h + 2, w), 7, np.uint16)            # a row before and a row after the output
+                        whole, framed = _at_offset(rdf, frame, k_out, (h + 2, w))
+                        out = framed[1:h + 1]
+                        assert out.ptr % 16 == (2 * (k_out + w)) % 16 == 2 * k_out
+                        ops.prepare_hand_depth(np.array([w, h], np.int32), level, 1, d_groups, ins[k_in], out, flip)
+                        got = whole.get()
+                        assert not got[:8 + k_out].any() and not got[-8:].any()
+                        got = got[8 + k_out:-8].reshape(h + 2, w)
+                        assert (got[0] == 7).all() and (got[-1] == 7).all(), (w, h, level, flip, k_in, k_out)
+                        assert np.array_equal(got[1:-1], want), (w, h, level, flip, k_in, k_out)
+
+
+@pytest.mark.gpu
+def test_setup_depth_keeps_points_whose_w_is_tiny_or_nan(rdf, gpu_runtime):
+    """w == 0.0f is true for -0.0 and for nothing else: NaN, the subnormals and the smallest normal numbers of either sign
+    are points that stay (a build that flushed subnormals would drop them)."""
+    tiny, sub = np.finfo(np.float32).tiny, np.float32(1e-45)
+    ws = np.array([0.0, -0.0, np.nan, sub, -sub, np.float32(5.9e-39), np.float32(-5.9e-39), tiny, -tiny, 1.0, -np.nan],
+                  np.float32)
+    assert ws[3] > 0 and ws[5] < tiny and np.signbit(ws[1])
+    n = 300                                                     # two blocks
+    pts = np.random.default_rng(44).standard_normal((n, 4)).astype(np.float32)
+    pts[:, 3] = ws[np.arange(n) % ws.size]
+    depth = np.where(np.arange(n) % 13 == 0, 0, 1234).astype(np.uint16)
+    want = po_np.setup_depth_image_for_forest(pts, depth.copy())
+    keep = (depth != 0) & (np.arange(n) % ws.size >= 2)
+    assert (want[keep] == 1234).all() and (want[~keep] == 65535).all()
+    dev = rdf.to_device(depth)
+    _ops().setup_depth_image_for_forest(n, rdf.to_device(pts), dev)
+    assert np.array_equal(dev.get(), want), np.flatnonzero(dev.get() != want)
+
+
+@pytest.mark.gpu
+def test_rgba_without_colors_and_flip_x_at_the_block_width(rdf, gpu_runtime):
+    """num_colors = 0 (no colour table at all): every label is beyond it and the image stays as it was.  flip_x at one
+    column, and one under, at and over the 64 columns of a block."""
+    ops = _ops()
+    rng = np.random.default_rng(45)
+    labels = rng.integers(0, 6, size=(5, 70)).astype(np.uint16)
+    labels[2, 3:9] = 65535
+    before = rng.integers(0, 256, size=(5, 70, 4)).astype(np.uint8)
+    img = rdf.to_device(before)
+    ops.make_rgba_from_labels(70, 5, 0, rdf.to_device(labels), None, img)
+    assert np.array_equal(img.get(), before)
+    assert np.array_equal(po_np.make_rgba_from_labels(labels, np.zeros((0, 4), np.uint8), before.copy()), before)
+    for w in (1, 63, 64, 65):
+        for h in (1, 5):
+            src = rng.integers(0, 65536, size=(h, w)).astype(np.uint16)
+            whole, out = _at_offset(rdf, np.full((h, w), 7, np.uint16), 0, (h, w))
+            ops.flip_x(np.array([w, h], np.int32), rdf.to_device(src), out)
+            got = whole.get()
+            assert not got[:8].any() and not got[-8:].any()
+            assert np.array_equal(got[8:-8].reshape(h, w), po_np.flip_x(src, np.zeros((h, w), np.uint16))), (w, h)
