@@ -21,6 +21,7 @@ from .frontend import FrameFrontEnd  # noqa: F401
 from .grouping import HandGrouping  # noqa: F401
 from .host_stream import HostFramesEvaluator  # noqa: F401
 from .pipeline import HandPipeline  # noqa: F401
+from .rerender import SceneRerender  # noqa: F401
 from .util import MAX_UINT16  # noqa: F401
 
 _REFERENCE_MODULE_NAMES = ("decision_tree", "util", "engine", "engine.buffer", "cuda", "cuda.points_ops", "cuda.mean_shift",
@@ -50,6 +51,6 @@ def install_reference_aliases(force=False):
 
 
 __all__ = ["DecisionTree", "DecisionForest", "LayeredDecisionForest", "DecisionTreeEvaluator", "DecisionTreeTrainer",
-           "GpuBuffer", "CalibratedPlane", "ColorLabeler", "RecordingConverter", "FrameFrontEnd", "HandGrouping", "HandPipeline", "HostFramesEvaluator",
+           "GpuBuffer", "CalibratedPlane", "ColorLabeler", "RecordingConverter", "SceneRerender", "FrameFrontEnd", "HandGrouping", "HandPipeline", "HostFramesEvaluator",
            "DeviceArray", "HipRuntime", "MAX_UINT16", "RdfError", "device_ptr", "get_runtime", "set_runtime",
            "to_device", "host_mapped_array", "library_path", "synth", "install_reference_aliases"]

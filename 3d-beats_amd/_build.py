@@ -28,8 +28,9 @@ LIBRARIES = {lib.key: lib for lib in (
     # the depth front end
     Library("frontend", os.path.join(HERE, "csrc", "librdf_frontend.so"), [os.path.join(HERE, "csrc", "frontend_hip.hip")],
             [os.path.join(HERE, "..", "include", "rdf_frontend.h")], "rdf_frontend_"),
-    # glove-colour recordings to training labels
-    Library("labels", os.path.join(HERE, "csrc", "librdf_labels.so"), [os.path.join(HERE, "csrc", "labels_hip.hip")],
+    # glove-colour recordings to training labels, and the re-render that augments them
+    Library("labels", os.path.join(HERE, "csrc", "librdf_labels.so"),
+            [os.path.join(HERE, "csrc", "labels_hip.hip"), os.path.join(HERE, "csrc", "rerender_hip.hip")],
             [os.path.join(HERE, "..", "include", "rdf_labels.h")], "rdf_labels_"),
 )}
 

@@ -3,6 +3,9 @@
  * behind the reference's src/live_data_convert.py: split_pixels_by_nearest_color, apply_point_mapping and
  * depths_from_points (src/cuda/points_ops.cu:207-255, 167-205, 39-63), the whole of its make_color_mapping
  * (live_data_convert.py:156-204) as device work, and the per-frame labelling of its tick() (:413-458) as one pass.
+ * And the converter's augmentation: the centre of a frame's points (rdf_points_center) and the re-render of the moved
+ * scene (rdf_rerender), a software rasteriser in place of the reference's OpenGL draw; those two are fp32 / fp64 with a
+ * stated operation order, described with their declarations below.
  *
  * It is a library of its own, next to librdf_hip.so and librdf_frontend.so, with its own ABI number and build id.
  * Conventions are those of rdf_hip.h: every pointer is caller-owned DEVICE memory; nothing is allocated, freed or
@@ -13,7 +16,7 @@
  * Images: colour uint8 [dim_y][dim_x][3] (r, g, b), 4-byte aligned (pixels are read four at a time as three dwords);
  * colours / mappings uint8 [K][3].  1 <= K <= RDF_LABELS_MAX_COLORS, 1 <= tries <= RDF_LABELS_MAX_TRIES.
  *
- * Arithmetic is integer throughout, so every result is independent of the order in which pixels are visited:
+ * Arithmetic of the colour kernels is integer throughout, so every result is independent of the order in which pixels are visited:
  *   skipped pixel    r + g + b == 0.
  *   nearest colour   d(i) = (r - c_i.r)^2 + (g - c_i.g)^2 + (b - c_i.b)^2 (each term <= 65 025, d <= 195 075); colour 0
  *                    first, then a strictly smaller d wins: ties go to the lowest index.  The reference computes d in fp32,
@@ -34,7 +37,11 @@
 extern "C" {
 #endif
 
-/* 1: first version. */
+/*
+ * 1: first version.  The number changes when something declared here is removed or re-typed; a pure addition (as
+ * rdf_points_center and rdf_rerender were) keeps it, since every caller of the older entry points still links and runs.
+ * Two builds with the same number are told apart by rdf_labels_build_id().
+ */
 #define RDF_LABELS_ABI_VERSION 1
 
 #ifndef RDF_OK
@@ -107,6 +114,69 @@ int rdf_label_frame(int dim_x, int dim_y, int num_colors, const uint8_t *mapping
  * needs it before rdf_make_color_mapping, which the reference runs on the masked image.
  */
 int rdf_mask_color_image(int dim_x, int dim_y, uint8_t *image, const uint16_t *mask_labels, int mask_label, void *stream);
+
+/*
+ * The four component sums of pts float32 [n_pts][4] (16-byte aligned) as sums double[4] in device memory; the caller
+ * divides by sums[3] (live_data_convert.py:363-364, where every point is read back to the host to be summed).
+ * fp64 in a fixed two-level order, without float atomics, so the result is the same from run to run: B = min(ceil(n_pts /
+ * 256), 1024) workgroups of 256 lanes; lane t of workgroup b adds points b * 256 + t, + B * 256, ... in that order, the
+ * workgroup's 256 sums are halved (t += t + 128, t += t + 64, ..., t += t + 1) into its partial; one workgroup then sums
+ * the partials the same way (lane t takes partials t, t + 256, ...).  n_pts == 0 gives zeros.
+ * workspace: rdf_points_center_workspace_bytes(n_pts) bytes, 8-byte aligned, contents irrelevant before and after.
+ */
+size_t rdf_points_center_workspace_bytes(int n_pts);
+int rdf_points_center(int n_pts, const float *pts, void *workspace, double *sums, void *stream);
+
+/*
+ * The re-render of live_data_convert.py:207-282 (rerender_image: make_triangles, std_camera.vert / .frag through OpenGL) as
+ * a software rasteriser: the frame's points become a triangle mesh, the mesh is moved by obj_tform and drawn back into a
+ * new depth image and a new colour image.  A GL driver's rasteriser cannot be matched bit for bit and is not; the rules
+ * below are this library's own, tests/rerender_numpy.py restates them, and the kernels match that bit for bit.
+ *
+ *   pts float32 [dim_y][dim_x][4] (16-byte aligned), camera space; color uint8 [dim_y][dim_x][3]; obj_tform: 16 floats in
+ *   HOST memory, row-major, read during the call (as rdf_transform_points takes its matrix), last row exactly (0, 0, 0, 1);
+ *   f > 0, ppx, ppy: the depth camera; 0 < zmin <= zmax: the near and far plane (the converter passes 50 and 50000).
+ *   depth_out uint16 [dim_y][dim_x], color_out uint8 [dim_y][dim_x][3] (not the input colour): every pixel is written;
+ *   a pixel nothing covers gets depth 0 and colour (0, 0, 0), as after glClear.  dim_x, dim_y <= 32768 (else
+ *   RDF_ERR_TOO_LARGE); a matrix that is not affine, f <= 0 or an empty or non-finite depth range is RDF_ERR_BAD_ARG.
+ *
+ * 1. Mesh (points_ops.cu:77-115).  Quad (x, y), x < dim_x - 1 and y < dim_y - 1, exists iff its four corner points have
+ *    w > 0.  It gives triangle 0 = (p00, p01, p10) and triangle 1 = (p01, p10, p11), p01 = point (y, x + 1), p10 = point
+ *    (y + 1, x).  Triangle id = 2 * (y * (dim_x - 1) + x) + k: fixed, where the reference draws them in the order of an
+ *    atomic counter.  No index buffer is written.
+ * 2. Vertex (std_camera.vert).  p' = M (x, y, z, 1) in fp32, each of the three rows as ((m0 * x + m1 * y) + m2 * z) + m3,
+ *    every operation rounded (no fused multiply-add).  A triangle with a vertex whose z' is not > 0 is dropped (GL would
+ *    clip a triangle that crosses the near plane; this does not).
+ * 3. Projection (util.rs_projection, reduced to what reaches the viewport).  sx = (f * x') / z' + ppx, sy = (f * y') / z' +
+ *    ppy, snapped to 1/256 pixel: X = (integer) floor(sx * 256 + 0.5), Y likewise.  A triangle with a vertex whose |X| or
+ *    |Y| exceeds 2^20 (or is NaN) is dropped.  Pixel (i, j) is sampled at (256 i + 128, 256 j + 128).  So a vertex
+ *    deprojected from pixel x (which deproject_points places at sx = x) sits on that pixel's top-left corner, half a pixel
+ *    from its centre, exactly as in the reference: THE IDENTITY TRANSFORM RESAMPLES THE FRAME BY HALF A PIXEL AND LOSES ITS
+ *    LAST ROW AND COLUMN.
+ * 4. Coverage.  Integer arithmetic (int64).  E(A, B, P) = (B.X - A.X) * (P.Y - A.Y) - (B.Y - A.Y) * (P.X - A.X); area =
+ *    E(V0, V1, V2), a triangle of area 0 is dropped, sgn = the area's sign: both windings are drawn (GL's default, no
+ *    culling).  e0 = sgn * E(V1, V2, P), e1 = sgn * E(V2, V0, P), e2 = sgn * E(V0, V1, P).  P is covered iff every e_k > 0,
+ *    or e_k == 0 on a top or left edge: with D = sgn * (B - A) the edge's direction, D.Y < 0 (left) or D.Y == 0 and D.X > 0
+ *    (top).  A pixel centre on an edge shared by two triangles belongs to exactly one of them.
+ * 5. Attributes, perspective-correct as GL interpolates v_depth and v_color: w_k = e_k as fp32 (round to nearest even),
+ *    q_k = w_k / z'_k, s = (q0 + q1) + q2, z = ((w0 + w1) + w2) / s, channel c = ((q0 * c0 + q1 * c1) + q2 * c2) / s stored
+ *    as min(255, floor(c + 0.5)).  A fragment whose z is not within [zmin, zmax] is discarded.  Depth is stored as z
+ *    truncated to uint16 (std_camera.frag:20), 65535 at most.
+ * 6. Depth test.  A pixel keeps the fragment with the smallest 64-bit key (bits(z) << 32) | triangle id: the nearest one
+ *    (z > 0, so the bit pattern orders as the value), ties to the lowest id.  An integer minimum does not depend on the
+ *    order in which fragments arrive.
+ *
+ * workspace: rdf_rerender_workspace_bytes(dim_x, dim_y) bytes (one key per pixel), 8-byte aligned.  EVERY BYTE MUST BE
+ * 0xFF BEFORE THE FIRST CALL (the empty key); each call leaves it so, so one fill serves every later frame of that size.
+ * Two launches: one lane per quad sets up its two triangles, walks their bounding boxes clipped to the frame and takes the
+ * 64-bit atomic minimum per covered pixel; then one lane per pixel recomputes the winner's attributes from its id, writes
+ * depth and colour and resets the key.  The first launch costs time in proportion to the summed bounding boxes: a
+ * transform that blows one triangle up to the whole frame makes every lane of that workgroup walk the frame.
+ */
+size_t rdf_rerender_workspace_bytes(int dim_x, int dim_y);
+int rdf_rerender(int dim_x, int dim_y, const float *pts, const uint8_t *color, const float *obj_tform_host, float f,
+                 float ppx, float ppy, float zmin, float zmax, void *workspace, uint16_t *depth_out, uint8_t *color_out,
+                 void *stream);
 
 int rdf_labels_abi_version(void);
 const char *rdf_labels_build_id(void);
