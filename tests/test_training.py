@@ -62,8 +62,8 @@ def test_numpy_trainer_learns_a_separable_problem(rdf, oracle):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("sorted_rows", [True, False], ids=["sorted_rows", "wave_atomics"])
-@pytest.mark.parametrize("cfg", [(6, 2, 16, 1 << 17), (5, 1, 40, 1 << 17), (7, 3, 8, 8)],
-                         ids=["D6_2x16", "D5_1x40", "D7_3x8_nodeblocks8"])
+@pytest.mark.parametrize("cfg", [(6, 2, 16, 1 << 17), (5, 1, 40, 1 << 17), (7, 3, 8, 8), (6, 1, 130, 1 << 17), (5, 2, 72, 8)],
+                         ids=["D6_2x16", "D5_1x40", "D7_3x8_nodeblocks8", "D6_1x130", "D5_2x72_nodeblocks8"])
 def test_device_trainer_matches_restatement_bit_for_bit(cfg, sorted_rows, rdf, gpu_runtime):
     """Both ways of counting -- rows of decision bits in (node, class) order (the default) and the histogram kernel with
     its per-wave atomics -- train the restatement's tree, bit for bit."""
