@@ -371,9 +371,12 @@ struct EvalArgsN {
 //                         launches) | DEEP walk the deep levels from the deep blocks
 //   per workgroup, once   "stage the top K levels": the node table's top levels into LDS; which tables serve the forest
 //                         (last-level table, deep blocks: their trailers)
-//   per tile              "take the next tile" (static first tile, then the per-XCD queues; a helper launch's workgroups have no
-//                         static tile: rdf_eval_forest_packed_split) -> which pixels the lanes of a wave stand on (one row of 64, or
-//                         -- narrow tiles for a label map's last columns -- `fold` rows of 64 / fold) -> "empty tile?" -> "stage
+//   per tile              "take the next tile": the workgroup's own index first; after that "the look-ahead wave" -- the first wave to
+//                         leave the pixel loop of the tile before (the election at the loop's end) -- pulls from the per-XCD queues
+//                         (pull_tile; a helper launch's workgroups have no static tile: rdf_eval_forest_packed_split), looks at
+//                         every tile it pulls (rows_have_pixels) and posts the first one with a pixel to evaluate; TW: thread 0
+//                         pulls -> which pixels the lanes of a wave stand on (place_tile: one row of 64, or -- narrow tiles for a
+//                         label map's last columns -- `fold` rows of 64 / fold) -> "empty tile, tree waves" (TW only) -> "stage
 //                         depth" into LDS at address 0 -> "compact" (COMPACT only)
 //   per pixel group       early-outs (tree_eval.cu:81-89; DEEP: a lane without a pixel stays in the loop with idle tree slots, `live`,
 //                         because the wave fetches its deep blocks together), the pixel's reciprocal, then per CMAX classes and per GROUP trees:
@@ -461,7 +464,8 @@ __global__ __launch_bounds__(BLOCK, TW ? 8 : DEEP ? 4 : BLOCK == 512 ? 6 : BLOCK
             lds_nodes[i] = make_uint4(r.w[0], r.w[1], r.w[2], r.w[3]);
         }
     }
-    if (tid == 0) s_tile[2] = s_tile[3] = 0u;   // (made visible by the first tile's barrier)
+    if (tid == 0) s_tile[2] = s_tile[3] = s_tile[4] = s_tile[5] = s_tile[6] = 0u;   // (made visible by the first tile's barrier; a helper launch's wave 0
+                                                                                     // reads [6] before it: the same wave)
     // (STATS) per-lane visit counters: pixels, node records read, leaves reached; and what a launch with THIS geometry needs
     // from the vector memory pipeline at the least: node records read from LDS, and 128-byte lines touched by the loads that
     // serve walking slots -- records and leaf rows from global memory, far probes that load, deep blocks -- counted per wave
@@ -487,70 +491,194 @@ __global__ __launch_bounds__(BLOCK, TW ? 8 : DEEP ? 4 : BLOCK == 512 ? 6 : BLOCK
         return (active && (!prev_active || prev != line)) ? 1u : 0u;
     };
     const char *depth_b = reinterpret_cast<const char *>(a.depth);
-    uint32_t static_tile = block_id;
     const uint32_t xcc = (uint32_t)__builtin_amdgcn_s_getreg(20 | (31 << 11)) & 7u;   // HW_REG_XCC_ID: the XCD this workgroup runs on
-    uint32_t q_empty = 0u;                   // (thread 0) queues found empty so far
     const uint32_t q_static = a.q_static ? a.q_static : n_blocks;      // tiles handed out statically (split launches: the main launch's grid)
     const uint32_t q_blocks = a.q_blocks ? a.q_blocks : n_blocks;      // workgroups that finish on this slot
     const uint32_t queued = a.n_tiles > q_static ? a.n_tiles - q_static : 0u;   // tiles the queues hand out (the first q_static are static)
 
-    for (uint32_t it = 0;; ++it) {
-        // ---- take the next tile: 64 label columns x tile_rows label rows of one image ----
-        uint32_t tile;
-        if (a.sched) {
-            // A workgroup's FIRST tile is its own index: no atomic round trip in front of the first staging (2-3 us
-            // of every launch), and a launch with no more tiles than workgroups -- one live frame -- touches no queue at
-            // all: no pull, no failing pulls at the end, no finished-workgroup count.  The queues hand out the rest.
-            if (it == 0u && !a.q_helper) {
-                __syncthreads();
-                tile = block_id;     // (a permutation that hands each XCD a contiguous run of first tiles was tried: a
-                                     // four-frame batch 0.24 -> 0.29 ms, larger batches unchanged)
-            } else {
-                if (queued == 0u) break;             // (workgroup-uniform)
-                if (tid == 0) {
-                    uint32_t t = a.n_tiles;      // nothing left anywhere
-                    if (q_static < kXcdQueuesFrom) {            // a small launch: one queue (head 0) over the rest
-                        const uint32_t got = atomicAdd(a.sched, 1u);
-                        if (got < queued) t = q_static + got;
-                    } else {
-                        // nothing guarantees that every XCD runs a workgroup of this launch (CU masks), so some workgroups
-                        // -- eight consecutive ones in every 128, workgroups 0-7 always among them -- go round all queues
-                        // (and every workgroup does when the queues hold several rounds of tiles: a few frames of uneven
-                        // cost are uneven ranges, and the failing pulls at the end are a small share of such a launch)
-                        const uint32_t reach = (((block_id >> 3) & 15u) == 0u || queued >= 2u * q_static || a.q_helper) ? 7u : kStealFrom;
-                        for (uint32_t k = 0; k <= reach; ++k) {
-                            const uint32_t q = (xcc + k) & 7u;
-                            if ((q_empty >> q) & 1u) continue;
-                            const uint32_t lo = (uint32_t)(((unsigned long long)queued * q) >> 3);
-                            const uint32_t hi = (uint32_t)(((unsigned long long)queued * (q + 1u)) >> 3);
-                            const uint32_t got = lo < hi ? atomicAdd(a.sched + q * kSchedStride, 1u) : hi;
-                            if (lo < hi && got < hi - lo) { t = q_static + lo + got; break; }
-                            q_empty |= 1u << q;
-                        }
-                    }
-                    s_tile[it & 1u] = t;
-                }
-                __syncthreads();   // also: every wave is done with the previous tile's LDS image
-                tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_tile[it & 1u]);   // scalar: the tile's geometry and image base stay in SGPRs
-            }
-        } else {
-            __syncthreads();
-            tile = static_tile;
-            static_tile += n_blocks;
-        }
-        if (tile >= a.n_tiles) break;
+    // where a tile lies: its image, its first label pixel, and how a wave's 64 lanes sit on it -- one row of 64 pixels, or
+    // (narrow tiles, an image's last columns) `fold` rows of 64 / fold
+    struct TilePlace { uint32_t img, x0, y0, fold, col_shift; bool narrow; };
+    auto place_tile = [&](uint32_t tile) -> TilePlace {
         const uint32_t tiles_wide = a.tiles_x * a.tiles_y;          // an image's ordinary tiles, then its narrow ones
         const uint32_t tiles_per_img = tiles_wide + a.tiles_y_n;
-        const uint32_t img = tile / tiles_per_img;
-        const uint32_t trem = tile - img * tiles_per_img;
-        const bool narrow = trem >= tiles_wide;                     // (scalar)
-        const uint32_t ty = narrow ? trem - tiles_wide : trem / a.tiles_x;
-        const uint32_t tx = narrow ? a.tiles_x : trem - ty * a.tiles_x;
-        // where a wave's 64 lanes sit: one row of 64 pixels, or (narrow tiles) `fold` rows of 64 / fold
-        const uint32_t fold = narrow ? a.fold : 1u;
-        const uint32_t col_shift = narrow ? (a.fold == 4u ? 4u : 5u) : 6u;
+        TilePlace p;
+        p.img = tile / tiles_per_img;
+        const uint32_t trem = tile - p.img * tiles_per_img;
+        p.narrow = trem >= tiles_wide;                              // (scalar)
+        const uint32_t ty = p.narrow ? trem - tiles_wide : trem / a.tiles_x;
+        const uint32_t tx = p.narrow ? a.tiles_x : trem - ty * a.tiles_x;
+        p.fold = p.narrow ? a.fold : 1u;
+        p.col_shift = p.narrow ? (a.fold == 4u ? 4u : 5u) : 6u;
+        p.x0 = tx * 64u, p.y0 = ty * tile_rows * p.fold;
+        return p;
+    };
+    // ---- empty tile?  (live frames are mostly background.)  The centre depths of the tile's rows first, first + step, ...
+    // straight from global memory, one pixel per lane and row: true when some lane of this wave stands on a pixel to
+    // evaluate.  The loads of four rows are issued together and without a branch, so a wave that looks at a whole tile
+    // waits for a few round trips, not for one per row: a row below the tile or the label map is read as the tile's last
+    // row inside the map -- a pixel of this tile, which may be looked at as often as one likes.
+    // store_fails: a pixel that fails gets the fused pre-fill's 65535 here (the caller's a.fill_untouched). ----
+    auto rows_have_pixels = [&](const TilePlace &p, uint32_t first, uint32_t step, bool store_fails) -> bool {
+        const uint32_t lane_col = (uint32_t)lane & ((1u << p.col_shift) - 1u), lane_row = (uint32_t)lane >> p.col_shift;
+        const uint32_t lx = p.x0 + lane_col;
+        const int y_last = min(a.Hl, (int)(p.y0 + tile_rows * p.fold)) - 1;
+        const uint32_t img_boff = (p.img * a.per_img_d) << 1, img_loff = p.img * a.per_img_l;
+        const uint32_t dy = step * p.fold;
+        uint32_t ly = p.y0 + first * p.fold + lane_row;
+        uint32_t seen = 0u;     // max of (depth + 1) mod 2^16 over the pixels: above 1 iff one of them is neither 0 nor 65535
+        if ((int)lx < a.Wl) {
+#pragma clang loop unroll(disable)
+            for (uint32_t trow = first; trow < tile_rows; trow += 4u * step, ly += 4u * dy) {
+                uint32_t i[4], d[4];
+#pragma unroll
+                for (uint32_t k = 0; k < 4u; ++k) {
+                    const uint32_t y = (uint32_t)min((int)(ly + k * dy), y_last);
+                    i[k] = img_loff + y * (uint32_t)a.Wl + lx;
+                    d[k] = *reinterpret_cast<const uint16_t *>(
+                        depth_b + (img_boff + ((__umul24(y * (uint32_t)a.r, (uint32_t)a.W) + lx * (uint32_t)a.r) << 1)));
+                }
+                if (a.filter_class != -1) {
+                    uint32_t f[4];
+#pragma unroll
+                    for (uint32_t k = 0; k < 4u; ++k) f[k] = a.filter[i[k]];
+#pragma unroll
+                    for (uint32_t k = 0; k < 4u; ++k) d[k] = (int)f[k] == a.filter_class ? d[k] : 0u;
+                }
+#pragma unroll
+                for (uint32_t k = 0; k < 4u; ++k) {
+                    d[k] = (d[k] + 1u) & 0xFFFFu;
+                    seen = max(seen, d[k]);
+                    if (store_fails && d[k] <= 1u) a.labels[i[k]] = (uint16_t)kNoPixel;
+                }
+            }
+        }
+        return seen > 1u;
+    };
+    // the fused pre-fill of a tile that is not walked at all
+    auto fill_tile = [&](const TilePlace &p) {
+        const uint32_t lane_col = (uint32_t)lane & ((1u << p.col_shift) - 1u), lane_row = (uint32_t)lane >> p.col_shift;
+        const int lx = (int)(p.x0 + lane_col);
+#pragma clang loop vectorize(disable) unroll(disable)
+        for (uint32_t trow = 0; trow < tile_rows; ++trow) {
+            const int ly = (int)(p.y0 + trow * p.fold + lane_row);
+            if (ly < a.Hl && lx < a.Wl) a.labels[p.img * a.per_img_l + (uint32_t)ly * (uint32_t)a.Wl + (uint32_t)lx] = (uint16_t)kNoPixel;
+        }
+    };
+    // ---- one lane takes a tile off the queues (or, without queues, the tile n_blocks behind `after`); a.n_tiles: nothing left.
+    // q_empty: queues found empty so far (the puller's own; between look-ahead waves it travels in the mailbox) ----
+    auto pull_tile = [&](uint32_t after, uint32_t &q_empty) -> uint32_t {
+        if (!a.sched) return after + n_blocks < a.n_tiles ? after + n_blocks : a.n_tiles;
+        uint32_t t = a.n_tiles;      // nothing left anywhere
+        if (q_static < kXcdQueuesFrom) {            // a small launch: one queue (head 0) over the rest
+            const uint32_t got = atomicAdd(a.sched, 1u);
+            if (got < queued) t = q_static + got;
+        } else {
+            // nothing guarantees that every XCD runs a workgroup of this launch (CU masks), so some workgroups
+            // -- eight consecutive ones in every 128, workgroups 0-7 always among them -- go round all queues
+            // (and every workgroup does when the queues hold several rounds of tiles: a few frames of uneven
+            // cost are uneven ranges, and the failing pulls at the end are a small share of such a launch)
+            const uint32_t reach = (((block_id >> 3) & 15u) == 0u || queued >= 2u * q_static || a.q_helper) ? 7u : kStealFrom;
+            for (uint32_t k = 0; k <= reach; ++k) {
+                const uint32_t q = (xcc + k) & 7u;
+                if ((q_empty >> q) & 1u) continue;
+                const uint32_t lo = (uint32_t)(((unsigned long long)queued * q) >> 3);
+                const uint32_t hi = (uint32_t)(((unsigned long long)queued * (q + 1u)) >> 3);
+                const uint32_t got = lo < hi ? atomicAdd(a.sched + q * kSchedStride, 1u) : hi;
+                if (lo < hi && got < hi - lo) { t = q_static + lo + got; break; }
+                q_empty |= 1u << q;
+            }
+        }
+        return t;
+    };
+    // Without queues a workgroup walks tiles block_id, block_id + n_blocks, ...; with them, its own index first and then what
+    // the queues hand out -- and a launch with no more tiles than workgroups (one live frame) is over after that first tile.
+    const bool more_tiles = a.sched ? queued != 0u : block_id + n_blocks < a.n_tiles;      // (workgroup-uniform)
+    // (not TW) this wave looks ahead at the next tile change: the first wave that left the previous tile's pixel loop -- or
+    // wave 0 where no tile was walked before (a helper launch's workgroups have no static tile; a first tile found empty)
+    bool scout = !TW && a.sched && a.q_helper && wave == 0u;
+    uint32_t q_empty = 0u;      // (TW: thread 0) queues found empty so far
+    uint32_t tile = block_id;
+
+    for (uint32_t it = 0;; ++it) {
+        // ---- take the next tile: 64 label columns x tile_rows label rows of one image ----
+        // A workgroup's FIRST tile is its own index: no atomic round trip in front of the first staging (2-3 us
+        // of every launch), and a launch with no more tiles than workgroups -- one live frame -- touches no queue at
+        // all: no pull, no failing pulls at the end, no finished-workgroup count.  The queues hand out the rest.
+        // (a permutation that hands each XCD a contiguous run of first tiles was tried: a four-frame batch 0.24 -> 0.29 ms,
+        // larger batches unchanged)
+        const bool own_tile = it == 0u && !(a.sched && a.q_helper);     // (workgroup-uniform)
+        if (!own_tile && !more_tiles) break;
+        if (TW) {
+            // Tree waves are small launches, mostly of one tile per workgroup, whose duration is one wave's instruction
+            // count: thread 0 pulls, and every wave looks at its own rows ("empty tile, tree waves" below).  With the
+            // look-ahead wave's code in this kernel one frame at labels_reduce 2 took two to three microseconds longer
+            // (profiles/tile_lookahead_ab.txt).
+            if (!own_tile && tid == 0) s_tile[it & 1u] = pull_tile(tile, q_empty);
+        } else {
+            // ---- Two ways to a tile that has a pixel to evaluate (a.check_empty: launches that fill the chip, and small ones
+            // at labels_reduce > 1 -- eval_common; other launches take every tile).
+            // The workgroup's own first tile: no wave has finished anything yet, so every wave looks at its own rows
+            // (wave, wave + kWaves, ...) and says "some pixel" in s_tile[2]; a pixel that fails gets the fused pre-fill.
+            // Every later tile: the look-ahead wave -- ONE wave of the workgroup, while the others finish the tile before
+            // or wait at the barrier below -- pulls a tile, looks at ALL of its rows itself, and goes on to the next one
+            // while no lane finds a pixel: an empty tile costs the workgroup no barrier at all, and its pixels get the
+            // fused pre-fill here.  The tile it stops at -- or a.n_tiles: this workgroup's final, failing pull -- is posted
+            // in s_tile[it & 1].
+            // Both go through ONE copy of the row check (the library's size: tests/test_abi.py), hence one loop: own_tile
+            // leaves it after its single pass.
+            // The mailbox: s_tile[0..1] the posted tiles, [2] the first tile's "some pixel" word, [4..5] the election
+            // words, [6] q_empty (the look-ahead wave changes from tile to tile; two of them are a barrier apart). ----
+            if (own_tile && a.check_empty) __syncthreads();      // (the mailbox words of the prologue)
+            if (scout || (own_tile && a.check_empty)) {
+                uint32_t t = tile;
+                q_empty = s_tile[6];
+                for (;;) {
+                    if (!own_tile) {
+                        if (lane == 0) t = pull_tile(t, q_empty);
+                        t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+                    }
+                    if (t >= a.n_tiles || !a.check_empty) break;
+                    const TilePlace p = place_tile(t);
+                    const bool any = (p.narrow ? a.tw_n : a.tw) <= 0 ||
+                                     __any(rows_have_pixels(p, own_tile ? wave : 0u, own_tile ? kWaves : 1u, own_tile && a.fill_untouched));
+                    if (own_tile) {
+                        // workgroup-wide OR through a mailbox word (__syncthreads_or would bring the runtime's static LDS
+                        // scratch, which moves the depth tile away from LDS address 0)
+                        if (any && lane == 0) s_tile[2] = 1u;
+                        break;
+                    }
+                    if (any) break;
+                    if (a.fill_untouched) fill_tile(p);
+                }
+                if (!own_tile && lane == 0) {
+                    s_tile[it & 1u] = t;
+                    s_tile[6] = q_empty;
+                }
+            }
+            scout = false;
+        }
+        __syncthreads();   // also: every wave is done with the previous tile's LDS image
+        if (!own_tile) {
+            tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_tile[it & 1u]);   // scalar: the tile's geometry and image base stay in SGPRs
+            // Election word (it + 1) & 1 -- the one tile it - 1 used, and tile it + 1 will use -- is cleared here: every
+            // wave made its add for tile it - 1 before this barrier, and the adds for tile it + 1 come behind the barrier at
+            // the top of tile it + 1.  (The two words alternate as the two posted tiles do: a word is written again only
+            // when a barrier separates the writer from every reader.  After a first tile found empty nobody was elected:
+            // then this clears a word that is zero, and tile 1's word is zero from the prologue.)
+            if (!TW && tid == 0) s_tile[4u + ((it + 1u) & 1u)] = 0u;
+        }
+        if (tile >= a.n_tiles) break;
+        if (!TW && own_tile && a.check_empty && s_tile[2] == 0u) {     // (workgroup-uniform) the first tile is not staged:
+            scout = wave == 0u;                                        // nobody left a pixel loop, wave 0 looks ahead
+            continue;
+        }
+        const TilePlace tp = place_tile(tile);
+        const uint32_t img = tp.img;
+        const bool narrow = tp.narrow;                              // (scalar)
+        const uint32_t fold = tp.fold, col_shift = tp.col_shift;
         const uint32_t lane_col = (uint32_t)lane & ((1u << col_shift) - 1u), lane_row = (uint32_t)lane >> col_shift;
-        const uint32_t x0 = tx * 64u, y0 = ty * tile_rows * fold;   // the tile's first label pixel
+        const uint32_t x0 = tp.x0, y0 = tp.y0;                      // the tile's first label pixel
         const int lx = (int)(x0 + lane_col);
         const uint32_t img_boff = (img * a.per_img_d) << 1;
         const uint32_t img_loff = img * a.per_img_l;
@@ -564,10 +692,10 @@ __global__ __launch_bounds__(BLOCK, TW ? 8 : DEEP ? 4 : BLOCK == 512 ? 6 : BLOCK
                             (uint32_t)tw * 2u, (uint32_t)th, (uint32_t)twp * 2u, (uint32_t)a.W * 2u, (uint32_t)a.H,
                             (uint32_t)tx0 * 2u, (uint32_t)ty0};
 
-        // ---- empty tile?  (live frames are mostly background.)  Every wave looks at the centre depths of its
-        // own rows straight from global memory; a tile without a single pixel to evaluate is not staged.
+        // ---- empty tile, tree waves: every wave looks at the centre depths of its own rows straight from global memory; a
+        // tile without a single pixel to evaluate is not staged.
         // (a.check_empty: launches that fill the chip, and small ones at labels_reduce > 1 -- eval_common) ----
-        if (a.check_empty && tw > 0) {
+        if (TW && a.check_empty && tw > 0) {
             bool mine = false;
             for (int sub = 0; sub < rows_per_wave; ++sub) {
                 const uint32_t trow = (uint32_t)sub * kWaves + wave;
@@ -1228,6 +1356,13 @@ __global__ __launch_bounds__(BLOCK, TW ? 8 : DEEP ? 4 : BLOCK == 512 ? 6 : BLOCK
                     a.labels[tw_i] = (uint16_t)best_c;
                 }
             }
+        }
+        // ---- the first wave to get here looks ahead for the workgroup ("the look-ahead wave", at the top of the next tile): one LDS
+        // add with return on this tile's election word; the other waves go to the barrier ----
+        if (!TW && more_tiles) {
+            uint32_t before = 0u;
+            if (lane == 0) before = atomicAdd(&s_tile[4u + (it & 1u)], 1u);
+            scout = __builtin_amdgcn_readfirstlane((int)before) == 0;
         }
     }
 
