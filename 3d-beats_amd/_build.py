@@ -10,7 +10,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "rdf_hip.hip")
 SOURCES = [SRC, os.path.join(HERE, "csrc", "mean_shift_hip.hip"), os.path.join(HERE, "csrc", "points_ops_hip.hip"),
            os.path.join(HERE, "csrc", "tree_train_hip.hip"), os.path.join(HERE, "csrc", "grouping_hip.hip")]
-HEADERS = [os.path.join(HERE, "..", "include", "rdf_hip.h"), os.path.join(HERE, "csrc", "rdf_device.hpp")]
+HEADERS = [os.path.join(HERE, "..", "include", "rdf_hip.h"), os.path.join(HERE, "csrc", "rdf_device.hpp"),
+           os.path.join(HERE, "csrc", "rdf_host_state.hpp")]
 SO = os.path.join(HERE, "csrc", "librdf_hip.so")
 
 

@@ -107,7 +107,7 @@ class DecisionForest:
 
     @staticmethod
     def _forget(buf):
-        """The library keeps what it knows about a packed table per (device, address): told before the memory goes away, so that
+        """The library keeps what it knows about a packed table per address: told before the memory goes away, so that
         another table that later lands on the same address is read afresh (rdf_forest_forget)."""
         try:
             from . import device
@@ -143,12 +143,18 @@ class DecisionForest:
         if table_bytes.size != nbytes:
             raise ValueError(f"adopt_packed: a packed table of {table_bytes.size} bytes; this forest's "
                              f"(T{self.num_trees}/D{self.max_depth}/C{self.num_classes}) is {nbytes}")
+        return self._receive_table(s, nbytes, lambda buf: buf.set(table_bytes), "adopt_packed")
+
+    def _receive_table(self, s, nbytes, fill, who):
+        """A packed table for scale `s` that arrives by other means than rdf_forest_pack: `fill(buf)` writes its `nbytes` into
+        the device buffer (an upload in `adopt_packed`, a broadcast in `distributed.replicate_forest`), then the library looks
+        at it (`_verify_table`) and it becomes this forest's table for `s`, its deep-level choice the one found inside."""
         hit = self._packed.get(s)
         buf = hit[1] if (hit is not None and hit[1].nbytes == nbytes) else DeviceArray((nbytes,), np.uint8)
         self._forget(buf)               # whatever the library knew about this address
-        self._packed.pop(s, None)       # (nothing half-adopted stays behind a failing check)
-        buf.set(table_bytes)
-        self._verify_table(buf, s, "adopt_packed")
+        self._packed.pop(s, None)       # (nothing half-received stays behind a failing check)
+        fill(buf)
+        self._verify_table(buf, s, who)
         self._packed[s] = ((id(self.forest_cu), self.forest_cu.version), buf)
         self.__dict__.setdefault("_tuned", {}).pop(s, None)
         return buf

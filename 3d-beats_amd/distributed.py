@@ -45,7 +45,7 @@ def replicate_forest(forest, src=0, group=None, packed_scales=()):
     if rank != src:
         _touch(forest.forest_cu)                    # (written outside the array API: the packed-table cache must notice)
     if packed_scales:
-        from .device import DeviceArray, get_runtime
+        from .device import get_runtime
         lib = get_runtime().lib
         nbytes = int(lib.rdf_forest_packed_bytes(int(forest.num_trees), int(forest.max_depth), int(forest.num_classes)))
         for s_ in packed_scales:
@@ -53,19 +53,12 @@ def replicate_forest(forest, src=0, group=None, packed_scales=()):
             if nbytes == 0:
                 continue
             if rank == src:
-                buf = forest.packed(s)
+                dist.broadcast(forest.packed(s).torch_bytes(), src=src, group=group)
             else:
-                hit = forest._packed.get(s)
-                buf = hit[1] if (hit is not None and hit[1].nbytes == nbytes) else DeviceArray((nbytes,), np.uint8)
-                forest._forget(buf)                 # whatever the library knew about this address
-                forest._packed.pop(s, None)
-            dist.broadcast(buf.torch_bytes(), src=src, group=group)
-            if rank != src:
-                # the library's first look at the received bytes, now (magic, shape, generation; the scale against `s`): a bad
-                # table raises ValueError here instead of evaluating with another scale later (DecisionForest._verify_table)
-                forest._verify_table(buf, s, f"replicate_forest (rank {rank})")
-                forest._packed[s] = ((id(forest.forest_cu), forest.forest_cu.version), buf)
-                forest.__dict__.setdefault("_tuned", {}).pop(s, None)
+                # the library's first look at the received bytes follows at once (magic, shape, generation; the scale against
+                # `s`): a bad table raises ValueError here instead of evaluating with another scale later
+                forest._receive_table(s, nbytes, lambda buf: dist.broadcast(buf.torch_bytes(), src=src, group=group),
+                                      f"replicate_forest (rank {rank})")
     return forest
 
 

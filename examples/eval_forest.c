@@ -55,7 +55,7 @@ int main(void)
     }
     /* The life of a packed table (include/rdf_hip.h, "Load-time repack"): allocate rdf_forest_packed_bytes(), pack once at model
      * load, evaluate from it as often as needed, and TELL the library before the memory goes away -- it remembers what it read
-     * from a table's info block per (device, address), and an allocation that later lands on the same address must not meet
+     * from a table's info block per address, and an allocation that later lands on the same address must not meet
      * that memory (a consumer that forgets is told: the call after such a launch returns RDF_ERR_STALE). */
     {
         void *d_packed = NULL;

@@ -53,8 +53,10 @@ extern "C" {
                                     compares the two on the device (no synchronous read).  That earlier call's labels are right
                                     unless the new table holds nodes that need the exact numerators and the call passed no `forest`
                                     (the kernel reads the scale from the table itself, never from the host's memory).  The library
-                                    has dropped everything it knew about this device's tables when it returns this code: call
-                                    again, and the info blocks are read afresh. */
+                                    has dropped everything it knew about packed tables when it returns this code -- every table's,
+                                    on whichever device: the flag does not say which table, and what the host keeps is only a
+                                    copy of each table's own info block (in a process with one device these are that device's
+                                    tables) -- call again, and the info blocks are read afresh. */
 
 /*
  * Forest evaluation.  Replaces `evaluate_image_using_forest`
@@ -185,7 +187,7 @@ int rdf_eval_forest_packed_stats(const uint16_t *depth, int n_img, int dim_x, in
  * heap-order records.  rdf_forest_set_deep_from makes the choice for one packed table (level > 0: deep blocks from that level
  * on, 0: never, -1: no choice) and WRITES IT INTO THE TABLE's info block (a synchronous 4-byte copy), so it stays with the
  * table: later evaluations, a copy of the table, another process that maps it all find it (the host keeps what it knows of a
- * table per device and address and reads the info block once); rdf_forest_pack into the same memory starts over.
+ * table per address and reads the info block once); rdf_forest_pack into the same memory starts over.
  * rdf_forest_info reports what a table's info block says -- the choice (-1: none made), how many nodes need the exact
  * numerators (> 0: evaluations need the caller's forest), the scale it was packed for -- reading the block back first if this
  * process has not seen the table at this address yet (synchronous then; RDF_ERR_BAD_ARG for memory that is not a table of
@@ -206,7 +208,10 @@ int rdf_eval_forest_packed_stats(const uint16_t *depth, int n_img, int dim_x, in
  *     [rdf_forest_tune(...) once]  rdf_eval_forest_packed(...) ...  rdf_forest_forget(packed);  hipFree(packed);
  * (examples/eval_forest.c).  rdf_forest_set_deep_from and rdf_forest_tune WRITE to the table (`packed` is const for the
  * evaluation calls only): a synchronous 4-byte copy, device-wide -- load-time calls, not to be made while another thread
- * captures a hipGraph in global mode.  All four calls find the table's device from the pointer, not from the current device.
+ * captures a hipGraph in global mode.  What the host keeps about a table is filed under the table's ADDRESS alone, for the
+ * whole process: device pointers are unique across a process's devices and an IPC-opened table has an address of its own, so
+ * evaluations, these four calls and rdf_forest_pack mean the same entry whichever device is current (a table evaluated from a
+ * peer device included), and rdf_forest_forget makes no HIP call at all -- a finalizer may call it from anywhere.
  */
 int rdf_forest_set_deep_from(const void *packed, int level);
 int rdf_forest_info(const void *packed, int n_trees, int max_depth, int n_classes, void *stream, int *deep_from,
@@ -547,8 +552,8 @@ int rdf_event_destroy(void *event);
 int rdf_stream_synchronize(void *stream);
 
 int rdf_abi_version(void);
-/* Identity of the build: 16 hex digits of a SHA-256 over the library's sources (the five .hip files, rdf_device.hpp, this
- * header) and its compiler flags, baked in at compile time (3d-beats_amd/_build.py).  The Python binding recomputes it from
+/* Identity of the build: 16 hex digits of a SHA-256 over the library's sources (the five .hip files, rdf_device.hpp,
+ * rdf_host_state.hpp, this header) and its compiler flags, baked in at compile time (3d-beats_amd/_build.py).  The Python binding recomputes it from
  * the sources next to the library and refuses a library built from other sources (an ABI number cannot tell yesterday's
  * kernels from today's).  "unknown" for a build that did not define it. */
 const char *rdf_build_id(void);

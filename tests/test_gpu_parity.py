@@ -1680,7 +1680,9 @@ def test_a_table_copied_over_a_known_address_without_forget_is_reported_stale(rd
     every launch the number the host remembers; the kernel compares them and raises the device's stale flag (pinned host
     memory: no synchronous read), the NEXT call returns RDF_ERR_STALE and the library has forgotten what it knew, the call
     after that reads the info block afresh.  The launch that met the foreign table already used the TABLE's scale (the kernel
-    reads it from the info block, not from the host's memory), so its labels are the new table's."""
+    reads it from the info block, not from the host's memory), so its labels are the new table's.
+    The flag does not say which table, so the library forgets EVERY table: a bystander table with a deep-level choice of its own
+    is read afresh too, and loses nothing by it -- the choice lives in its info block."""
     import ctypes
     lib, st = gpu_runtime.lib, gpu_runtime.stream()
     forest_np = rdf.synth.forest(3, 10, 4, "trained", 5)
@@ -1704,12 +1706,31 @@ def test_a_table_copied_over_a_known_address_without_forget_is_reported_stale(rd
 
     rc, got = call()
     assert rc == 0 and np.array_equal(got, want[1.0])
+    # the bystander: another forest's table, with a choice made for it, evaluated before anything goes wrong
+    by_np = rdf.synth.forest(3, 10, 4, "trained", 6)
+    by = rdf.DecisionForest.from_numpy(by_np)
+    by_want = np.full(depth_np.shape, 65535, np.uint16)
+    oracle.eval_forest(depth_np, by_np, by_want)
+    by_out = rdf.DeviceArray(depth_np.shape, np.uint16)
+
+    def bystander():
+        by_out.fill(65535)
+        rc = lib.rdf_eval_forest_packed(depth.ptr, 2, 160, 96, by.packed(1.0).ptr, by.forest_cu.ptr, 3, 10, 4, None, -1, by_out.ptr, 1, st)
+        level = ctypes.c_int(-2)
+        rc_info = lib.rdf_forest_info(by.packed(1.0).ptr, 3, 10, 4, st, ctypes.byref(level), None, None)
+        return rc, rc_info, level.value, by_out.get()
+
+    assert lib.rdf_forest_set_deep_from(by.packed(1.0).ptr, 8) == 0
+    rc, rc_info, level, got = bystander()
+    assert (rc, rc_info, level) == (0, 0, 8) and np.array_equal(got, by_want)
     other = rdf.DecisionForest.from_numpy(wild).packed_bytes(0.5)   # the same forest packed for another scale, elsewhere
     buf.set(other)                                                  # a raw copy over the known address; the library is not told
     rc, got = call()
     assert rc == 0 and np.array_equal(got, want[0.5])               # the table's own scale
     rc, _ = call()
     assert rc == -7 and b"rdf_forest_forget" in lib.rdf_error_string(-7)
+    rc, rc_info, level, got = bystander()                           # forgotten with the rest, read afresh: labels and choice as before
+    assert (rc, rc_info, level) == (0, 0, 8) and np.array_equal(got, by_want)
     rc, got = call()
     assert rc == 0 and np.array_equal(got, want[0.5])
     scale = ctypes.c_float(0)

@@ -45,11 +45,11 @@ def edit():
     t = sub1(t, "if (block != 256 && block != 512) block = (big && !filtered_r1) ? 512 : 256;",
              "if (block != 256 && block != 512 && block != 768 && block != 896 && block != 1024) block = (big && !filtered_r1) ? 512 : 256;\n"
              "    if (block > 512 && (!q.packed || q.filter_class != -1 || q.n_classes > 4 || q.stats)) block = 512;")
-    t = sub1(t, "        rc = p.g.block == 512 ? launch_block<512>(p.packed, p.compact_launch, a, p.lds_bytes, cus, st, split)\n",
-             "        rc = p.g.block == 768 ? launch_one<768, true, 4, false, 4, false>(a, p.lds_bytes, cus, st, split)\n"
-             "           : p.g.block == 896 ? launch_one<896, true, 4, false, 4, false>(a, p.lds_bytes, cus, st, split)\n"
-             "           : p.g.block == 1024 ? launch_one<1024, true, 4, false, 4, false>(a, p.lds_bytes, cus, st, split)\n"
-             "           : p.g.block == 512 ? launch_block<512>(p.packed, p.compact_launch, a, p.lds_bytes, cus, st, split)\n")
+    t = sub1(t, "        rc = p.g.block == 512 ? launch_block<512>(p.packed, p.compact_launch, a, p.lds_bytes, ds, cus, st, split)\n",
+             "        rc = p.g.block == 768 ? launch_one<768, true, 4, false, 4, false>(a, p.lds_bytes, ds, cus, st, split)\n"
+             "           : p.g.block == 896 ? launch_one<896, true, 4, false, 4, false>(a, p.lds_bytes, ds, cus, st, split)\n"
+             "           : p.g.block == 1024 ? launch_one<1024, true, 4, false, 4, false>(a, p.lds_bytes, ds, cus, st, split)\n"
+             "           : p.g.block == 512 ? launch_block<512>(p.packed, p.compact_launch, a, p.lds_bytes, ds, cus, st, split)\n")
     # (rows per wave for the big blocks: the knob; default 2)
     t = sub1(t, "        if (big && block == 512) {", "        if (big && block >= 512) {")
     # -- ablations
