@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """Records what the reference's own hand grouping (src/cpp_grouping/grouping.cpp, `CppGrouping::make_groups`) computes on a
-set of shrunk frames into tests/golden/grouping_v1.npz.  grouping.cpp is the one piece of the reference that runs on a CPU, so
+set of shrunk frames into tests/golden/grouping_v1.npz, and on the tile-crossing and limit-sized frames of tests/grouping_cases.py
+into tests/golden/grouping_v2.npz.  grouping.cpp is the one piece of the reference that runs on a CPU, so
 rdf_hand_groups' components, sizes, centroids and selection are pinned to the reference's code, not to a restatement.
 
 Runs in the build container only (it needs /root/reference, which never travels to the GPU box): grouping.cpp is compiled
 with g++ -O2 into a temporary directory together with this script's own three-line extern "C" driver; nothing of the
 reference is copied.  g_info is zero-filled before every call; for a side without a winner only the size (0) is recorded,
-since the reference leaves that side's centroid uninitialised.  The fixture holds data only.
+since the reference leaves that side's centroid uninitialised.  The fixtures hold data only.  grouping_v2.npz has the layout
+of grouping_v1.npz; a case named in grouping_cases.WITHOUT_COORDS keeps its g_info only (its breadth-first coordinate list
+would be most of the file): its `coords` has no rows and `<name>/has_coords` is False.
 
-    python3 tests/golden/make_grouping_golden.py        # rewrites tests/golden/grouping_v1.npz
+    python3 tests/golden/make_grouping_golden.py        # rewrites tests/golden/grouping_v1.npz and grouping_v2.npz
 """
 import ctypes
 import os
@@ -19,6 +22,8 @@ import tempfile
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+import grouping_cases  # noqa: E402
 REF = "/root/reference/src/cpp_grouping"
 
 DRIVER = r'''
@@ -159,6 +164,36 @@ def cases():
     return out
 
 
+def _record(lib, img, pct):
+    """(g_info float32 [2, 3], coords int32 [n1 + n2, 3]) of the reference's make_groups on one shrunk frame."""
+    hm, wm = img.shape
+    coords = np.zeros((max(hm * wm, 1), 3), np.int32)
+    g_info = np.zeros((2, 3), np.float32)
+    lib.drive(img.ctypes.data, wm, hm, coords.ctypes.data, g_info.ctypes.data, ctypes.c_float(pct))
+    n1, n2 = int(g_info[0, 0]), int(g_info[1, 0])
+    for side, n in ((0, n1), (1, n2)):
+        if n == 0:
+            g_info[side, 1:] = 0.0                         # uninitialised in the reference: not recorded
+    return g_info, coords[:n1 + n2].copy()
+
+
+def record_v2(lib):
+    data = {}
+    names = []
+    for name, img, pct in grouping_cases.cases():
+        g_info, coords = _record(lib, img, pct)
+        names.append(name)
+        data[f"{name}/img"] = img
+        data[f"{name}/pct"] = np.float32(pct)
+        data[f"{name}/g_info"] = g_info
+        if name in grouping_cases.WITHOUT_COORDS:
+            coords = coords[:0]
+            data[f"{name}/has_coords"] = np.bool_(False)
+        data[f"{name}/coords"] = coords
+    data["names"] = np.array(names)
+    return data
+
+
 def main():
     with tempfile.TemporaryDirectory() as tmp:
         lib = _build(tmp)
@@ -180,9 +215,13 @@ def main():
             data[f"{name}/g_info"] = g_info
             data[f"{name}/coords"] = coords[:n1 + n2].copy()
         data["names"] = np.array(names)
+        data_v2 = record_v2(lib)
     path = os.path.join(HERE, "grouping_v1.npz")
     np.savez_compressed(path, **data)
     print(f"{path}: {len(names)} cases, {os.path.getsize(path)} bytes")
+    path = os.path.join(HERE, "grouping_v2.npz")
+    np.savez_compressed(path, **data_v2)
+    print(f"{path}: {len(data_v2['names'])} cases, {os.path.getsize(path)} bytes")
 
 
 if __name__ == "__main__":

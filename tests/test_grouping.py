@@ -1,16 +1,20 @@
 """The hand-group image on the device (rdf_hand_groups, HandGrouping, CppGrouping, and the three stand-alone kernels of the
-reference's host round trip) against the reference's own grouping.cpp (tests/golden/grouping_v1.npz, recorded by
+reference's host round trip) against the reference's own grouping.cpp (tests/golden/grouping_v1.npz and, for the
+tile-crossing and limit-sized frames of tests/grouping_cases.py, grouping_v2.npz; both recorded by
 tests/golden/make_grouping_golden.py) and against the CPU restatement in tests/grouping_numpy.py."""
 import ctypes
+import functools
 import importlib
 import os
 
 import numpy as np
 import pytest
 
+import grouping_cases as gcases
 import grouping_numpy as gnp
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "grouping_v1.npz")
+GOLDEN_V2 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "grouping_v2.npz")
 NEW_SYMBOLS = ("rdf_shrink_image", "rdf_write_pixel_groups_to_stencil_image", "rdf_grow_groups",
                "rdf_hand_groups_workspace_bytes", "rdf_hand_groups")
 AUTO, RESIDENT, GLOBAL = 0, 1, 2
@@ -64,6 +68,117 @@ def test_grow_and_stencil_restatements_on_hand_derived_cases():
     assert np.array_equal(gnp.write_stencil(c, 2, (2, 2)), np.array([[0, 1], [2, 0]], np.uint16))
     assert np.array_equal(gnp.shrink(np.arange(30, dtype=np.uint16).reshape(5, 6), 1), np.array([[0, 2, 4], [12, 14, 16]]))
 
+@functools.lru_cache(maxsize=None)
+def _golden_v2():
+    """{name: (img, pct, g_info, coords or None)} of grouping_v2.npz, in the order of grouping_cases.cases()."""
+    z = np.load(GOLDEN_V2, allow_pickle=False)
+    out = {}
+    for n in z["names"]:
+        n = str(n)
+        has = bool(z[f"{n}/has_coords"]) if f"{n}/has_coords" in z.files else True
+        out[n] = (z[f"{n}/img"], float(z[f"{n}/pct"]), z[f"{n}/g_info"], z[f"{n}/coords"] if has else None)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _want_v2(name):
+    """The restatement's (groups, g_info, comps, coords rows) of one v2 case: computed once, shared, never written."""
+    img, pct, _, _ = _golden_v2()[name]
+    return gnp.hand_groups(img, 0, pct)
+
+
+def _flood(img):
+    """Components by a raster-order flood fill over the four neighbours, as grouping.cpp walks them (no scipy): int32
+    [Hm, Wm] of each foreground pixel's first-met pixel = its component's minimum raster index, -1 for background."""
+    hm, wm = img.shape
+    fg = (img != 0).reshape(-1).tolist()
+    out = [-1] * (hm * wm)
+    for s in range(hm * wm):
+        if not fg[s] or out[s] >= 0:
+            continue
+        out[s] = s
+        todo = [s]
+        while todo:
+            i = todo.pop()
+            y, x = divmod(i, wm)
+            for ok, j in ((x > 0, i - 1), (x + 1 < wm, i + 1), (y > 0, i - wm), (y + 1 < hm, i + wm)):
+                if ok and fg[j] and out[j] < 0:
+                    out[j] = s
+                    todo.append(j)
+    return np.array(out, np.int32).reshape(hm, wm)
+
+
+def test_v2_fixture_is_small_data_of_the_named_cases():
+    assert os.path.getsize(GOLDEN_V2) < 1_000_000
+    built = gcases.cases()
+    gold = _golden_v2()
+    assert list(gold) == [name for name, _, _ in built] and len(built) == 17
+    for name, img, pct in built:
+        g_img, g_pct, g_info, coords = gold[name]
+        assert img.dtype == np.uint16 and np.array_equal(img, g_img), name
+        assert np.float32(pct) == np.float32(g_pct), name
+        assert (coords is None) == (name in gcases.WITHOUT_COORDS), name
+    assert [n for n, (img, _, _, _) in gold.items() if not gcases.fits_resident(img)] == [
+        "checker_127x126", "row_16001x1", "comb_200x150", "comb_upside_down_200x150",
+        "large_sums_400x300", "large_sums_one_side_400x300"]
+
+
+def test_restatement_matches_the_v2_reference_fixture():
+    for name, (img, pct, g_info, coords) in _golden_v2().items():
+        _, gi, _, rows = _want_v2(name)
+        stencil = gnp.make_groups(img, pct)[1]
+        assert np.array_equal(gi.view(np.uint32), g_info.view(np.uint32)), name
+        assert int(gi[0, 0]) + int(gi[1, 0]) == len(rows), name
+        if coords is None:
+            continue
+        assert np.array_equal(stencil, gnp.write_stencil(coords, len(coords), img.shape)), name
+        assert np.array_equal(_rows(rows), _rows(coords)), name
+        assert len(coords) == len(rows), name
+
+
+# name: (components, size of the largest), from each case's construction
+V2_COMPONENTS = {
+    "serpentine_160x100": (1, 50 * 160 + 50), "two_serpentines_160x100": (2, 50 * 79 + 50),
+    "checker_160x100": (8000, 1), "checker_125x127": ((125 * 127 + 1) // 2, 1), "spiral_121": (1, 7439),
+    "staircase_130x120": (1, 240), "border_lines_100x90": (11, 400),
+    "corner_touch_100x90": (10, 1), "full_160x100": (1, 16000), "empty_160x100": (0, 0),
+    "checker_127x126": (8001, 1), "row_16001x1": (4572, 3), "column_1x4099": (1, 4099),
+    "comb_200x150": (1, 100 * 150 + 100), "comb_upside_down_200x150": (1, 15100),
+    "large_sums_400x300": (2, 200 * 300 - 2), "large_sums_one_side_400x300": (1, 400 * 300 - 2),
+}
+
+
+def test_the_hard_cases_are_what_they_claim():
+    gold = _golden_v2()
+    assert set(V2_COMPONENTS) == set(gold)
+    for name, (img, pct, g_info, _) in gold.items():
+        comps = _flood(img)
+        assert np.array_equal(comps, _want_v2(name)[2]), name              # the restatement's scipy labels agree
+        roots, sizes = np.unique(comps[comps >= 0], return_counts=True)
+        assert (len(roots), int(sizes.max()) if len(sizes) else 0) == V2_COMPONENTS[name], name
+        fg = np.nonzero(img.reshape(-1))[0]
+        if name.startswith("checker") or name == "corner_touch_100x90":    # every pixel is its own component
+            assert np.array_equal(comps.reshape(-1)[fg], fg), name
+        if name.split("_")[0] in ("serpentine", "spiral", "comb", "staircase", "column", "full"):
+            assert (comps.reshape(-1)[fg] == 0).all() and fg[0] == 0, name
+    sizes = {n: img.size for n, (img, _, _, _) in gold.items()}
+    assert sizes["serpentine_160x100"] == sizes["checker_160x100"] == gcases.RESIDENT_MAX_PIXELS == 16000
+    assert sizes["checker_127x126"] == 16002 and sizes["row_16001x1"] == 16001 and sizes["checker_125x127"] == 15875
+    # resident_lds_bytes of grouping_hip.hip: parent int32 [P] + {count, sum x, sum y} int32 [ceil(P / 2)]
+    lds = lambda p: 4 * p + 12 * ((p + 1) // 2)
+    assert lds(16000) == 160_000 and lds(16000) + 152 <= 160 * 1024 and lds(15875) == 4 * 15875 + 12 * 7938
+    # the ties: 4000 equal bidders per side in the 160x100 checkerboard, the smallest root of each side wins
+    gi = gold["checker_160x100"][2]
+    assert gi.tolist() == [[1, 0, 0], [1, 80, 0]]
+    two = _flood(gold["two_serpentines_160x100"][0])
+    assert set(np.unique(two).tolist()) == {-1, 0, 81}
+    # the corner pairs: ten one-pixel components, diagonal neighbours never joined
+    ys, xs = np.nonzero(gold["corner_touch_100x90"][0])
+    assert list(zip(ys.tolist(), xs.tolist())) == [(k + d, k + d) for k in (15, 31, 47, 63, 79) for d in (0, 1)]
+    # the row: runs 3, 1, 3, 1, ...: 2286 components of size 3, 2286 of size 1, all of them bid at pct = 0
+    row = _flood(gold["row_16001x1"][0])
+    assert np.unique(np.unique(row[row >= 0], return_counts=True)[1], return_counts=True)[1].tolist() == [2286, 2286]
+
 
 def test_library_exports_the_grouping_entry_points(rdf):
     _lib = importlib.import_module("3d-beats_amd._lib")
@@ -80,27 +195,37 @@ def test_library_exports_the_grouping_entry_points(rdf):
 
 
 # ------------------------------------------------------------------ GPU ------------------------------------------------------
-def _run(rdf, depth, level, pct, path, coords=True):
-    """depth uint16 [n, H, W] -> (groups, g_info, comps, coords) from rdf_hand_groups through the C ABI."""
+def _launch(rdf, depth, level, pct, path, coords=True, workspace=True):
+    """depth uint16 [n, H, W] -> (return code, (groups, g_info, comps, coords)) from rdf_hand_groups through the C ABI.
+    Every output starts from a sentinel fill (7, NaN, -5, -9; 0xAB in the workspace); a shape that shrinks to no pixels
+    gets one-element outputs."""
     lib = rdf.get_runtime().lib
-    _lib = importlib.import_module("3d-beats_amd._lib")
     n, h, w = depth.shape
     hm, wm = h >> level, w >> level
+    p1 = max(hm * wm, 1)
     d = rdf.to_device(depth)
-    g = rdf.DeviceArray((n, hm, wm), np.uint16).fill(7)
+    g = rdf.DeviceArray((n, hm, wm) if hm * wm else (n, 1), np.uint16).fill(7)
     gi = rdf.DeviceArray((n, 2, 3), np.float32).fill(np.float32(np.nan))
-    comps = rdf.DeviceArray((n, hm, wm), np.int32).fill(-5)
-    co = rdf.DeviceArray((n, max(hm * wm, 1), 3), np.int32).fill(-9) if coords else None
+    comps = rdf.DeviceArray((n, hm, wm) if hm * wm else (n, 1), np.int32).fill(-5)
+    co = rdf.DeviceArray((n, p1, 3), np.int32).fill(-9) if coords else None
     ws = rdf.DeviceArray((max(int(lib.rdf_hand_groups_workspace_bytes(n, w, h, level)), 8),), np.uint8).fill(0xAB)
-    rc = lib.rdf_hand_groups(d.ptr, n, w, h, level, float(pct), g.ptr, gi.ptr, comps.ptr, co.ptr if coords else None, ws.ptr,
-                             path, rdf.get_runtime().stream())
-    _lib.check(lib, rc, "rdf_hand_groups")
-    return g.get(), gi.get(), comps.get(), (co.get() if coords else None)
+    rc = lib.rdf_hand_groups(d.ptr, n, w, h, level, float(pct), g.ptr, gi.ptr, comps.ptr, co.ptr if coords else None,
+                             ws.ptr if workspace else None, path, rdf.get_runtime().stream())
+    rdf.get_runtime().synchronize()
+    return rc, (g.get(), gi.get(), comps.get(), (co.get() if coords else None))
 
 
-def _check_frame(got, i, depth, level, pct, ref_ginfo=None, ref_coords=None):
+def _run(rdf, depth, level, pct, path, coords=True):
+    """depth uint16 [n, H, W] -> (groups, g_info, comps, coords) from rdf_hand_groups through the C ABI."""
+    _lib = importlib.import_module("3d-beats_amd._lib")
+    rc, got = _launch(rdf, depth, level, pct, path, coords)
+    _lib.check(rdf.get_runtime().lib, rc, "rdf_hand_groups")
+    return got
+
+
+def _check_frame(got, i, depth, level, pct, ref_ginfo=None, ref_coords=None, want=None):
     groups, g_info, comps, coords = got
-    want_g, want_gi, want_c, want_rows = gnp.hand_groups(depth, level, pct)
+    want_g, want_gi, want_c, want_rows = want if want is not None else gnp.hand_groups(depth, level, pct)
     assert np.array_equal(groups[i], want_g)
     assert np.array_equal(g_info[i].view(np.uint32), want_gi.view(np.uint32)), (g_info[i], want_gi)
     assert np.array_equal(comps[i], want_c)
@@ -109,6 +234,7 @@ def _check_frame(got, i, depth, level, pct, ref_ginfo=None, ref_coords=None):
     assert (coords[i][n:] == -9).all()                          # rows past the two groups are untouched
     if ref_ginfo is not None:
         assert np.array_equal(g_info[i].view(np.uint32), ref_ginfo.view(np.uint32))
+    if ref_coords is not None:
         assert np.array_equal(_rows(coords[i][:n]), _rows(ref_coords))
 
 
@@ -326,3 +452,138 @@ def test_make_group_image_replays_from_a_captured_graph(level, rdf, gpu_runtime)
         want_g, want_gi, _, _ = gnp.hand_groups(frame, level, 0.06)
         assert np.array_equal(got[0], want_g) and np.array_equal(got[1][0].view(np.uint32), want_gi.view(np.uint32))
     del graph
+
+
+# ------------------------------------ tile-crossing shapes and the resident limit ---------------------------------------------
+def _paths_for(img):
+    return (RESIDENT, GLOBAL) if gcases.fits_resident(img) else (GLOBAL,)
+
+
+def _same_bits(a, b):
+    for u, v in zip(a, b):
+        assert u.dtype == v.dtype and u.shape == v.shape
+        assert np.array_equal(u.view(np.uint8), v.view(np.uint8))   # NaN sentinels compare as bytes
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", gcases.NAMES)
+def test_tile_crossing_shapes_match_the_reference_on_both_paths(name, rdf, gpu_runtime):
+    img, pct, g_info, coords = _golden_v2()[name]
+    first = None
+    for path in _paths_for(img):
+        got = _run(rdf, img[None], 0, pct, path)
+        _check_frame(got, 0, img, 0, pct, g_info, coords, want=_want_v2(name))
+        _same_bits(got, _run(rdf, img[None], 0, pct, path))        # the order lanes and workgroups ran in does not show
+        if first is not None:
+            _same_bits(first, got)                                  # resident == global
+        first = got
+
+
+@pytest.mark.gpu
+def test_resident_limit(rdf, gpu_runtime):
+    BAD, NULL = -1, -2
+    gold = _golden_v2()
+    for name in ("serpentine_160x100", "checker_160x100"):         # P = 16000: 160 000 B of dynamic LDS
+        img, pct, g_info, coords = gold[name]
+        rc_res, res = _launch(rdf, img[None], 0, pct, RESIDENT)
+        rc_auto, auto = _launch(rdf, img[None], 0, pct, AUTO, workspace=False)   # resident: no workspace needed
+        assert (rc_res, rc_auto) == (0, 0)
+        _same_bits(res, auto)
+        _check_frame(res, 0, img, 0, pct, g_info, coords, want=_want_v2(name))
+    for name in ("checker_127x126", "row_16001x1"):                # the first frames past it
+        img, pct, g_info, coords = gold[name]
+        rc_glb, glb = _launch(rdf, img[None], 0, pct, GLOBAL)
+        rc_auto, auto = _launch(rdf, img[None], 0, pct, AUTO)
+        assert (rc_glb, rc_auto) == (0, 0)
+        _same_bits(glb, auto)
+        _check_frame(auto, 0, img, 0, pct, g_info, coords, want=_want_v2(name))
+        rc, untouched = _launch(rdf, img[None], 0, pct, RESIDENT)
+        assert rc == BAD
+        rc2, untouched2 = _launch(rdf, img[None], 0, pct, AUTO, workspace=False)
+        assert rc2 == NULL
+        for out in (untouched, untouched2):                         # a refused call writes nothing
+            assert (out[0] == 7).all() and np.isnan(out[1]).all() and (out[2] == -5).all() and (out[3] == -9).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", [RESIDENT, GLOBAL])
+def test_a_batch_of_hard_frames(path, rdf, gpu_runtime):
+    names = ["serpentine_160x100", "checker_160x100", "full_160x100", "empty_160x100", "two_serpentines_160x100"]
+    gold = _golden_v2()
+    depth = np.stack([gold[n][0] for n in names])
+    pct = -1.0                                                      # the checkerboard's; the others keep every component
+    got = _run(rdf, depth, 0, pct, path)
+    for i, n in enumerate(names):
+        img, own_pct, g_info, coords = gold[n]
+        comps = _want_v2(n)[2]
+        sizes = np.unique(comps[comps >= 0], return_counts=True)[1]
+        assert (sizes.astype(np.float32) / np.float32(16000) > np.float32(own_pct)).all()   # so the fixture holds at -1 too
+        _check_frame(got, i, img, 0, pct, g_info, coords)
+    e = names.index("empty_160x100")
+    assert not got[0][e].any() and not got[1][e].view(np.uint32).any()
+    assert (got[2][e] == -1).all() and (got[3][e] == -9).all()
+    _same_bits(got, _run(rdf, depth, 0, pct, path))
+
+
+def _embed(pattern, level):
+    """The largest depth frame that still shrinks to `pattern` at `level`: pixel (y << level, x << level) carries the
+    pattern, every other pixel is its block's opposite (nonzero where the pattern is 0, 0 where it is not); the rows and
+    columns past the last block take the opposite of the last block."""
+    hm, wm = pattern.shape
+    f = 1 << level
+    h, w = (hm << level) + f - 1, (wm << level) + f - 1
+    ys, xs = np.minimum(np.arange(h) >> level, hm - 1), np.minimum(np.arange(w) >> level, wm - 1)
+    depth = np.where(pattern[np.ix_(ys, xs)] != 0, 0, 1234).astype(np.uint16)
+    depth[:hm * f:f, :wm * f:f] = pattern
+    return depth
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("level", [1, 3])
+@pytest.mark.parametrize("name", ["two_serpentines_160x100", "border_lines_100x90"])
+def test_fused_shrink_samples_only_its_own_pixels(name, level, rdf, gpu_runtime):
+    img, pct, g_info, coords = _golden_v2()[name]
+    depth = _embed(img, level)
+    assert depth.shape == ((img.shape[0] << level) + (1 << level) - 1, (img.shape[1] << level) + (1 << level) - 1)
+    assert np.array_equal(gnp.shrink(depth, level), img)
+    f = 1 << level
+    hm, wm = img.shape
+    block = np.kron(img != 0, np.ones((f, f), bool))               # each pixel's block's pattern
+    sampled = np.zeros(block.shape, bool)
+    sampled[::f, ::f] = True
+    assert ((depth[:hm * f, :wm * f] != 0) != block)[~sampled].all()   # every pixel the shrink skips is the opposite
+    assert (depth[hm * f:] != 0).any() and (depth[:, wm * f:] != 0).any()
+    want = _want_v2(name)                                           # the level-0 result of the bare pattern
+    first = None
+    for path in _paths_for(img):
+        got = _run(rdf, depth[None], level, pct, path)
+        _check_frame(got, 0, depth, level, pct, g_info, coords, want=want)
+        if first is not None:
+            _same_bits(first, got)
+        first = got
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", [AUTO, RESIDENT, GLOBAL])
+def test_a_level_that_leaves_no_pixels(path, rdf, gpu_runtime):
+    depth = np.full((2, 8, 8), 500, np.uint16)                     # level 4: Hm = Wm = 0
+    rc, (groups, g_info, comps, coords) = _launch(rdf, depth, 4, 0.06, path)
+    assert rc == 0
+    assert g_info.shape == (2, 2, 3) and not g_info.view(np.uint32).any()
+    assert (groups == 7).all() and (comps == -5).all() and (coords == -9).all()   # the one-element stand-ins: untouched
+
+
+@pytest.mark.gpu
+def test_cpp_grouping_drop_in_on_the_hard_shapes(rdf, gpu_runtime):
+    cg = importlib.import_module("3d-beats_amd.cpp_grouping").CppGrouping()
+    gold = _golden_v2()
+    for name in ("checker_160x100", "comb_200x150", "row_16001x1"):   # one object: resident, then larger buffers, then global
+        img, pct, ref_gi, ref_coords = gold[name]
+        coords = np.full((img.size, 3), -9, np.int32)
+        g_info = np.full((2, 3), np.nan, np.float32)
+        cg.make_groups(img, coords, g_info, pct)
+        assert np.array_equal(g_info.view(np.uint32), ref_gi.view(np.uint32)), name
+        rows = _want_v2(name)[3]
+        assert len(rows) == len(ref_coords) and np.array_equal(coords[:len(rows)], rows), name
+        assert (coords[len(rows):] == -9).all(), name
+        assert np.array_equal(_rows(coords[:len(rows)]), _rows(ref_coords)), name
