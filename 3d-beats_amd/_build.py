@@ -26,8 +26,9 @@ class Library(NamedTuple):
 # Each library has its own sources and build id, so adding one leaves the others' binaries as they were.
 LIBRARIES = {lib.key: lib for lib in (
     Library("hip", SO, SOURCES, HEADERS, "rdf_"),
-    # the depth front end
-    Library("frontend", os.path.join(HERE, "csrc", "librdf_frontend.so"), [os.path.join(HERE, "csrc", "frontend_hip.hip")],
+    # the depth front end, and the note state machine behind the fingertip heights
+    Library("frontend", os.path.join(HERE, "csrc", "librdf_frontend.so"),
+            [os.path.join(HERE, "csrc", "frontend_hip.hip"), os.path.join(HERE, "csrc", "hand_state_hip.hip")],
             [os.path.join(HERE, "..", "include", "rdf_frontend.h")], "rdf_frontend_"),
     # glove-colour recordings to training labels, and the re-render that augments them
     Library("labels", os.path.join(HERE, "csrc", "librdf_labels.so"),

@@ -134,7 +134,7 @@ ABI_VERSION = 5
 # symbol its header declares)
 BINDINGS = {
     "hip": (ABI_VERSION, SIGNATURES),
-    "frontend": (1, {
+    "frontend": (2, {
         "rdf_make_plane_candidates": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                                _c_void_p]),
         "rdf_plane_inliers": (_c_int, [_c_int, _c_float, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
@@ -149,6 +149,11 @@ BINDINGS = {
         "rdf_filter_points_by_plane": (_c_int, [_c_int, _c_float, _c_void_p, _c_void_p]),
         "rdf_remove_missing_3d_points_from_depth_image": (_c_int, [_c_int, _c_void_p, _c_void_p, _c_void_p]),
         "rdf_gaussian_depth_filter": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+        "rdf_hand_state_bytes": (_c_size_t, [_c_int, _c_int]),
+        "rdf_hand_state_init": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
+        "rdf_hand_state_set": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p]),
+        "rdf_hand_state_step": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, ctypes.c_uint32,
+                                         _c_void_p]),
         "rdf_frontend_abi_version": (_c_int, []),
         "rdf_frontend_build_id": (ctypes.c_char_p, []),
         "rdf_frontend_error_string": (ctypes.c_char_p, [_c_int]),

@@ -463,6 +463,7 @@ const char *rdf_frontend_error_string(int code)
     case RDF_OK: return "ok";
     case RDF_ERR_BAD_ARG: return "rdf_frontend: bad argument";
     case RDF_ERR_NULL_PTR: return "rdf_frontend: required pointer is NULL";
+    case RDF_ERR_CAPTURE: return "rdf_frontend: the stream is being captured into a graph and this call cannot be recorded";
     case RDF_ERR_TOO_LARGE: return "rdf_frontend: call addresses >= 2^31 elements (or too many candidates / frames for one grid)";
     default: return code > 0 ? hipGetErrorString(static_cast<hipError_t>(code)) : "rdf_frontend: unknown error";
     }

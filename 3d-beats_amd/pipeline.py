@@ -62,9 +62,13 @@ def _release_deferred():
 
 class HandPipeline:
     def __init__(self, layered_rdf, depth_dims, labels_reduce, eval_to_train_dim_ratio, mean_shift_rounds,
-                 mean_shift_variances, fingertip_idxes, intrinsics, plane, depth_mm_level=0, fused_io=True):
+                 mean_shift_variances, fingertip_idxes, intrinsics, plane, depth_mm_level=0, fused_io=True,
+                 hand_state=None, tip_first=0):
         """depth_dims = (DIM_Y, DIM_X); intrinsics = (fx, fy, ppx, ppy) of the depth stream; plane = the calibrated
-        plane's 4x4 matrix (calibrated_plane.plane); fingertip_idxes = 1-based composite label ids (3d_bz.py:112)."""
+        plane's 4x4 matrix (calibrated_plane.plane) or a float32 device array of 16 elements that is read every frame
+        (FrameFrontEnd.calibrated_plane.plane_cu: a recalibration then reaches the heights); fingertip_idxes = 1-based
+        composite label ids (3d_bz.py:112); hand_state = a HandState whose fingertips tip_first .. tip_first + n - 1 every
+        frame advances, on the device, from the heights where the chain wrote them (3d_bz.py:496-522 without the read)."""
         self._rt = get_runtime()
         self._lib = self._rt.lib
         # run() writes the stack's per-layer label buffers: a stack that already serves another pipeline is replaced by a
@@ -98,7 +102,14 @@ class HandPipeline:
         self.mean_shift_variances = DeviceArray((len(mean_shift_variances),), np.float32).set(
             np.asarray(mean_shift_variances, dtype=np.float32))
         self._ids = DeviceArray((len(self.fingertip_idxes),), np.int32).set(np.asarray(self.fingertip_idxes, np.int32))
-        self._plane = DeviceArray((4, 4), np.float32).set(np.ascontiguousarray(plane, dtype=np.float32))
+        if isinstance(plane, DeviceArray) or hasattr(plane, "cu"):
+            self._plane = plane.cu() if hasattr(plane, "cu") else plane
+            assert np.dtype(self._plane.dtype) == np.float32 and int(np.prod(self._plane.shape)) == 16, self._plane.shape
+        else:
+            self._plane = DeviceArray((4, 4), np.float32).set(np.ascontiguousarray(plane, dtype=np.float32))
+        self.hand_state, self.tip_first = hand_state, int(tip_first)
+        if hand_state is not None:
+            assert 0 <= self.tip_first and self.tip_first + len(self.fingertip_idxes) <= hand_state.n_tips
         # means [L,2] followed by heights [n_fingertips]: one device->host copy per frame
         self._L = int(layered_rdf.num_layered_classes)
         self._result = DeviceArray((self._L * 2 + len(self.fingertip_idxes),), np.float64)
@@ -109,14 +120,26 @@ class HandPipeline:
         if self.fused_io and alloc is not None and len(self.fingertip_idxes) <= 1024:
             self._host = alloc(self._result.nbytes)
 
-    def run(self, depth_image, depth_image_mm_groups, g_id, flip_x):
+    def run(self, depth_image, depth_image_mm_groups, g_id, flip_x, height_depth=None):
         """depth_image: GpuBuffer uint16 [DIM_Y, DIM_X] (the frame, 0 = no reading);
         depth_image_mm_groups: GpuBuffer of the hand-group image at mip level depth_mm_level;
+        height_depth: the frame a fingertip's depth is looked up in, when it is not depth_image -- the reference looks it up
+        in the raw camera frame (3d_bz.py:517), not in the table-free, filtered frame that the stencil reads;
         returns (label_means float64 [L, 2], fingertip heights float64 [n], NaN = "reset" in the reference)."""
-        self._enqueue(depth_image, depth_image_mm_groups, g_id, flip_x)
+        self.enqueue(depth_image, depth_image_mm_groups, g_id, flip_x, height_depth)
         return self._read()
 
-    def capture(self, depth_image, depth_image_mm_groups, g_id, flip_x):
+    def enqueue(self, depth_image, depth_image_mm_groups, g_id, flip_x, height_depth=None):
+        """run() without the read: the frame, and the hand_state's step when there is one, on the current stream."""
+        self._enqueue(depth_image, depth_image_mm_groups, g_id, flip_x, height_depth)
+
+    @property
+    def heights_ptr(self):
+        """Where a frame's fingertip heights (float64 [n]) land: mapped pinned host memory with fused_io, else device memory."""
+        at = self._L * 2 * 8
+        return self._host[1] + at if self._host is not None else self._result.ptr + at
+
+    def capture(self, depth_image, depth_image_mm_groups, g_id, flip_x, height_depth=None):
         """Records the chain for these buffers and arguments into a hipGraph (through torch) and returns a
         function that replays it on the buffers' current contents and returns what run() returns: one graph
         launch per hand per frame instead of ~16 kernel launches.  replay(read=False) only enqueues (replay.read()
@@ -128,13 +151,14 @@ class HandPipeline:
         import torch
         side = torch.cuda.Stream()
         with torch.cuda.stream(side):      # warm-up on the capture stream: workspaces, occupancy queries, queue slot
-            self._enqueue(depth_image, depth_image_mm_groups, g_id, flip_x)
+            # (without the hand_state's step, which needs none: the capture itself must not advance the notes by a frame)
+            self._enqueue(depth_image, depth_image_mm_groups, g_id, flip_x, height_depth, step_state=False)
         side.synchronize()
         graph = torch.cuda.CUDAGraph()
         cap_id = ctypes.c_uint64(0)
         with torch.cuda.graph(graph, stream=side):
             named = self._lib.rdf_stream_capture_id(self._rt.stream(), ctypes.byref(cap_id)) == 0
-            self._enqueue(depth_image, depth_image_mm_groups, g_id, flip_x)
+            self._enqueue(depth_image, depth_image_mm_groups, g_id, flip_x, height_depth)
 
         read_fn = self._read
         done = torch.cuda.Event()       # re-recorded behind every replay, on the stream the replay was launched on
@@ -173,7 +197,15 @@ class HandPipeline:
             out = self._result.get()
         return out[:self._L * 2].reshape(self._L, 2), out[self._L * 2:]
 
-    def _enqueue(self, depth_image, depth_image_mm_groups, g_id, flip_x):
+    def _enqueue(self, depth_image, depth_image_mm_groups, g_id, flip_x, height_depth=None, step_state=True):
+        self._chain(depth_image, depth_image_mm_groups, g_id, flip_x, depth_image if height_depth is None else height_depth)
+        if self.hand_state is not None:
+            if step_state:
+                self.hand_state.step_device(self.heights_ptr, self.tip_first, len(self.fingertip_idxes))
+            else:
+                self.hand_state.state_ptr        # (its device side exists before a capture starts)
+
+    def _chain(self, depth_image, depth_image_mm_groups, g_id, flip_x, height_depth):
         dims = np.array([self.DIM_X, self.DIM_Y], dtype=np.int32)
         ldims = np.array([self.LABELS_DIM_X, self.LABELS_DIM_Y], dtype=np.int32)
         po = self.points_ops
@@ -207,7 +239,7 @@ class HandPipeline:
             base = self._host[1]
             self.mean_shift.run_device_with_heights(
                 self.mean_shift_rounds, self.labels_image.cu().reshape((1, self.LABELS_DIM_Y, self.LABELS_DIM_X)), self._L,
-                self.mean_shift_variances, self._ids, len(self.fingertip_idxes), depth_image.cu(), self.LABELS_REDUCE,
+                self.mean_shift_variances, self._ids, len(self.fingertip_idxes), height_depth.cu(), self.LABELS_REDUCE,
                 self.intrinsics, self._plane, base, base + self._L * 2 * 8)
             return
         means = self.mean_shift.run_device(self.mean_shift_rounds,
@@ -217,7 +249,7 @@ class HandPipeline:
         heights = self._result[self._L * 2:]
         # z is looked up in the ORIGINAL depth frame (3d_bz.py:515), not the stencilled / flipped one
         rc = self._lib.rdf_fingertip_heights(means.ptr, self._L, self._ids.ptr, len(self.fingertip_idxes),
-                                             device_ptr(depth_image.cu()), self.DIM_X, self.DIM_Y, self.LABELS_REDUCE,
+                                             device_ptr(height_depth.cu()), self.DIM_X, self.DIM_Y, self.LABELS_REDUCE,
                                              fx, fy, ppx, ppy, self._plane.ptr, heights.ptr, self._rt.stream())
         _lib.check(self._lib, rc, "rdf_fingertip_heights")
         self._result.mark_dirty()

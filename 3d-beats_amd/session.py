@@ -1,0 +1,131 @@
+"""A whole frame of the reference's app, from the camera's depth frame to note events: `App_3d_bz.tick` and
+`run_per_hand_pipeline` (src/3d_bz.py:133-286, 388-522 of the reference) without camera, GUI or MIDI.
+
+`BeatsSession` owns a `FrameFrontEnd` (raw depth -> table-free depth), a `HandGrouping` (-> the hand-group image), two
+`HandPipeline`s (right hand: group 1, unflipped; left hand: group 2, flipped; the second on a sibling of the forest stack)
+and ONE `HandState` of ten fingertips (right 0-4, left 5-9).  Everything runs on the current stream; a frame is enqueued by
+`tick()` and nothing is read until `poll()`.  The fingertip heights are looked up in the raw camera frame, as the reference
+does (3d_bz.py:517), and the heights read the front end's plane on the device, so a recalibration reaches them.
+"""
+import numpy as np
+
+from . import _lib
+from .device import DeviceArray, get_runtime
+from .frontend import FrameFrontEnd
+from .grouping import HandGrouping
+from .hand_state import MAX_VELOCITY, MIN_VELOCITY, VELOCITY_SENSITIVE, HandState
+from .pipeline import HandPipeline
+
+TRAIN_DIM_X = 848
+
+
+class _Frame:
+    """One frame of a batch buffer behind the `.cu()` that HandPipeline asks of its images."""
+
+    def __init__(self, array):
+        self._cu, self.shape, self.dtype = array, array.shape, array.dtype
+
+    def cu(self):
+        return self._cu
+
+
+class BeatsSession:
+    def __init__(self, layered_rdf, depth_dims, intrinsics, on_fn=None, off_fn=None, labels_reduce=2, depth_mm_level=3,
+                 group_min_size=0.06, plane_z_threshold=40., gauss_sigma=2.0, mean_shift_rounds=6,
+                 mean_shift_variances=(50., 8., 8., 8., 8., 8., 8.), fingertip_idxes=(2, 3, 4, 5, 6), z_thresh_offset=25.,
+                 min_velocity=10., max_velocity=120., velocity_sensitive=True, scale_factor=None,
+                 fingertip_thresholds=(200., 160., 160., 160., 160.), first_notes=(36, 41), max_frames=8,
+                 num_random_guesses=25000, seed=None, fused_io=True, capacity=4096):
+        """layered_rdf: a LayeredDecisionForest built for depth_dims = (DIM_Y, DIM_X) and labels_reduce; intrinsics = (focal,
+        ppx, ppy) of the depth camera.  The other defaults are the app's (3d_bz.py:49-124); scale_factor = DIM_X / 848 when
+        None.  max_frames = the batch of run_sequence's front end and grouping."""
+        self._rt = get_runtime()
+        self.DIM_Y, self.DIM_X = int(depth_dims[0]), int(depth_dims[1])
+        self.max_frames = int(max_frames)
+        focal, ppx, ppy = (float(v) for v in intrinsics)
+        scale = self.DIM_X / TRAIN_DIM_X if scale_factor is None else float(scale_factor)
+        n = len(fingertip_idxes)
+        assert len(fingertip_thresholds) == n
+        self.front_end = FrameFrontEnd((self.DIM_Y, self.DIM_X), (focal, ppx, ppy), plane_z_threshold, gauss_sigma=gauss_sigma,
+                                       num_random_guesses=num_random_guesses, seed=seed)
+        self.grouping = HandGrouping((self.DIM_Y, self.DIM_X), depth_mm_level, group_min_size, max_frames=self.max_frames)
+        defaults = [(fingertip_thresholds[i], first + i) for first in first_notes for i in range(n)]
+        self.hand_state = HandState(defaults, on_fn, off_fn, capacity=capacity)
+        self.hand_state.set_field(MIN_VELOCITY, [min_velocity] * (2 * n))
+        self.hand_state.set_field(MAX_VELOCITY, [max_velocity] * (2 * n))
+        self.hand_state.set_field(VELOCITY_SENSITIVE, [1. if velocity_sensitive else 0.] * (2 * n))
+        self.hand_state.z_thresh_offset = z_thresh_offset
+        args = ((self.DIM_Y, self.DIM_X), labels_reduce, scale, mean_shift_rounds, list(mean_shift_variances),
+                list(fingertip_idxes), (focal, focal, ppx, ppy), self.front_end.calibrated_plane.plane_cu)
+        self.right = HandPipeline(layered_rdf, *args, depth_mm_level=depth_mm_level, fused_io=fused_io,
+                                  hand_state=self.hand_state, tip_first=0)
+        self.left = HandPipeline(layered_rdf, *args, depth_mm_level=depth_mm_level, fused_io=fused_io,
+                                 hand_state=self.hand_state, tip_first=n)
+        self.n_tips = 2 * n
+        hm, wm = self.grouping.depth_mm_dims
+        self._raw = DeviceArray((self.max_frames, self.DIM_Y, self.DIM_X), np.uint16)
+        self._clean = DeviceArray((self.max_frames, self.DIM_Y, self.DIM_X), np.uint16)
+        self._groups = DeviceArray((self.max_frames, hm, wm), np.uint16)
+        self._clean_f = [_Frame(self._clean[i]) for i in range(self.max_frames)]
+        self._groups_f = [_Frame(self._groups[i]) for i in range(self.max_frames)]
+
+    # -- the plane --
+    def calibrate(self, depth):
+        """Fit the table plane to a frame (host or device uint16 [DIM_Y, DIM_X]); returns the 4x4 plane."""
+        return self.front_end.calibrate(self._on_device(depth, 1)[0])
+
+    def set_plane(self, plane):
+        self.front_end.set_plane(plane)
+
+    def _on_device(self, frames, n):
+        """uint16 [n, DIM_Y, DIM_X] on the device: the frames themselves, or their copy in this session's raw buffer."""
+        if hasattr(frames, "cu"):
+            frames = frames.cu()
+        if isinstance(frames, DeviceArray):
+            return frames.reshape((n, self.DIM_Y, self.DIM_X))
+        self._raw[:n].set(np.ascontiguousarray(frames, np.uint16).reshape(n, self.DIM_Y, self.DIM_X))
+        return self._raw[:n]
+
+    # -- live --
+    def tick(self, depth):
+        """Enqueues one whole frame (uint16 [DIM_Y, DIM_X]) on the current stream and returns nothing: front end, grouping,
+        both hands, the note step.  A device frame is only enqueued and the stream is never waited for; a host frame is
+        copied to the device first."""
+        raw = self._on_device(depth, 1)
+        self.front_end.run(raw, self._clean[:1])
+        self.grouping.make_group_image(self._clean[:1], self._groups[:1])
+        raw = _Frame(raw[0])
+        # the right hand's launch precedes the left's: events of a frame come out right hand first
+        self.right.enqueue(self._clean_f[0], self._groups_f[0], 1, False, height_depth=raw)
+        self.left.enqueue(self._clean_f[0], self._groups_f[0], 2, True, height_depth=raw)
+
+    def poll(self):
+        """HandState.poll(): waits for the stream and delivers the events since the last poll."""
+        return self.hand_state.poll()
+
+    # -- offline --
+    def run_sequence(self, frames):
+        """frames: uint16 [F, DIM_Y, DIM_X] on the host or the device.  The front end and the grouping run in batches of
+        max_frames; the per-hand chains run frame by frame (batching the layered forest and the mean shift over frames is
+        out of scope here); one synchronisation, at the end.  Returns (events, heights float64 [F, 10]).  The heights log
+        is written on the device: each hand's heights are copied into the frame's row behind its chain (a stream-ordered
+        copy of 40 bytes), and the log is read once, after the last frame."""
+        F = int(frames.shape[0])
+        n = self.n_tips // 2
+        log = DeviceArray((max(F, 1), self.n_tips), np.float64)
+        lib, stream = self._rt.lib, self._rt.stream
+        for a in range(0, F, self.max_frames):
+            b = min(F - a, self.max_frames)
+            raw = self._on_device(frames[a:a + b], b)
+            self.front_end.run(raw, self._clean[:b])
+            self.grouping.make_group_image(self._clean[:b], self._groups[:b])
+            for i in range(b):
+                raw_i = _Frame(raw[i])
+                for pipe in (self.right, self.left):
+                    g_id, flip = (1, False) if pipe is self.right else (2, True)
+                    pipe.enqueue(self._clean_f[i], self._groups_f[i], g_id, flip, height_depth=raw_i)
+                    rc = lib.rdf_memcpy_device_async(log.ptr + ((a + i) * self.n_tips + pipe.tip_first) * 8, pipe.heights_ptr,
+                                                     n * 8, stream())
+                    _lib.check(lib, rc, "rdf_memcpy_device_async")
+        events = self.poll()
+        return events, log.get()[:F]

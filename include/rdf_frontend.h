@@ -30,13 +30,14 @@
 extern "C" {
 #endif
 
-/* 1: first version. */
-#define RDF_FRONTEND_ABI_VERSION 1
+/* 1: first version.  2: rdf_hand_state_* (the note state machine behind the fingertip heights), RDF_ERR_CAPTURE. */
+#define RDF_FRONTEND_ABI_VERSION 2
 
 #define RDF_OK 0
 #define RDF_ERR_BAD_ARG (-1)
 #define RDF_ERR_NULL_PTR (-2)
 #define RDF_ERR_TOO_LARGE (-3)
+#define RDF_ERR_CAPTURE (-6)     /* `stream` is being captured into a hipGraph and the call may not be recorded */
 
 #define RDF_FRONTEND_MAX_FILTER 41   /* largest Gaussian window (points_ops.py: MAX_FILTER_SIZE) */
 
@@ -143,6 +144,86 @@ int rdf_filter_points_by_plane(int n_pts, float threshold, float *pts, void *str
 int rdf_remove_missing_3d_points_from_depth_image(int n_pts, const float *pts, uint16_t *depth, void *stream);
 int rdf_gaussian_depth_filter(int dim_x, int dim_y, int k, const float *gauss, const uint16_t *d_in, uint16_t *d_out,
                               void *stream);
+
+/*
+ * ---- Fingertip heights to note events: the reference's FingertipState / HandState (src/hand_state.py:4-75), driven as
+ * src/3d_bz.py:496-522 drives them, as a state block in device memory and one kernel behind the heights. ----
+ *
+ * The state block is a struct of arrays; T = n_tips (1 .. 64), P = num_positions (11 .. 4096).  A host reads all of it
+ * with ONE copy of rdf_hand_state_bytes(T, P) bytes.  Offsets in bytes:
+ *      0  int32   n_tips
+ *      4  int32   num_positions
+ *      8  double  z_thresh_offset         the global offset added to every fingertip's threshold
+ *     16  uint32  produced                events ever produced (what a step stores into *head)
+ *     20  uint32  reserved[3]             0
+ *     32  double  z_thresh[T]
+ *         double  min_velocity[T]         15 after init
+ *         double  max_velocity[T]         150 after init
+ *         double  on_last[T]              the "on" run: its last element,
+ *         double  on_mid[T]                 and the sum of its elements 1 .. on_count-2, added in arrival order
+ *         double  positions[P][T]         a ring per fingertip: slot pos_next[t] holds the oldest height and is written next
+ *         int32   midi_note[T]
+ *         int32   note_on[T]              0 / 1
+ *         int32   velocity_sensitive[T]   0 / 1, 1 after init
+ *         int32   on_count[T]             length of the "on" run
+ *         int32   steps[T]                frames this fingertip has consumed
+ *         int32   pos_next[T]
+ * rdf_hand_state_bytes = 32 + T * (8 * (5 + P) + 4 * 6); 0 for T or P outside the ranges above.
+ *
+ * One step of fingertip t with height z (IEEE float64, no contraction; thr = z_thresh[t] + z_thresh_offset; p[-1] is the
+ * height just pushed, p[-2] and p[-3] the two before it):
+ *   z is NaN (the pipeline's "reset", 3d_bz.py:512-513): every position := 0, then OFF.
+ *   otherwise: positions[pos_next] := z, pos_next := (pos_next + 1) % P; then
+ *     z < thr:  v1 = p[-3] - p[-2], v2 = p[-2] - p[-1]; when v1 > min_velocity && v2 > min_velocity:
+ *               v = ((v1 + v2) / 2) / (max_velocity - min_velocity); v = 0.4 + v * (1 - 0.4); v > 1 -> 1; not velocity
+ *               sensitive -> 1; ON(v).  Otherwise nothing: a note stays on while the finger stays below the threshold.
+ *     else:     OFF.
+ *     then, when note_on: on_count >= 2 -> on_mid += on_last; on_last = z; on_count += 1.
+ *   ON(v) while off:  note_on = 1; event {steps, t, midi_note, (int)(v * 127)} (truncation); the on-run is cleared
+ *                     (on_count = 0, on_last = 0, on_mid = 0).
+ *   OFF while on:     note_on = 0; event {steps, t, midi_note, -1}; when on_count >= 4: on_z = on_mid / (on_count - 2.),
+ *                     and when on_z > 70: z_thresh = (1.0 - 0.1) * z_thresh + 0.1 * on_z; the on-run is cleared.
+ *   steps += 1.
+ * The one difference from the reference: it sums the on-run with np.sum(on_positions[1:-1]), which adds pairwise with eight
+ * accumulators from eight elements on; on_mid adds in arrival order.  z_thresh can differ from the reference's in the last
+ * bits (a relative 3e-16 over 3000-frame tap sequences); events and positions do not.  (The reference's positions list holds
+ * num_positions entries from the start, so its `len(positions) > 10` is always true for P >= 11.)
+ *
+ * Events are int32 [4] = {step, tip, note, velocity or -1 for note off}, stored at events[(seq % capacity) * 4] where seq
+ * counts every event since init.  Within a frame they are in fingertip order (a ballot and a prefix count over the one
+ * wave; no atomics), frames are in order, launches in stream order.  *head (uint32) receives `produced` once per launch,
+ * after a system-scope fence that follows the event stores.  events and head are device memory or pinned host memory
+ * mapped into the device's address space; a host that reads them waits for the stream first.  When more than `capacity`
+ * events arrive between two reads the oldest are overwritten; a reader sees that from head.
+ */
+#define RDF_HAND_STATE_MAX_TIPS 64
+#define RDF_HAND_STATE_MIN_POSITIONS 11
+#define RDF_HAND_STATE_MAX_POSITIONS 4096
+
+#define RDF_HAND_STATE_Z_THRESH 0
+#define RDF_HAND_STATE_MIN_VELOCITY 1
+#define RDF_HAND_STATE_MAX_VELOCITY 2
+#define RDF_HAND_STATE_VELOCITY_SENSITIVE 3     /* values[i] != 0 */
+#define RDF_HAND_STATE_Z_THRESH_OFFSET 4        /* global: tip_first = 0, n = 1 */
+
+size_t rdf_hand_state_bytes(int n_tips, int num_positions);
+
+/* Writes the whole block: the header, z_thresh and midi_notes from the HOST arrays [n_tips] (copied during the call),
+ * z_thresh_offset = 0, the defaults above, everything else 0.  state: 8-byte aligned device memory. */
+int rdf_hand_state_init(void *state, int n_tips, int num_positions, const double *z_thresh, const int32_t *midi_notes,
+                        void *stream);
+
+/* field[tip_first .. tip_first + n - 1] = values[0 .. n - 1], values a HOST array copied during the call; ordered on
+ * `stream` with the steps around it.  RDF_ERR_CAPTURE while `stream` is being captured: a recorded setter would replay
+ * the value of the day of the capture. */
+int rdf_hand_state_set(void *state, int field, int tip_first, int n, const double *values, void *stream);
+
+/* n_frames >= 1 steps of fingertips tip_first .. tip_first + n - 1 (the others are untouched), heights float64
+ * [n_frames][n] in device or mapped pinned host memory, read when the kernel runs.  One workgroup of one wave, one lane
+ * per fingertip.  n_frames = F leaves exactly the bytes and events of F calls with n_frames = 1.  A range that does not
+ * fit the block's n_tips does nothing.  capacity >= 1.  Can be captured into a graph. */
+int rdf_hand_state_step(void *state, const double *heights, int n_frames, int tip_first, int n, int32_t *events,
+                        uint32_t *head, uint32_t capacity, void *stream);
 
 int rdf_frontend_abi_version(void);
 const char *rdf_frontend_build_id(void);
