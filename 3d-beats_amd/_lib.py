@@ -26,6 +26,9 @@ SIGNATURES = {
     "rdf_layered_run_hand": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                       _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p,
                                       _c_int, _c_float, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p]),
+    "rdf_layered_run_hand_batch": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                            _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p,
+                                            _c_void_p, _c_int, _c_float, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p]),
     "rdf_forest_packed_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
     "rdf_forest_pack": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_float, _c_void_p, _c_void_p]),
     "rdf_eval_forest_packed_stats": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p,
@@ -52,11 +55,16 @@ SIGNATURES = {
     "rdf_mean_shift_heights": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int,
                                         _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _c_float, _c_void_p,
                                         _c_void_p, _c_void_p]),
+    "rdf_mean_shift_heights_batch": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p,
+                                              _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _c_float,
+                                              _c_void_p, _c_void_p, _c_int, _c_void_p]),
     "rdf_convert_0s_to_maxuint": (_c_int, [_c_void_p, _c_size_t, _c_void_p]),
     "rdf_setup_depth_image_for_forest": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_void_p]),
     "rdf_stencil_depth_image_by_group": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "rdf_flip_x": (_c_int, [_c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
     "rdf_prepare_hand_depth": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p]),
+    "rdf_prepare_hand_depth_batch": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int,
+                                              _c_void_p]),
     "rdf_make_rgba_from_labels": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "rdf_shrink_image": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
     "rdf_write_pixel_groups_to_stencil_image": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_void_p]),

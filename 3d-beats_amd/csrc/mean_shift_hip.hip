@@ -81,6 +81,7 @@ struct HeightArgs {
     float fx, fy, ppx, ppy;
     const float *plane;        // 4x4 row-major (device)
     double *heights;           // [n_ids]
+    int heights_stride;        // doubles between two frames' heights (rdf_mean_shift_heights_batch; unused for one frame)
 };
 
 __device__ __forceinline__ double height_of_mode(double mx, double my, const HeightArgs &h)
@@ -112,6 +113,10 @@ __global__ __launch_bounds__(kMsThreads) void k_mean_shift_fused(const uint16_t 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t want = blockIdx.x + 1u;
     const uint32_t n_px = (uint32_t)dim_x * (uint32_t)dim_y;
+    // workgroup (c, f) is class c of frame f (rdf_mean_shift_heights_batch); a single frame is a grid y of 1, offset 0
+    const size_t frame = blockIdx.y;
+    labels += frame * n_px;
+    means_out += frame * (size_t)L * 2;
 
     // ---- list this class's pixels.  A wave takes kMsSteps x 512 pixels per batch (512 consecutive ones per step, the
     // sixteen waves interleaved), eight per lane and step
@@ -272,9 +277,12 @@ __global__ __launch_bounds__(kMsThreads) void k_mean_shift_fused(const uint16_t 
         // the heights of this class's fingertips ride on its workgroup (rdf_mean_shift_heights: one launch less per hand
         // and frame); ids that name no class are the first workgroup's
         if (tid < hp.n_ids) {
+            HeightArgs h = hp;
+            h.depth += frame * (size_t)hp.dim_x * (size_t)hp.dim_y;
+            double *heights = hp.heights + frame * (size_t)hp.heights_stride;
             const int c = hp.class_ids[tid];
-            if (c == (int)want) hp.heights[tid] = height_of_mode(mx, my, hp);
-            else if (blockIdx.x == 0 && (c < 1 || c > L)) hp.heights[tid] = nan("");
+            if (c == (int)want) heights[tid] = height_of_mode(mx, my, h);
+            else if (blockIdx.x == 0 && (c < 1 || c > L)) heights[tid] = nan("");
         }
     }
 }
@@ -302,7 +310,7 @@ size_t rdf_mean_shift_workspace_bytes(int num_classes, int num_rounds)
 }
 
 static int mean_shift_launch(const uint16_t *labels, int dim_x, int dim_y, int num_classes, const float *variances,
-                             int num_rounds, double *means_out, const HeightArgs *heights, void *stream)
+                             int num_rounds, double *means_out, const HeightArgs *heights, void *stream, int n_frames = 1)
 {
     if (dim_x < 0 || dim_y < 0 || dim_x > 65535 || dim_y > 65535 || num_classes < 0 || num_classes > kMsMaxClasses ||
         num_rounds < 0)
@@ -328,13 +336,13 @@ static int mean_shift_launch(const uint16_t *labels, int dim_x, int dim_y, int n
         }
     }
     if (heights)
-        hipLaunchKernelGGL(k_mean_shift_fused<true>, dim3((unsigned)num_classes), dim3(kMsThreads), lds_bytes,
-                           reinterpret_cast<hipStream_t>(stream), labels, dim_x, dim_y, num_classes, variances, num_rounds,
-                           means_out, *heights);
+        hipLaunchKernelGGL(k_mean_shift_fused<true>, dim3((unsigned)num_classes, (unsigned)n_frames), dim3(kMsThreads),
+                           lds_bytes, reinterpret_cast<hipStream_t>(stream), labels, dim_x, dim_y, num_classes, variances,
+                           num_rounds, means_out, *heights);
     else
-        hipLaunchKernelGGL(k_mean_shift_fused<false>, dim3((unsigned)num_classes), dim3(kMsThreads), lds_bytes,
-                           reinterpret_cast<hipStream_t>(stream), labels, dim_x, dim_y, num_classes, variances, num_rounds,
-                           means_out, HeightArgs{});
+        hipLaunchKernelGGL(k_mean_shift_fused<false>, dim3((unsigned)num_classes, (unsigned)n_frames), dim3(kMsThreads),
+                           lds_bytes, reinterpret_cast<hipStream_t>(stream), labels, dim_x, dim_y, num_classes, variances,
+                           num_rounds, means_out, HeightArgs{});
     return (int)hipGetLastError();
 }
 
@@ -352,7 +360,7 @@ int rdf_fingertip_heights(const double *means, int num_classes, const int *class
     if (num_classes < 0 || n_ids < 0 || dim_x < 0 || dim_y < 0 || labels_reduce < 1) return RDF_ERR_BAD_ARG;
     if (n_ids == 0) return RDF_OK;
     if (!means || !class_ids || !depth || !plane || !heights_out) return RDF_ERR_NULL_PTR;
-    const HeightArgs h = {class_ids, n_ids, depth, dim_x, dim_y, labels_reduce, fx, fy, ppx, ppy, plane, heights_out};
+    const HeightArgs h = {class_ids, n_ids, depth, dim_x, dim_y, labels_reduce, fx, fy, ppx, ppy, plane, heights_out, 0};
     hipLaunchKernelGGL(k_fingertip_heights, dim3((n_ids + 63) / 64), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
                        means, num_classes, h);
     return (int)hipGetLastError();
@@ -373,8 +381,29 @@ int rdf_mean_shift_heights(const uint16_t *labels, int dim_x, int dim_y, int num
     }
     if (!class_ids || !depth || !plane || !heights_out) return RDF_ERR_NULL_PTR;
     const HeightArgs h = {class_ids, n_ids, depth, depth_dim_x, depth_dim_y, labels_reduce, fx, fy, ppx, ppy, plane,
-                          heights_out};
+                          heights_out, 0};
     return mean_shift_launch(labels, dim_x, dim_y, num_classes, variances, num_rounds, means_out, &h, stream);
+}
+
+int rdf_mean_shift_heights_batch(const uint16_t *labels, int n, int dim_x, int dim_y, int num_classes, const float *variances,
+                                 int num_rounds, double *means_out, const int *class_ids, int n_ids, const uint16_t *depth,
+                                 int depth_dim_x, int depth_dim_y, int labels_reduce, float fx, float fy, float ppx, float ppy,
+                                 const float *plane, double *heights_out, int heights_stride, void *stream)
+{
+    // (no two-call fallback here: a batch without ids or classes is refused)
+    if (n < 0 || n_ids <= 0 || n_ids > kMsThreads || num_classes <= 0 || depth_dim_x < 0 || depth_dim_y < 0 ||
+        labels_reduce < 1 || heights_stride < n_ids)
+        return RDF_ERR_BAD_ARG;
+    if (dim_x < 0 || dim_y < 0 || dim_x > 65535 || dim_y > 65535 || num_classes > kMsMaxClasses || num_rounds < 0)
+        return RDF_ERR_BAD_ARG;
+    if (n > 65535) return RDF_ERR_TOO_LARGE;      // (the frame is the grid's y)
+    if (n == 0) return RDF_OK;
+    // the depth lookup indexes one frame with a long long; a frame of 2^31 pixels or more is refused like the labels'
+    if ((long long)depth_dim_x * depth_dim_y >= (1ll << 31)) return RDF_ERR_TOO_LARGE;
+    if (!class_ids || !depth || !plane || !heights_out) return RDF_ERR_NULL_PTR;
+    const HeightArgs h = {class_ids, n_ids, depth, depth_dim_x, depth_dim_y, labels_reduce, fx, fy, ppx, ppy, plane,
+                          heights_out, heights_stride};
+    return mean_shift_launch(labels, dim_x, dim_y, num_classes, variances, num_rounds, means_out, &h, stream, n);
 }
 
 } // extern "C"

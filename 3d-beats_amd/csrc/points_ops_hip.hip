@@ -83,6 +83,7 @@ __global__ __launch_bounds__(256) void k_rgba(int dim_x, int dim_y, int num_colo
 // The app's per-hand input chain in ONE read and ONE write (3d_bz.py:396-420: fill(0) -> stencil_depth_image_by_group ->
 // flip_x or copy -> convert_0s_to_maxuint): out[y][x'] = (group(x, y) == g and d != 0) ? d : 65535, x' = W-1-x when
 // flipping.  One lane = eight consecutive pixels of a row (16 bytes in, 16 bytes out where the row pitch allows).
+// blockIdx.z = the frame of a batch (rdf_prepare_hand_depth_batch); a single frame is a grid z of 1.
 __global__ __launch_bounds__(256) void k_prepare_hand(int dim_x, int dim_y, int level, int group, const uint16_t *g_in,
                                                       const uint16_t *d_in, uint16_t *d_out, int flip, int vec_ok)
 {
@@ -91,7 +92,8 @@ __global__ __launch_bounds__(256) void k_prepare_hand(int dim_x, int dim_y, int 
     if (x0 >= dim_x || y >= dim_y) return;
     const int gw = dim_x >> level, gh = dim_y >> level;
     const int gy = y >> level;
-    const size_t row = (size_t)y * dim_x;
+    const size_t row = (size_t)blockIdx.z * dim_y * dim_x + (size_t)y * dim_x;
+    g_in += (size_t)blockIdx.z * gh * gw;
     uint32_t v[8];
     const int n = min(8, dim_x - x0);
     if (vec_ok && n == 8) {
@@ -201,6 +203,24 @@ int rdf_prepare_hand_depth(int dim_x, int dim_y, int mipmap_level, int group, co
     if (depth_in == depth_out && flip_x) return RDF_ERR_BAD_ARG;   // a flip in place would read what it has overwritten
     const int vec_ok = dim_x % 8 == 0 && ((reinterpret_cast<uintptr_t>(depth_in) | reinterpret_cast<uintptr_t>(depth_out)) & 15u) == 0;
     hipLaunchKernelGGL(k_prepare_hand, dim3((dim_x + 511) / 512, (dim_y + 3) / 4), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), dim_x, dim_y, mipmap_level, group, groups_in, depth_in,
+                       depth_out, flip_x ? 1 : 0, vec_ok);
+    return (int)hipGetLastError();
+}
+
+int rdf_prepare_hand_depth_batch(int n, int dim_x, int dim_y, int mipmap_level, int group, const uint16_t *groups_in,
+                                 const uint16_t *depth_in, uint16_t *depth_out, int flip_x, void *stream)
+{
+    if (n < 0 || dim_x < 0 || dim_y < 0 || mipmap_level < 0 || mipmap_level > 30) return RDF_ERR_BAD_ARG;
+    if (n == 0 || dim_x == 0 || dim_y == 0) return RDF_OK;
+    if (!groups_in || !depth_in || !depth_out) return RDF_ERR_NULL_PTR;
+    if (depth_in == depth_out && flip_x) return RDF_ERR_BAD_ARG;   // a flip in place would read what it has overwritten
+    if (n > 65535) return RDF_ERR_TOO_LARGE;                       // (the frame is the grid's z)
+    // every frame starts a whole number of 16-byte words behind the base, or the call takes the scalar path
+    const size_t frame_bytes = (size_t)dim_x * dim_y * sizeof(uint16_t);
+    const int vec_ok = dim_x % 8 == 0 && (n == 1 || frame_bytes % 16 == 0) &&
+                       ((reinterpret_cast<uintptr_t>(depth_in) | reinterpret_cast<uintptr_t>(depth_out)) & 15u) == 0;
+    hipLaunchKernelGGL(k_prepare_hand, dim3((dim_x + 511) / 512, (dim_y + 3) / 4, n), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), dim_x, dim_y, mipmap_level, group, groups_in, depth_in,
                        depth_out, flip_x ? 1 : 0, vec_ok);
     return (int)hipGetLastError();

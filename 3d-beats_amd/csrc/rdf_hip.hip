@@ -2715,14 +2715,15 @@ int rdf_composite(const uint16_t *const *label_images, int n_images, int dim_x, 
     return (int)hipGetLastError();
 }
 
-static int layered_run(const uint16_t *depth, int dim_x, int dim_y, int n_layers, const void *const *packed,
+// `n_img` frames [n_img][dim_y][dim_x]; the label images and the composite are [n_img][lh][lw] (rdf_layered_run_hand_batch).
+static int layered_run(const uint16_t *depth, int n_img, int dim_x, int dim_y, int n_layers, const void *const *packed,
                        const float *const *forests, const int *n_trees, const int *max_depth, const int *n_classes,
                        const int *filter_layer, const int *filter_class, uint16_t *const *layer_labels,
                        const uint16_t *const *layer_labels_dev_table, const int32_t *cond, int n_cond,
                        uint16_t *composite_out, int32_t *bad_count, int labels_reduce, float scale_factor,
                        int flip_x, const uint8_t *colors_rgba, int num_colors, uint8_t *image_rgba, void *stream)
 {
-    if (n_layers < 0 || dim_x < 0 || dim_y < 0 || labels_reduce < 1 || n_cond < 0) return RDF_ERR_BAD_ARG;
+    if (n_img < 0 || n_layers < 0 || dim_x < 0 || dim_y < 0 || labels_reduce < 1 || n_cond < 0) return RDF_ERR_BAD_ARG;
     if (n_layers > 0 && (!forests || !n_trees || !max_depth || !n_classes || !filter_layer || !filter_class ||
                          !layer_labels || !layer_labels_dev_table))
         return RDF_ERR_NULL_PTR;
@@ -2737,10 +2738,11 @@ static int layered_run(const uint16_t *depth, int dim_x, int dim_y, int n_layers
     // UNFILTERED in ONE launch (workgroup b takes layer b % n_layers: k_eval_forest<..., NL>) and the composite kernel
     // applies the filters afterwards (SpecFilters): same label images, same composite, one ramp and drain instead of
     // n_layers.  Two launches on two streams do not get there: a cross-queue event join costs more than it saves
-    // (DESIGN.md section 4).  Big launches keep the filtered evaluation, which does less work.
+    // (DESIGN.md section 4).  Big launches keep the filtered evaluation, which does less work, and so does a batch of
+    // frames (n_img > 1): one launch per layer over all frames.
     SpecFilters spec = {};
     DeviceState *dsp = nullptr;     // the current device's state: looked up by the first plan, for all layers
-    if (g_layers_one_launch.get(1) && (n_layers == 2 || n_layers == 3) && packed) {
+    if (n_img == 1 && g_layers_one_launch.get(1) && (n_layers == 2 || n_layers == 3) && packed) {
         Plan plans[3];
         bool ok = true;
         int cmax = 4, lds = 0;
@@ -2792,13 +2794,13 @@ static int layered_run(const uint16_t *depth, int dim_x, int dim_y, int n_layers
         const uint16_t *filt = fl >= 0 ? layer_labels[fl] : nullptr;
         const void *pk = packed ? packed[i] : nullptr;
         if (pk && max_depth[i] > 27) pk = nullptr;
-        const int rc = eval_common({depth, 1, dim_x, dim_y, pk, forests[i], n_trees[i], max_depth[i], n_classes[i],
+        const int rc = eval_common({depth, n_img, dim_x, dim_y, pk, forests[i], n_trees[i], max_depth[i], n_classes[i],
                                     filt, fl >= 0 ? filter_class[i] : -1, layer_labels[i], labels_reduce,
                                     pk ? 1.0f : scale_factor, 0, nullptr, stream, /*fill_untouched=*/1}, nullptr, &dsp);
         if (rc != RDF_OK) return rc;
     }
     const int lw = dim_x / labels_reduce, lh = dim_y / labels_reduce;
-    const long long n_px = (long long)lw * lh;
+    const long long n_px = (long long)n_img * lw * lh;      // (rows are whole: the flip inside a row holds across frames)
     if (n_px == 0) return RDF_OK;
     if (n_cond > 0 && !cond) return RDF_ERR_NULL_PTR;
     const unsigned blocks = (unsigned)((n_px + 255) / 256);
@@ -2818,9 +2820,35 @@ int rdf_layered_run_hand(const uint16_t *depth, int dim_x, int dim_y, int n_laye
 {
     if (num_colors < 0 || (image_rgba && num_colors > 0 && !colors_rgba)) return RDF_ERR_BAD_ARG;
     const unsigned long long t0 = now_ns();
-    const int rc = layered_run(depth, dim_x, dim_y, n_layers, packed, forests, n_trees, max_depth, n_classes, filter_layer,
+    const int rc = layered_run(depth, 1, dim_x, dim_y, n_layers, packed, forests, n_trees, max_depth, n_classes, filter_layer,
                                filter_class, layer_labels, layer_labels_dev_table, cond, n_cond, composite_out, bad_count,
                                labels_reduce, scale_factor, flip_x, colors_rgba, num_colors, image_rgba, stream);
+    g_host_ns_layered.fetch_add(now_ns() - t0, std::memory_order_relaxed);
+    g_host_layered_calls.fetch_add(1, std::memory_order_relaxed);
+    return rc;
+}
+
+int rdf_layered_run_hand_batch(const uint16_t *depth, int n_img, int dim_x, int dim_y, int n_layers,
+                               const void *const *packed, const float *const *forests, const int *n_trees,
+                               const int *max_depth, const int *n_classes, const int *filter_layer, const int *filter_class,
+                               uint16_t *const *layer_labels, const uint16_t *const *layer_labels_dev_table,
+                               const int32_t *cond, int n_cond, uint16_t *composite_out, int32_t *bad_count,
+                               int labels_reduce, float scale_factor, int flip_x, const uint8_t *colors_rgba, int num_colors,
+                               uint8_t *image_rgba, void *stream)
+{
+    if (n_img < 0) return RDF_ERR_BAD_ARG;
+    if (n_img == 1)     // one frame: the single call itself, with its one-launch path for small stacks
+        return rdf_layered_run_hand(depth, dim_x, dim_y, n_layers, packed, forests, n_trees, max_depth, n_classes, filter_layer,
+                                    filter_class, layer_labels, layer_labels_dev_table, cond, n_cond, composite_out, bad_count,
+                                    labels_reduce, scale_factor, flip_x, colors_rgba, num_colors, image_rgba, stream);
+    if (num_colors < 0 || (image_rgba && num_colors > 0 && !colors_rgba)) return RDF_ERR_BAD_ARG;
+    if (dim_x < 0 || dim_y < 0 || labels_reduce < 1) return RDF_ERR_BAD_ARG;
+    // the composite indexes every label pixel of the batch with 32 bits
+    if ((long long)n_img * (dim_x / labels_reduce) * (dim_y / labels_reduce) >= (1ll << 31)) return RDF_ERR_TOO_LARGE;
+    const unsigned long long t0 = now_ns();
+    const int rc = layered_run(depth, n_img, dim_x, dim_y, n_layers, packed, forests, n_trees, max_depth, n_classes,
+                               filter_layer, filter_class, layer_labels, layer_labels_dev_table, cond, n_cond, composite_out,
+                               bad_count, labels_reduce, scale_factor, flip_x, colors_rgba, num_colors, image_rgba, stream);
     g_host_ns_layered.fetch_add(now_ns() - t0, std::memory_order_relaxed);
     g_host_layered_calls.fetch_add(1, std::memory_order_relaxed);
     return rc;

@@ -58,6 +58,22 @@ class MeanShift:
                                               self._rt.stream())
         _lib.check(self._lib, rc, "rdf_mean_shift_heights")
 
+    def run_device_with_heights_batch(self, num_rounds, labels, num_labels, variances, class_ids, n_ids, depth_images,
+                                      labels_reduce, intrinsics, plane, means_out_ptr, heights_out_ptr, heights_stride):
+        """run_device_with_heights() for the n frames of labels [n, dim_y, dim_x] and depth_images [n, H, W] in ONE launch
+        (rdf_mean_shift_heights_batch): means float64 [n, num_labels, 2] at means_out_ptr, the height of id i of frame f at
+        heights_out_ptr + 8 * (f * heights_stride + i); each frame bit for bit what the single call gives."""
+        n, dim_y, dim_x = labels.shape
+        assert int(depth_images.shape[0]) == int(n), (labels.shape, depth_images.shape)
+        ddy, ddx = depth_images.shape[-2:]
+        fx, fy, ppx, ppy = (float(v) for v in intrinsics)
+        rc = self._lib.rdf_mean_shift_heights_batch(device_ptr(labels), int(n), int(dim_x), int(dim_y), int(num_labels),
+                                                    device_ptr(variances), int(num_rounds), int(means_out_ptr),
+                                                    device_ptr(class_ids), int(n_ids), device_ptr(depth_images), int(ddx),
+                                                    int(ddy), int(labels_reduce), fx, fy, ppx, ppy, device_ptr(plane),
+                                                    int(heights_out_ptr), int(heights_stride), self._rt.stream())
+        _lib.check(self._lib, rc, "rdf_mean_shift_heights_batch")
+
 
 def fingertip_heights(means, class_ids, depth_image, labels_reduce, fx, fy, ppx, ppy, plane):
     """Device version of the per-fingertip height of 3d_bz.py:503-522.

@@ -67,6 +67,15 @@ class PointsOps:
                                                   device_ptr(d_in), device_ptr(d_out), 1 if flip_x else 0, self._rt.stream()),
                  "rdf_prepare_hand_depth", d_out)
 
+    def prepare_hand_depth_batch(self, n, img_dim, mipmap_level, group, g_in, d_in, d_out, flip_x):
+        """prepare_hand_depth for n frames in one launch (rdf_prepare_hand_depth_batch): g_in [n, dim_y >> level,
+        dim_x >> level], d_in and d_out [n, dim_y, dim_x]; frame f of d_out is what prepare_hand_depth makes of frame f."""
+        dim_x, dim_y = (int(v) for v in np.asarray(img_dim).reshape(-1)[:2])
+        self._ok(self._lib.rdf_prepare_hand_depth_batch(int(n), dim_x, dim_y, int(mipmap_level), int(group), device_ptr(g_in),
+                                                        device_ptr(d_in), device_ptr(d_out), 1 if flip_x else 0,
+                                                        self._rt.stream()),
+                 "rdf_prepare_hand_depth_batch", d_out)
+
     def flip_x(self, img_dim, img_in, img_out, grid=None, block=None):
         dim_x, dim_y = (int(v) for v in np.asarray(img_dim).reshape(-1)[:2])
         self._ok(self._lib.rdf_flip_x(dim_x, dim_y, device_ptr(img_in), device_ptr(img_out), self._rt.stream()),

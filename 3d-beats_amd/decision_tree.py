@@ -348,8 +348,54 @@ class LayeredDecisionForest:
                                      np.uint32(self.num_layered_classes), labels_image.cu(), self.label_colors.cu(),
                                      color_image.cu())
 
-    def _run_fused(self, depth_image, labels_image, scale_factor, flip_x=False, color_image=None):
-        """Same result through ONE C-ABI call (rdf_layered_run): the three fills are fused into the kernels."""
+    def run_hand_batch(self, depth_images, labels_images, scale_factor=1., flip_x=False, color_images=None):
+        """run_hand() for n frames in one call (rdf_layered_run_hand_batch): depth_images [n, H, W], labels_images
+        [n, lh, lw] and color_images [n, lh, lw, 4] (or None) are device arrays; every frame's composite, colours and
+        per-layer labels are what run_hand() leaves for that frame alone.  The per-layer labels land in
+        `batch_label_images` (one [capacity, lh, lw] array a layer, the first n frames of each), NOT in `label_images`,
+        which stay the single-frame path's.  Those buffers and their device pointer table are allocated once, for the
+        largest n seen, before anything is enqueued: call it once with the largest batch before capturing a stream.
+        Stacks that cannot take the fused call raise ValueError."""
+        import ctypes
+        if not self.fused:
+            raise ValueError("run_hand_batch needs a stack that takes the fused call (no layer filtering on a later layer)")
+        depth_images = depth_images.cu() if hasattr(depth_images, "cu") else depth_images
+        labels_images = labels_images.cu() if hasattr(labels_images, "cu") else labels_images
+        n = int(depth_images.shape[0])
+        assert tuple(depth_images.shape) == (n,) + self.depth_dims, depth_images.shape
+        assert tuple(labels_images.shape) == (n,) + tuple(self.labels_dims), labels_images.shape
+        if color_images is not None:
+            color_images = color_images.cu() if hasattr(color_images, "cu") else color_images
+            assert tuple(color_images.shape) == (n,) + tuple(self.labels_dims) + (4,), color_images.shape
+        nl = self.num_models
+        if getattr(self, "_batch_capacity", 0) < n:
+            self.batch_label_images = [DeviceArray((n,) + tuple(self.labels_dims), np.uint16) for _ in range(nl)]
+            self._batch_ptrs_cu = DeviceArray((max(nl, 1),), np.int64)
+            self._batch_ptrs_cu[:nl].set(np.array([b.ptr for b in self.batch_label_images], dtype=np.int64))
+            self._batch_layer_labels = (ctypes.c_void_p * nl)(*[b.ptr for b in self.batch_label_images])
+            self._batch_capacity = n
+        fa = self._fused_tables()
+        packed = None
+        if self.eval.use_packed:
+            tabs = [m.packed(scale_factor) if m.max_depth <= 27 else None for m, _, _ in self.m]
+            packed = fa["vp"](*[t.ptr if t is not None else None for t in tabs])
+        ev = self.eval
+        rc = ev._lib.rdf_layered_run_hand_batch(
+            depth_images.ptr, n, int(self.depth_dims[1]), int(self.depth_dims[0]), nl, packed, fa["forests"], fa["n_trees"],
+            fa["max_depth"], fa["n_classes"], fa["filter_layer"], fa["filter_class"], self._batch_layer_labels,
+            self._batch_ptrs_cu.ptr, device_ptr(self.labels_conditions_cu), int(self.labels_conditions_cu.shape[0]),
+            labels_images.ptr, ev._composite_bad.ptr, int(self.labels_reduce), float(scale_factor), 1 if flip_x else 0,
+            device_ptr(self.label_colors), int(self.num_layered_classes),
+            color_images.ptr if color_images is not None else None, ev._rt.stream())
+        _lib.check(ev._lib, rc, "rdf_layered_run_hand_batch")
+        for b in self.batch_label_images:
+            _touch(b)
+        _touch(labels_images)
+        if color_images is not None:
+            _touch(color_images)
+
+    def _fused_tables(self):
+        """The host arrays of the fused calls that never change: made once."""
         import ctypes
         n = self.num_models
         if self._fused_args is None:
@@ -362,7 +408,12 @@ class LayeredDecisionForest:
                 filter_layer=ci(*[-1 if f is None else int(f) for _, f, _ in self.m]),
                 filter_class=ci(*[-1 if c is None else int(c) for _, _, c in self.m]),
                 layer_labels=vp(*[device_ptr(b) for b in self.label_images]), vp=vp)
-        fa = self._fused_args
+        return self._fused_args
+
+    def _run_fused(self, depth_image, labels_image, scale_factor, flip_x=False, color_image=None):
+        """Same result through ONE C-ABI call (rdf_layered_run): the three fills are fused into the kernels."""
+        n = self.num_models
+        fa = self._fused_tables()
         packed = None
         if self.eval.use_packed:
             tabs = [m.packed(scale_factor) if m.max_depth <= 27 else None for m, _, _ in self.m]

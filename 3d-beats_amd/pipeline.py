@@ -133,6 +133,39 @@ class HandPipeline:
         """run() without the read: the frame, and the hand_state's step when there is one, on the current stream."""
         self._enqueue(depth_image, depth_image_mm_groups, g_id, flip_x, height_depth)
 
+    def enqueue_batch(self, depth_images, group_images, g_id, flip_x, height_depth, heights_out_ptr, heights_stride):
+        """The chain for n frames in three calls (rdf_prepare_hand_depth_batch, rdf_layered_run_hand_batch,
+        rdf_mean_shift_heights_batch) on the current stream: depth_images and height_depth are device arrays uint16
+        [n, DIM_Y, DIM_X], group_images [n, DIM_Y >> level, DIM_X >> level].  Frame f's heights (float64 [n_fingertips]) go
+        to heights_out_ptr + 8 * f * heights_stride (device memory), its modes to `means_batch[f]` (device, [n, L, 2]) and
+        its composite to `labels_batch[f]`; each frame bit for bit what enqueue() computes for it.  No RGBA image is written
+        and no hand_state is stepped: the caller steps it, once for both hands.  The batch buffers are sized on first use,
+        for the largest n seen."""
+        if not self.fused_io:
+            raise ValueError("enqueue_batch needs fused_io=True")
+        depth_images, group_images, height_depth = (a.cu() if hasattr(a, "cu") else a
+                                                    for a in (depth_images, group_images, height_depth))
+        n = int(depth_images.shape[0])
+        assert tuple(depth_images.shape) == (n, self.DIM_Y, self.DIM_X), depth_images.shape
+        assert tuple(height_depth.shape) == (n, self.DIM_Y, self.DIM_X), height_depth.shape
+        assert int(group_images.shape[0]) == n, group_images.shape
+        if getattr(self, "_batch_capacity", 0) < n:
+            self._depth_batch = DeviceArray((n, self.DIM_Y, self.DIM_X), np.uint16)
+            self._labels_batch = DeviceArray((n, self.LABELS_DIM_Y, self.LABELS_DIM_X), np.uint16)
+            self._means_batch = DeviceArray((n, self._L, 2), np.float64)
+            self._batch_capacity = n
+        dims = np.array([self.DIM_X, self.DIM_Y], dtype=np.int32)
+        depth_2, labels = self._depth_batch[:n], self._labels_batch[:n]
+        self.labels_batch, self.means_batch = labels, self._means_batch[:n]
+        self.points_ops.prepare_hand_depth_batch(n, dims, self.depth_mm_level, g_id, group_images, depth_images, depth_2,
+                                                 flip_x)
+        self.layered_rdf.run_hand_batch(depth_2, labels, self.EVAL_TO_TRAIN_DIM_RATIO, flip_x)
+        self.mean_shift.run_device_with_heights_batch(
+            self.mean_shift_rounds, labels, self._L, self.mean_shift_variances, self._ids, len(self.fingertip_idxes),
+            height_depth, self.LABELS_REDUCE, self.intrinsics, self._plane, self.means_batch.ptr, heights_out_ptr,
+            heights_stride)
+        self.means_batch.mark_dirty()
+
     @property
     def heights_ptr(self):
         """Where a frame's fingertip heights (float64 [n]) land: mapped pinned host memory with fused_io, else device memory."""

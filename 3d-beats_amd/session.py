@@ -104,12 +104,18 @@ class BeatsSession:
         return self.hand_state.poll()
 
     # -- offline --
-    def run_sequence(self, frames):
+    def run_sequence(self, frames, batched=False):
         """frames: uint16 [F, DIM_Y, DIM_X] on the host or the device.  The front end and the grouping run in batches of
-        max_frames; the per-hand chains run frame by frame (batching the layered forest and the mean shift over frames is
-        out of scope here); one synchronisation, at the end.  Returns (events, heights float64 [F, 10]).  The heights log
-        is written on the device: each hand's heights are copied into the frame's row behind its chain (a stream-ordered
-        copy of 40 bytes), and the log is read once, after the last frame."""
+        max_frames; one synchronisation, at the end.  Returns (events, heights float64 [F, 10]).  The heights log is
+        written on the device and read once, after the last frame.
+        batched=False: the per-hand chains run frame by frame; each hand's heights are copied into the frame's row behind
+        its chain (a stream-ordered copy of 40 bytes).
+        batched=True (needs fused_io): the per-hand chains take the whole block too -- HandPipeline.enqueue_batch for the
+        right hand writes columns 0-4 of the block's log rows, for the left hand columns 5-9, and ONE note step advances
+        all ten fingertips over the block's frames.  Same events, heights and state, bit for bit; a prepare, one launch a
+        forest layer, a composite and a mean shift per hand and block instead of per hand and frame, and no copies."""
+        if batched and not (self.right.fused_io and self.left.fused_io):
+            raise ValueError("run_sequence(batched=True) needs a session built with fused_io=True")
         F = int(frames.shape[0])
         n = self.n_tips // 2
         log = DeviceArray((max(F, 1), self.n_tips), np.float64)
@@ -119,6 +125,13 @@ class BeatsSession:
             raw = self._on_device(frames[a:a + b], b)
             self.front_end.run(raw, self._clean[:b])
             self.grouping.make_group_image(self._clean[:b], self._groups[:b])
+            if batched:
+                row = log.ptr + a * self.n_tips * 8
+                # the right hand's columns precede the left's: events of a frame come out right hand first, as in tick()
+                self.right.enqueue_batch(self._clean[:b], self._groups[:b], 1, False, raw, row, self.n_tips)
+                self.left.enqueue_batch(self._clean[:b], self._groups[:b], 2, True, raw, row + n * 8, self.n_tips)
+                self.hand_state.step_device(row, 0, self.n_tips, n_frames=b)
+                continue
             for i in range(b):
                 raw_i = _Frame(raw[i])
                 for pipe in (self.right, self.left):

@@ -33,7 +33,9 @@ extern "C" {
  * chose for is walked from the heap-order records (version 3 chose by forest size); new: rdf_forest_info,
  * rdf_forest_forget, rdf_build_id, RDF_ERR_CAPTURE (was RDF_ERR_BAD_ARG).  Nothing was removed or re-typed; table sizes unchanged.
  * 5: a packed table's info block carries the shape it was packed for and a generation number (tables of version 4 are refused:
- * re-pack); new: RDF_ERR_STALE, rdf_eval_forest_packed_split.  Nothing was removed or re-typed; table sizes unchanged. */
+ * re-pack); new: RDF_ERR_STALE, rdf_eval_forest_packed_split.  Nothing was removed or re-typed; table sizes unchanged.
+ * Added since, without a new number (pure additions): rdf_prepare_hand_depth_batch, rdf_layered_run_hand_batch,
+ * rdf_mean_shift_heights_batch. */
 #define RDF_ABI_VERSION 5
 
 #define RDF_OK 0
@@ -134,6 +136,23 @@ int rdf_layered_run_hand(const uint16_t *depth, int dim_x, int dim_y, int n_laye
                          const int32_t *cond, int n_cond, uint16_t *composite_out, int32_t *bad_count,
                          int labels_reduce, float scale_factor, int flip_x, const uint8_t *colors_rgba,
                          int num_colors, uint8_t *image_rgba, void *stream);
+
+/*
+ * rdf_layered_run_hand for n_img frames in one call: depth is [n_img][dim_y][dim_x], every layer_labels[i] and
+ * composite_out are [n_img][lh][lw] (lw = dim_x / labels_reduce, lh = dim_y / labels_reduce), image_rgba is
+ * [n_img][lh][lw][4] or NULL.  Every output byte equals what n_img calls of rdf_layered_run_hand on the frames one by one
+ * leave, and *bad_count grows by the same total.  n_img == 1 IS rdf_layered_run_hand; n_img > 1 evaluates each layer
+ * filtered, in one launch over all frames, and composites all frames in one launch: n_layers + 1 launches a batch.
+ * n_img * lw * lh must stay below 2^31 (RDF_ERR_TOO_LARGE).  n_img == 0 launches nothing.
+ */
+int rdf_layered_run_hand_batch(const uint16_t *depth, int n_img, int dim_x, int dim_y, int n_layers,
+                               const void *const *packed, const float *const *forests,
+                               const int *n_trees, const int *max_depth, const int *n_classes,
+                               const int *filter_layer, const int *filter_class,
+                               uint16_t *const *layer_labels, const uint16_t *const *layer_labels_dev_table,
+                               const int32_t *cond, int n_cond, uint16_t *composite_out, int32_t *bad_count,
+                               int labels_reduce, float scale_factor, int flip_x, const uint8_t *colors_rgba,
+                               int num_colors, uint8_t *image_rgba, void *stream);
 
 /*
  * Load-time repack of a forest into a table of 16-byte hot records {23-bit floor(s*u), 23-bit floor(s*v), integer threshold,
@@ -323,6 +342,18 @@ int rdf_mean_shift_heights(const uint16_t *labels, int dim_x, int dim_y, int num
                            const float *plane, double *heights_out, void *stream);
 
 /*
+ * rdf_mean_shift_heights for n frames in ONE launch (workgroup (c, f) = class c of frame f): labels is [n][dim_y][dim_x],
+ * depth is [n][depth_dim_y][depth_dim_x], means_out is float64 [n][num_classes][2], and the height of id i in frame f goes
+ * to heights_out[f * heights_stride + i] (heights_stride in doubles, >= n_ids; what lies between the rows is not touched).
+ * Frame f's means and heights equal, bit for bit, what rdf_mean_shift_heights gives for frame f alone.  There is no
+ * two-call fallback here: n_ids == 0 or num_classes == 0 is RDF_ERR_BAD_ARG.  n <= 65535; n == 0 launches nothing.
+ */
+int rdf_mean_shift_heights_batch(const uint16_t *labels, int n, int dim_x, int dim_y, int num_classes, const float *variances,
+                                 int num_rounds, double *means_out, const int *class_ids, int n_ids, const uint16_t *depth,
+                                 int depth_dim_x, int depth_dim_y, int labels_reduce, float fx, float fy, float ppx, float ppy,
+                                 const float *plane, double *heights_out, int heights_stride, void *stream);
+
+/*
  * ---- element-wise kernels either side of the forest; all in place / byte exact ----
  * rdf_convert_0s_to_maxuint           src/cuda/points_ops.cu:117-127   depth[i] == 0 -> 65535
  * rdf_setup_depth_image_for_forest    :149-165   depth[i] == 0 or pts[i].w == 0 -> 65535 (pts = float4 per pixel)
@@ -342,6 +373,11 @@ int rdf_flip_x(int dim_x, int dim_y, const uint16_t *in, uint16_t *out, void *st
  * rdf_flip_x (or a copy) + rdf_convert_0s_to_maxuint.  depth_in and depth_out may be the same buffer only when flip_x == 0. */
 int rdf_prepare_hand_depth(int dim_x, int dim_y, int mipmap_level, int group, const uint16_t *groups_in,
                            const uint16_t *depth_in, uint16_t *depth_out, int flip_x, void *stream);
+/* rdf_prepare_hand_depth for n frames in one launch: groups_in is [n][dim_y >> level][dim_x >> level], depth_in and depth_out
+ * are [n][dim_y][dim_x]; frame f of depth_out is what rdf_prepare_hand_depth writes for frame f of the inputs.  n <= 65535;
+ * n == 0 launches nothing. */
+int rdf_prepare_hand_depth_batch(int n, int dim_x, int dim_y, int mipmap_level, int group, const uint16_t *groups_in,
+                                 const uint16_t *depth_in, uint16_t *depth_out, int flip_x, void *stream);
 int rdf_make_rgba_from_labels(int dim_x, int dim_y, int num_colors, const uint16_t *labels,
                               const uint8_t *colors_rgba, uint8_t *image_rgba, void *stream);
 
