@@ -181,6 +181,9 @@ BINDINGS = {
         "rdf_rerender_workspace_bytes": (_c_size_t, [_c_int, _c_int]),
         "rdf_rerender": (_c_int, [_c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_float, _c_float, _c_float, _c_float,
                                   _c_float, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+        "rdf_score_counts_bytes": (_c_size_t, [_c_int]),
+        "rdf_score_labels": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                      _c_void_p]),
         "rdf_labels_abi_version": (_c_int, []),
         "rdf_labels_build_id": (ctypes.c_char_p, []),
         "rdf_labels_error_string": (ctypes.c_char_p, [_c_int]),

@@ -372,7 +372,7 @@ const char *rdf_labels_error_string(int code)
 {
     switch (code) {
     case RDF_OK: return "ok";
-    case RDF_ERR_BAD_ARG: return "rdf_labels: bad argument (colours outside 1..16, tries outside 1..8, iterations < 1, a misaligned pointer; a re-render with a matrix that is not affine, f <= 0 or an empty depth range)";
+    case RDF_ERR_BAD_ARG: return "rdf_labels: bad argument (colours outside 1..16, tries outside 1..8, iterations < 1, a misaligned pointer; a score with classes outside 1..64 or labels_reduce < 1; a re-render with a matrix that is not affine, f <= 0 or an empty depth range)";
     case RDF_ERR_NULL_PTR: return "rdf_labels: required pointer is NULL";
     case RDF_ERR_TOO_LARGE: return "rdf_labels: call addresses >= 2^31 elements";
     default: return code > 0 ? hipGetErrorString(static_cast<hipError_t>(code)) : "rdf_labels: unknown error";

@@ -164,8 +164,57 @@ def evaluate_saved_model(model_path, dataset_dir, num_images, out_dir=None):
     return pct
 
 
+def score_saved_model(model_path, dataset_dir, num_images, labels_reduce=1):
+    """evaluate_saved_model's flow with the comparison on the device: the forest's label maps of `num_images` random images
+    against their truth as a score.Score (confusion matrix, per-class and per-image figures).  No label map is read back.
+    With the same numpy seed, .pct_matching at labels_reduce 1 is evaluate_saved_model's return value bit for bit; above
+    1 the forest writes [H // r, W // r] maps and the truth is sampled at (x * r, y * r)."""
+    from .decision_tree import DecisionForest, DecisionTreeEvaluator
+    from .device import DeviceArray
+    from .score import LabelScorer
+    from .util import MAX_UINT16
+    forest = DecisionForest.load(model_path)
+    ev = DecisionTreeEvaluator()
+    ds = DecisionTreeDatasetConfig(dataset_dir, num_images=num_images, imgs_name='test')
+    n, h, w = ds.images_shape()
+    depth = DeviceArray((n, h, w), np.uint16)
+    ds.get_depth_block_cu(0, depth)
+    truth = DeviceArray((n, h, w), np.uint16)
+    ds.get_labels_block_cu(0, truth)
+    out = DeviceArray((n, h // labels_reduce, w // labels_reduce), np.uint16).fill(MAX_UINT16)
+    ev.get_labels_forest(forest, depth, out, labels_reduce=labels_reduce)
+    scorer = LabelScorer(max(int(forest.num_classes), ds.num_classes()))
+    return scorer.add(out, truth, labels_reduce, per_image=True).result()
+
+
+def score_layered_model(config_filename, dataset_dir, num_images, labels_reduce=2, scale_factor=1.):
+    """Score a layered model -- what the app runs -- on `num_images` random images of a dataset: LayeredDecisionForest.run per
+    frame into one [N, H // r, W // r] array of composite labels, scored in one pass against the truth sampled at
+    (x * r, y * r).  The host comparison cannot do this: the shapes differ.  The dataset's ids must be the composite's."""
+    from .decision_tree import LayeredDecisionForest
+    from .device import DeviceArray
+    from .engine.buffer import GpuBuffer
+    from .score import LabelScorer
+    ds = DecisionTreeDatasetConfig(dataset_dir, num_images=num_images, imgs_name='test')
+    n, h, w = ds.images_shape()
+    layered = LayeredDecisionForest.load(config_filename, (h, w), labels_reduce)
+    hl, wl = layered.labels_dims
+    depth = DeviceArray((n, h, w), np.uint16)
+    ds.get_depth_block_cu(0, depth)
+    truth = DeviceArray((n, h, w), np.uint16)
+    ds.get_labels_block_cu(0, truth)
+    composite = DeviceArray((n, hl, wl), np.uint16)
+    depth_buf, labels_buf = GpuBuffer((h, w), dtype=np.uint16), GpuBuffer((hl, wl), dtype=np.uint16)
+    for i in range(n):
+        depth_buf.cu().copy_from(depth[i])
+        layered.run(depth_buf, labels_buf, scale_factor)
+        composite[i].copy_from(labels_buf.cu())
+    scorer = LabelScorer(max(layered.num_layered_classes + 1, ds.num_classes()))
+    return scorer.add(composite, truth, labels_reduce, per_image=True).result()
+
+
 def train_forest(dataset_dir, num_train, num_test, proposals, proposals_block, out_trees, max_depth, out_path=None,
-                 trees_to_try=None, train_block=None, log=print, tree_seed=None, group=None):
+                 trees_to_try=None, train_block=None, log=print, tree_seed=None, group=None, device_score=False):
     """The flow of src/train_model.py:52-139 without its GLFW window: train `trees_to_try` candidate trees, keep
     the `out_trees` best by test accuracy, evaluate the forest, save it as the reference's .npy.
 
@@ -173,7 +222,12 @@ def train_forest(dataset_dir, num_train, num_test, proposals, proposals_block, o
     instead of continuing the global stream.  That makes the candidates independent of each other, which is what
     lets them be trained on different GPUs: with torch.distributed initialised (one process per GPU), rank r trains
     candidates r, r + world, ...; the trees and their scores are exchanged with all_gather_object and every rank
-    keeps the same best ones -- the same forest, bit for bit, as one process with the same tree_seed."""
+    keeps the same best ones -- the same forest, bit for bit, as one process with the same tree_seed.
+
+    device_score (not in the reference): score every candidate and the forest with score.LabelScorer on the device instead
+    of reading the test set's label maps back for a numpy comparison; the truth is not copied to the host either.  The log
+    lines, the selection, the return value and the saved file are the same.  The forest's Score (confusion matrix, per-class
+    and per-image figures) is then kept as train_forest.last_score, None after a run without device_score."""
     from .decision_tree import DecisionForest, DecisionTree, DecisionTreeEvaluator, DecisionTreeTrainer
     from .device import DeviceArray
     from .util import MAX_UINT16
@@ -190,7 +244,12 @@ def train_forest(dataset_dir, num_train, num_test, proposals, proposals_block, o
     test_depth, test_labels = DeviceArray(test_data.images_shape(), np.uint16), DeviceArray(test_data.images_shape(), np.uint16)
     test_data.get_depth_block_cu(0, test_depth)
     test_data.get_labels_block_cu(0, test_labels)
-    truth = test_labels.get()
+    train_forest.last_score = None
+    if device_score:
+        from .score import LabelScorer
+        scorer = LabelScorer(test_data.num_classes())
+    else:
+        truth = test_labels.get()
     best = [None] * out_trees
     forest_cpu = np.zeros((out_trees, tree1.TOTAL_TREE_NODES, tree1.TREE_NODE_ELS), dtype=np.float32)
     rank, world = 0, 1
@@ -205,7 +264,10 @@ def train_forest(dataset_dir, num_train, num_test, proposals, proposals_block, o
         trainer.train(train_data, tree1)
         out_cu.fill(MAX_UINT16)
         evaluator.get_labels(tree1, test_depth, out_cu)
-        pct = float(np.sum(out_cu.get() == truth) / np.sum(truth > 0))
+        if device_score:
+            pct = scorer.reset().add(out_cu, test_labels).result().pct_matching
+        else:
+            pct = float(np.sum(out_cu.get() == truth) / np.sum(truth > 0))
         log(f'tree {i}: pct. matching pixels: {pct:.4f}')
         candidates[i] = (pct, tree1.tree_out_cu.get())
     if world > 1:
@@ -226,8 +288,15 @@ def train_forest(dataset_dir, num_train, num_test, proposals, proposals_block, o
     forest.forest_cu.set(forest_cpu)
     out_cu.fill(MAX_UINT16)
     evaluator.get_labels_forest(forest, test_depth, out_cu)
-    pct = float(np.sum(out_cu.get() == truth) / np.sum(truth > 0))
+    if device_score:
+        train_forest.last_score = scorer.reset().add(out_cu, test_labels, per_image=True).result()
+        pct = train_forest.last_score.pct_matching
+    else:
+        pct = float(np.sum(out_cu.get() == truth) / np.sum(truth > 0))
     log(f'FOREST pct. matching pixels: {pct:.4f}')
     if out_path:
         np.save(out_path, forest_cpu)
     return forest_cpu, pct
+
+
+train_forest.last_score = None

@@ -6,6 +6,8 @@
  * And the converter's augmentation: the centre of a frame's points (rdf_points_center) and the re-render of the moved
  * scene (rdf_rerender), a software rasteriser in place of the reference's OpenGL draw; those two are fp32 / fp64 with a
  * stated operation order, described with their declarations below.
+ * And the score of what was trained on those labels: predicted label maps against true ones as a confusion matrix
+ * (rdf_score_labels), integer like the colour kernels.
  *
  * It is a library of its own, next to librdf_hip.so and librdf_frontend.so, with its own ABI number and build id.
  * Conventions are those of rdf_hip.h: every pointer is caller-owned DEVICE memory; nothing is allocated, freed or
@@ -177,6 +179,33 @@ size_t rdf_rerender_workspace_bytes(int dim_x, int dim_y);
 int rdf_rerender(int dim_x, int dim_y, const float *pts, const uint8_t *color, const float *obj_tform_host, float f,
                  float ppx, float ppy, float zmin, float zmax, void *workspace, uint16_t *depth_out, uint8_t *color_out,
                  void *stream);
+
+/*
+ * Score predicted label maps against truth label maps: the confusion matrix and the two sums of the reference's `pct.
+ * matching pixels` (train_model.py:104-107, 131-135, test_on_saved_model.py: np.sum(got == truth) / np.sum(truth > 0)) in
+ * one pass, with nothing but the counts to read back.  tests/score_numpy.py restates it.
+ *   pred   uint16 [n_img][dim_y / r][dim_x / r], r = labels_reduce >= 1 (integer division, as the forest's label maps);
+ *   truth  uint16 [n_img][dim_y][dim_x], sampled at (x * r, y * r) for label pixel (x, y).
+ *   Both need 2-byte alignment only (callers pass image slices).
+ * With C = num_classes (1..RDF_SCORE_MAX_CLASSES), clamp(v) = min(v, C): index C stands for "none or unknown", which takes
+ * the 65535 pre-fill and every id the model does not have.  For every label pixel, with p and t the raw 16-bit values:
+ *   counts[clamp(t) * (C + 1) + clamp(p)] += 1          the confusion matrix, truth by prediction;
+ *   counts[(C + 1)^2 + 0] += (p == t)                   the reference's numerator, raw values: a (0, 0) pixel counts;
+ *   counts[(C + 1)^2 + 1] += (t > 0)                    the reference's denominator.
+ * counts uint64 [(C + 1)^2 + 2] (rdf_score_counts_bytes(C) bytes, 0 for a rejected C), 8-byte aligned: the call ADDS, the
+ * caller zeroes (as rdf_split_pixels_by_nearest_color).  The matrix cells of one call sum to n_img * (dim_y / r) * (dim_x / r):
+ * no pixel is dropped.  per_image (may be NULL) uint32 [n_img][2] = {equal, labelled} of each image, ADDS likewise.
+ * Rejected arguments leave counts untouched: C outside 1..64, r < 1, a negative dimension or a misaligned pointer is
+ * RDF_ERR_BAD_ARG; zero label pixels is a successful no-op; else a NULL pred, truth or counts is RDF_ERR_NULL_PTR and
+ * n_img * dim_y * dim_x >= 2^31 RDF_ERR_TOO_LARGE (callers split the batch by images).
+ * One launch.  Counts are summed in registers and in 32-bit LDS histograms (a workgroup sees < 2^31 pixels) and each
+ * workgroup adds its non-zero cells to counts once, with 64-bit integer atomics: the result does not depend on the order of
+ * arrival and is the same from run to run.
+ */
+#define RDF_SCORE_MAX_CLASSES 64
+size_t rdf_score_counts_bytes(int num_classes);
+int rdf_score_labels(int n_img, int dim_x, int dim_y, int labels_reduce, int num_classes, const uint16_t *pred,
+                     const uint16_t *truth, uint64_t *counts, uint32_t *per_image, void *stream);
 
 int rdf_labels_abi_version(void);
 const char *rdf_labels_build_id(void);
