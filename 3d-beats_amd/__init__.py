@@ -19,6 +19,8 @@ from .device import DeviceArray, HipRuntime, device_ptr, get_runtime, host_mappe
 from .engine.buffer import GpuBuffer  # noqa: F401
 from .frontend import FrameFrontEnd  # noqa: F401
 from .grouping import HandGrouping  # noqa: F401
+from .hand_model import HandModel  # noqa: F401
+from .hand_scene import HandSceneRenderer  # noqa: F401
 from .hand_state import HandState  # noqa: F401
 from .host_stream import HostFramesEvaluator  # noqa: F401
 from .pipeline import HandPipeline  # noqa: F401
@@ -54,6 +56,6 @@ def install_reference_aliases(force=False):
 
 
 __all__ = ["DecisionTree", "DecisionForest", "LayeredDecisionForest", "DecisionTreeEvaluator", "DecisionTreeTrainer",
-           "GpuBuffer", "CalibratedPlane", "ColorLabeler", "RecordingConverter", "SceneRerender", "LabelScorer", "Score", "FrameFrontEnd", "HandGrouping", "HandPipeline", "HandState", "BeatsSession", "HostFramesEvaluator",
+           "GpuBuffer", "CalibratedPlane", "ColorLabeler", "RecordingConverter", "SceneRerender", "HandModel", "HandSceneRenderer", "LabelScorer", "Score", "FrameFrontEnd", "HandGrouping", "HandPipeline", "HandState", "BeatsSession", "HostFramesEvaluator",
            "DeviceArray", "HipRuntime", "MAX_UINT16", "RdfError", "device_ptr", "get_runtime", "set_runtime",
            "to_device", "host_mapped_array", "library_path", "synth", "install_reference_aliases"]

@@ -184,6 +184,11 @@ BINDINGS = {
         "rdf_score_counts_bytes": (_c_size_t, [_c_int]),
         "rdf_score_labels": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                       _c_void_p]),
+        "rdf_hand_scene_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
+        "rdf_hand_scene_render": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p,
+                                           _c_int, _c_void_p, _c_void_p, _c_float, _c_float, _c_float, _c_float, _c_float,
+                                           ctypes.c_uint16, ctypes.c_uint32, ctypes.c_uint32, _c_int, _c_void_p, _c_void_p,
+                                           _c_void_p, _c_void_p]),
         "rdf_labels_abi_version": (_c_int, []),
         "rdf_labels_build_id": (ctypes.c_char_p, []),
         "rdf_labels_error_string": (ctypes.c_char_p, [_c_int]),

@@ -8,6 +8,8 @@
  * stated operation order, described with their declarations below.
  * And the score of what was trained on those labels: predicted label maps against true ones as a confusion matrix
  * (rdf_score_labels), integer like the colour kernels.
+ * And where those labels come from when there is no recording: frames of an articulated, labelled triangle mesh over a table
+ * plane (rdf_hand_scene_render), the re-render's rasteriser with many frames per call.
  *
  * It is a library of its own, next to librdf_hip.so and librdf_frontend.so, with its own ABI number and build id.
  * Conventions are those of rdf_hip.h: every pointer is caller-owned DEVICE memory; nothing is allocated, freed or
@@ -41,7 +43,7 @@ extern "C" {
 
 /*
  * 1: first version.  The number changes when something declared here is removed or re-typed; a pure addition (as
- * rdf_points_center and rdf_rerender were) keeps it, since every caller of the older entry points still links and runs.
+ * rdf_points_center, rdf_rerender and rdf_hand_scene_render were) keeps it, since every caller of the older entry points still links and runs.
  * Two builds with the same number are told apart by rdf_labels_build_id().
  */
 #define RDF_LABELS_ABI_VERSION 1
@@ -206,6 +208,64 @@ int rdf_rerender(int dim_x, int dim_y, const float *pts, const uint8_t *color, c
 size_t rdf_score_counts_bytes(int num_classes);
 int rdf_score_labels(int n_img, int dim_x, int dim_y, int labels_reduce, int num_classes, const uint16_t *pred,
                      const uint16_t *truth, uint64_t *counts, uint32_t *per_image, void *stream);
+
+/*
+ * Labelled depth frames of an articulated triangle mesh over a table plane, n_frames per call: the package's own source of
+ * training sets (hand_model.py, hand_scene.py) where the reference renders a rigged hand in Blender (datagen/).  The same
+ * software rasteriser as rdf_rerender with per-triangle labels in place of interpolated colours; tests/hand_scene_numpy.py
+ * restates the rules below and the kernels match it bit for bit.
+ *
+ *   verts float32 [n_verts][3], model space; vert_part int32 [n_verts]: the part each vertex belongs to;
+ *   tris int32 [n_tris][3]: vertex indices; tri_label uint16 [n_tris];
+ *   part_tforms float32 [n_frames][n_parts][12]: rows 0..2 of an affine 4x4, row-major, model space -> camera space;
+ *   table float32 [n_frames][4] = (nx, ny, nz, d), the plane n . P = d in camera space; NULL: no table;
+ *   f > 0, ppx, ppy, 0 < zmin <= zmax as for rdf_rerender; empty_depth: what a pixel that shows nothing gets, 0 for a raw
+ *   camera frame, 65535 for a dataset frame; seed, hole_threshold, noise_amp: rule H;
+ *   depth_out, labels_out uint16 [n_frames][dim_y][dim_x] (two different buffers): every pixel of both is written.
+ * Every pointer is device memory.  n_frames < 1, a negative count or dimension, f <= 0, an empty or non-finite depth range,
+ * noise_amp outside [0, 32767] or a misaligned pointer is RDF_ERR_BAD_ARG; dim_x or dim_y above 32768, or 2^39 pixels and
+ * more in the batch, RDF_ERR_TOO_LARGE; zero pixels is a successful no-op; else a NULL workspace or output, or with
+ * n_tris > 0 a NULL mesh array or part_tforms, is RDF_ERR_NULL_PTR.  Pixel indices are 64-bit.
+ *
+ * V. Vertex.  Vertex v of frame n is moved by M = part_tforms[n][vert_part[v]] exactly as rule 2 of rdf_rerender moves a
+ *    point: each row as ((m0 * x + m1 * y) + m2 * z) + m3 in fp32, every operation rounded, no fused multiply-add.  A
+ *    triangle with a vertex index outside [0, n_verts), or a vertex whose part is outside [0, n_parts), is dropped without
+ *    that index being followed; so is one with a vertex whose z' is not > 0.
+ * 3, 4. Projection, snapping to 1/256 pixel, the |X|, |Y| <= 2^20 drop, coverage with both windings and the top-left fill
+ *    rule, pixel (i, j) sampled at (256 i + 128, 256 j + 128): rules 3 and 4 of rdf_rerender, unchanged.
+ * 5. Depth.  Rule 5's z = ((w0 + w1) + w2) / ((w0 / z'0 + w1 / z'1) + w2 / z'2), discarded unless zmin <= z <= zmax.  Nothing
+ *    else is interpolated: the label of a fragment of triangle t is tri_label[t].
+ * 6. Depth test.  Rule 6 with the key (bits(z) << 32) | t, t the triangle's index in tris: nearest first, then the lowest
+ *    index.  Every frame has its own plane of keys.
+ * T. Table.  Where table is not NULL, pixel (i, j) of frame n looks along rx = ((i + 0.5f) - ppx) / f, ry = ((j + 0.5f) -
+ *    ppy) / f; t = (nx * rx + ny * ry) + nz; if t > 0 and zt = d / t lies within [zmin, zmax] the table is at depth zt there,
+ *    else there is no table at that pixel.  All fp32, in that order.  The pixel shows the mesh fragment that won rule 6 if
+ *    there is one and (there is no table there or z <= zt), else the table with label 0, else nothing.
+ * E. Stored values.  Depth is z (or zt) truncated to uint16, 65535 at most.  A pixel that shows nothing gets empty_depth
+ *    and label 0.
+ * H. Holes and noise, integer, from a counter-based hash: no generator state, so a pixel's value depends on nothing but
+ *    (seed, n, p) with p = j * dim_x + i (< 2^30).  All arithmetic is uint32, wrapping:
+ *        mix(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16;
+ *        hash  = mix(mix(seed + n * 0x9e3779b9) ^ p)          hash' = mix(hash ^ 0x85ebca6b)
+ *    (frame n under seed s is frame 0 under seed s + n * 0x9e3779b9: a batch can be split into calls).  Only a pixel that
+ *    shows mesh or table is touched.  If hole_threshold != 0 and hash < hole_threshold it shows nothing instead
+ *    (empty_depth, label 0).  Else, if noise_amp > 0, its stored depth d becomes d + (hash' % (2 * noise_amp + 1)) -
+ *    noise_amp, clamped to [1, 65534].  With both zero the image is the clean render.
+ *
+ * workspace: rdf_hand_scene_workspace_bytes(n_frames, dim_x, dim_y) bytes (one key per pixel and frame; 0 for rejected
+ * arguments), 8-byte aligned.  EVERY BYTE MUST BE 0xFF BEFORE THE FIRST CALL; each call leaves it so.  A workspace for more
+ * frames serves a call with fewer.  Two launches, neither of which waits for another workgroup: eight lanes per (frame,
+ * triangle) move its three vertices, share the rows of its bounding box clipped to the frame and take the 64-bit atomic
+ * minimum per covered pixel; one lane per pixel then reads z and the triangle out of the key itself, applies rules T, E and H, writes
+ * both images and resets the key.  As for rdf_rerender the first launch costs time in proportion to the summed bounding
+ * boxes, which is why the table is analytic and not two frame-sized triangles.
+ */
+size_t rdf_hand_scene_workspace_bytes(int n_frames, int dim_x, int dim_y);
+int rdf_hand_scene_render(int n_frames, int dim_x, int dim_y, int n_verts, const float *verts, const int32_t *vert_part,
+                          int n_tris, const int32_t *tris, const uint16_t *tri_label, int n_parts, const float *part_tforms,
+                          const float *table, float f, float ppx, float ppy, float zmin, float zmax, uint16_t empty_depth,
+                          uint32_t seed, uint32_t hole_threshold, int noise_amp, void *workspace, uint16_t *depth_out,
+                          uint16_t *labels_out, void *stream);
 
 int rdf_labels_abi_version(void);
 const char *rdf_labels_build_id(void);
