@@ -125,6 +125,7 @@ SIGNATURES = {
     "rdf_set_last_level_table": (None, [_c_int]),
     "rdf_set_deep_from": (None, [_c_int]),
     "rdf_set_fold": (None, [_c_int]),
+    "rdf_set_plain_levels": (None, [_c_int]),
     "rdf_event_create": (_c_int, [ctypes.POINTER(_c_void_p)]),
     "rdf_event_record": (_c_int, [_c_void_p, _c_void_p]),
     "rdf_event_synchronize": (_c_int, [_c_void_p]),

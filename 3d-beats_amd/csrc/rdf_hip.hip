@@ -229,6 +229,7 @@ struct EvalArgs {
     int check_empty;       // look at a tile's centre depths before staging it (throughput shape)
     int keep_if_no_leaf;   // single-tree semantics: no leaf reached -> pixel untouched
     int fill_untouched;    // fused pre-fill: write 65535 to every label pixel that is not evaluated
+    int plain_levels;      // the level loop may start on its plain path (g_plain_levels); 0: the general loop from level 0
     float s;
     // (round 6) the packed table's info block, the generation the host believes the table at this address has, and where a
     // kernel that finds another one says so (pinned host memory, one word per device): see PackInfo.generation
@@ -353,6 +354,19 @@ __device__ __forceinline__ uint32_t walk_step(uint32_t h, int g, uint32_t w2, ui
     return next;
 }
 
+// The same step on a plain level (k_eval_forest, "plain levels"): the slot is walking and neither side of the node is a
+// leaf, so next = 2 h + side and nothing else -- the compare and the add with carry-in, which share vcc.
+__device__ __forceinline__ uint32_t walk_step_plain(uint32_t h, int g, uint32_t w2)
+{
+    uint32_t next;
+    asm("v_cmp_ge_i32_sdwa vcc, sext(%1), sext(%2) src0_sel:WORD_1 src1_sel:BYTE_0\n\t"
+        "v_addc_co_u32_e32 %0, vcc, %3, %3, vcc"
+        : "=v"(next)
+        : "v"(g), "v"(w2), "v"(h)
+        : "vcc");
+    return next;
+}
+
 // Every wave owns a.rows_per_wave label rows of the tile (up to kMaxRowsPerWave in the throughput shape, one for small
 // launches such as one live frame).
 // NL > 1 ("layers in one launch", small launches of a layered stack): workgroup b evaluates forest b % NL of the kernel's
@@ -381,6 +395,11 @@ struct EvalArgsN {
 //                         because the wave fetches its deep blocks together), the pixel's reciprocal, then per CMAX classes and per GROUP trees:
 //       the level loop    round-down mode; node fetch (LDS / packed table / reference records) -> probe coordinates (one fma per
 //                         coordinate, or the IEEE divide for flagged nodes) -> probes issued -> decisions (walk_step)
+//                         "plain levels" (kPlainLevels: the packed 512-thread four-class four-tree kernel without a pixel list,
+//                         the bench batch's; EvalArgs.plain_levels): a first loop of the same steps for the levels on which every
+//                         tree slot of the wave walks and no node has a leaf or exact flag -- no slot test, no node 0 for
+//                         finished slots, no leaf bit, no select (walk_step_plain); the general loop takes over for good at
+//                         the first level that is not plain
 //       then ONE of       "deep blocks" (DEEP: tree after tree, the WAVE fetches its lanes' 128-byte blocks with eight LDS-DMA loads into
 //                         its 8-KB slab, every lane reads the three records it takes; leaf PDFs with the last block)
 //                         "level D-1 from the last-level table" (node and both PDFs in one 64-byte record, tree after tree)
@@ -431,6 +450,10 @@ __global__ __launch_bounds__(BLOCK, TW ? 8 : DEEP ? 4 : BLOCK == 512 ? 6 : BLOCK
     const uint32_t lds_pitch = 1u << K;   // records per tree in LDS
     // (LastLevelRec) level D-1 is walked from the last-level table when the forest has a usable one
     constexpr bool kLastLevelTable = PACKED && CMAX == 4 && !TW;
+    // (plain levels) which instantiations carry the second, leaner level loop (see the level loop).  One: the loop costs
+    // 4.5 KB of code object per kernel and the library has 11 KB left under its limit (tests/test_abi.py).  The other packed
+    // kernels, the reference-layout, visit-counter, tree-wave and deep-block ones keep the general loop alone.
+    constexpr bool kPlainLevels = PACKED && !STATS && !TW && !DEEP && NL == 1 && BLOCK == 512 && CMAX == 4 && GROUP == 4 && !COMPACT;
     bool last_from_table = false;
     if (kLastLevelTable && a.last_level) {
         // the trailer's words: every record usable, and the forest uses at least a.last_level_min of its deepest nodes (a
@@ -925,7 +948,58 @@ __global__ __launch_bounds__(BLOCK, TW ? 8 : DEEP ? 4 : BLOCK == 512 ? 6 : BLOCK
                     const bool fast_levels = PACKED || K > 0;
                     if (fast_levels) set_round_down(rcp_s);
 
-                    for (int j = 0; j < walk_levels; ++j) {
+                    // (plain levels) While every tree slot of every active lane is walking and no fetched record carries a leaf or
+                    // exact flag, a level needs no bookkeeping: the slot test, the max that points finished slots at node 0, the
+                    // leaf bit and the select of the decision all compute what is known (walk_step_plain).  That state holds at
+                    // level 0 for a full group of live lanes, and a plain level cannot end a walk, so it is not tested again: the
+                    // plain levels end -- for good -- at the first level whose flags say otherwise, which the general loop below
+                    // walks again from its fetch (an LDS or L1 hit, once per walk; nothing but h[] crosses over: a level handed
+                    // over half-way kept its records live across both loops and spilled).
+                    int j = 0;
+                    if constexpr (kPlainLevels) {
+                        if (a.plain_levels != 0 && kb + GROUP <= a.T && !__any(!live)) {       // wave-uniform
+                            for (; j < walk_levels; ++j) {
+                                Node n[GROUP];
+                                if (j < K) {
+#pragma unroll
+                                    for (int k = 0; k < GROUP; ++k) {
+                                        const uint32_t tk = (uint32_t)min(kb + k, a.T - 1);   // (= kb + k; the general loop's expression: one base for both)
+                                        n[k] = decode_node(lds_nodes[tk * lds_pitch + h[k]]);
+                                    }
+                                } else {
+#pragma unroll
+                                    for (int k = 0; k < GROUP; ++k) {
+                                        const int tk = min(kb + k, a.T - 1);
+                                        const char *base = reinterpret_cast<const char *>(a.packed16 + ((size_t)tk << a.D));
+                                        n[k] = decode_node(*reinterpret_cast<const uint4 *>(base + h[k] * 16u));
+                                    }
+                                }
+                                uint32_t fl = 0u;
+#pragma unroll
+                                for (int k = 0; k < GROUP; ++k) fl |= n[k].flags;
+                                if (__any((fl & (kFlagLeftLeaf | kFlagRightLeaf | kFlagExact)) != 0u)) break;
+                                TileProbe qu[GROUP], qv[GROUP];
+#pragma unroll
+                                for (int k = 0; k < GROUP; ++k) {
+                                    const f2 nu = {n[k].ax, n[k].ay};
+                                    const f2 nv = {n[k].bx, n[k].by};
+                                    const f2 r2 = {rcp_s, rcp_s};
+                                    const f2 m2 = {kMagic, kMagic};
+                                    const f2 tu = __builtin_elementwise_fma(nu, r2, m2);
+                                    const f2 tv = __builtin_elementwise_fma(nv, r2, m2);
+                                    qu[k] = tprobe_issue(pc, (__float_as_uint(tu.x) << 1) + kx2, __float_as_uint(tu.y) + ky);
+                                    qv[k] = tprobe_issue(pc, (__float_as_uint(tv.x) << 1) + kx2, __float_as_uint(tv.y) + ky);
+                                }
+#pragma unroll
+                                for (int k = 0; k < GROUP; ++k) {
+                                    const int g = tprobe_value(qu[k]) - tprobe_value(qv[k]) - (int)n[k].lo16;
+                                    h[k] = walk_step_plain(h[k], g, n[k].w2);
+                                }
+                            }
+                        }
+                    }
+
+                    for (; j < walk_levels; ++j) {
                         bool any = false;
 #pragma unroll
                         for (int k = 0; k < GROUP; ++k) any |= (int)h[k] > 0;
@@ -1655,6 +1729,7 @@ Knob g_tree_waves{-1, "RDF_TREE_WAVES"};                // unset: on
 Knob g_stage_vec{-1, "RDF_STAGE_VEC"};                  // unset: on
 Knob g_layers_one_launch{-1, "RDF_LAYERS_ONE_LAUNCH"};  // unset/1: small packed layered runs evaluate their layers in one launch; 0: never
 Knob g_fold{-1, "RDF_FOLD"};                            // unset/1: narrow tiles for a label map's last <= 32 columns (EvalArgs.fold); 0: never
+Knob g_plain_levels{-1, "RDF_PLAIN_LEVELS"};            // unset/1: the level loop starts on its plain path where it can (EvalArgs.plain_levels); 0: never
 Knob g_deep_from{-1, "RDF_DEEP_FROM"};                  // unset: the table's own choice (choose_geometry); 0: never; > 0: from this level on (rounded up to a block root)
 Knob g_last_level_table{-1, "RDF_LAST_LEVEL_TABLE"};    // unset: level D-1 from the last-level table when it is usable and the forest uses half of that level; 1: whenever usable; 0: never
 
@@ -2381,6 +2456,7 @@ int plan_launch(DeviceState *&dsp, const Request &q, Plan *plan)
     if (g.n_tiles >= (1ll << 31)) return RDF_ERR_TOO_LARGE;
     a.fold = g.fold; a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y; a.tiles_y_n = g.tiles_y_n;
     a.n_tiles = (uint32_t)g.n_tiles; a.rows_per_wave = g.rpw;
+    a.plain_levels = g_plain_levels.get(1) != 0;
     // the empty-tile check (see the kernel): always on launches that fill the chip; on small launches only at labels_reduce > 1,
     // where a staged tile covers r x r times the image per label pixel and a live frame is mostly background (config 3's
     // two-layer frame 30.5 -> 29.2 us; at labels_reduce 1 the extra round trip costs more than the skipped staging saves:
@@ -2910,6 +2986,7 @@ void rdf_set_force_exact(int on) { g_force_exact.value = on; }
 void rdf_set_last_level_table(int on) { g_last_level_table.value = on; }
 void rdf_set_deep_from(int level) { g_deep_from.value = level; }
 void rdf_set_fold(int on) { g_fold.value = on; }
+void rdf_set_plain_levels(int on) { g_plain_levels.value = on; }
 
 int rdf_stream_create_with_reserved_cus(void **stream, int n_reserved)
 {

@@ -579,6 +579,10 @@ void rdf_set_deep_from(int level);       /* packed forests of up to eight classe
 void rdf_set_fold(int on);               /* a label map whose width leaves at most 32 columns beyond a multiple of 64 (848 = 13 x 64 + 16)
                                             gets narrow tiles for them, in which a wave covers 2 rows x 32 or 4 rows x 16 pixels,
                                             instead of a tile column whose waves run mostly empty: 1/-1 (default) on, 0 off */
+void rdf_set_plain_levels(int on);       /* the packed 512-thread kernels walk the levels on which every tree slot of a wave is still
+                                            walking and no node has a leaf side (the top levels of a trained forest, every level of a
+                                            full one) in a leaner loop without leaf and finished-slot bookkeeping: 1/-1 (default) on,
+                                            0 = the general loop from level 0.  Same labels either way (RDF_PLAIN_LEVELS). */
 /* hipEvent timing on the caller's stream (bench.py times the stream the kernels run on). */
 int rdf_event_create(void **event);
 int rdf_event_record(void *event, void *stream);
