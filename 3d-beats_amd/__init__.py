@@ -24,6 +24,7 @@ from .hand_scene import HandSceneRenderer  # noqa: F401
 from .hand_state import HandState  # noqa: F401
 from .host_stream import HostFramesEvaluator  # noqa: F401
 from .pipeline import HandPipeline  # noqa: F401
+from .pose_fit import PoseFitter  # noqa: F401
 from .rerender import SceneRerender  # noqa: F401
 from .score import LabelScorer, Score  # noqa: F401
 from .session import BeatsSession  # noqa: F401
@@ -56,6 +57,6 @@ def install_reference_aliases(force=False):
 
 
 __all__ = ["DecisionTree", "DecisionForest", "LayeredDecisionForest", "DecisionTreeEvaluator", "DecisionTreeTrainer",
-           "GpuBuffer", "CalibratedPlane", "ColorLabeler", "RecordingConverter", "SceneRerender", "HandModel", "HandSceneRenderer", "LabelScorer", "Score", "FrameFrontEnd", "HandGrouping", "HandPipeline", "HandState", "BeatsSession", "HostFramesEvaluator",
+           "GpuBuffer", "CalibratedPlane", "ColorLabeler", "RecordingConverter", "SceneRerender", "HandModel", "HandSceneRenderer", "PoseFitter", "LabelScorer", "Score", "FrameFrontEnd", "HandGrouping", "HandPipeline", "HandState", "BeatsSession", "HostFramesEvaluator",
            "DeviceArray", "HipRuntime", "MAX_UINT16", "RdfError", "device_ptr", "get_runtime", "set_runtime",
            "to_device", "host_mapped_array", "library_path", "synth", "install_reference_aliases"]

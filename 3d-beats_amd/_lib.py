@@ -190,6 +190,14 @@ BINDINGS = {
                                            _c_int, _c_void_p, _c_void_p, _c_float, _c_float, _c_float, _c_float, _c_float,
                                            ctypes.c_uint16, ctypes.c_uint32, ctypes.c_uint32, _c_int, _c_void_p, _c_void_p,
                                            _c_void_p, _c_void_p]),
+        "rdf_pose_cost": (_c_int, [_c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_void_p,
+                                   _c_void_p, ctypes.c_uint64, _c_void_p, _c_void_p]),
+        "rdf_pose_propose": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+        "rdf_pose_select": (_c_int, [_c_int, _c_void_p, _c_void_p, ctypes.c_uint32, ctypes.c_uint32, _c_int, _c_void_p, _c_void_p,
+                                     _c_void_p]),
+        "rdf_pose_fit_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
+        "rdf_pose_fit": (_c_int, [_c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_int,
+                                  _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
         "rdf_labels_abi_version": (_c_int, []),
         "rdf_labels_build_id": (ctypes.c_char_p, []),
         "rdf_labels_error_string": (ctypes.c_char_p, [_c_int]),

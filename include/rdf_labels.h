@@ -10,6 +10,8 @@
  * (rdf_score_labels), integer like the colour kernels.
  * And where those labels come from when there is no recording: frames of an articulated, labelled triangle mesh over a table
  * plane (rdf_hand_scene_render), the re-render's rasteriser with many frames per call.
+ * And the way back from a labelled depth frame to the hand's pose (rdf_pose_fit): candidates proposed, drawn, priced and
+ * selected on the device, the reference's pose_fit.py and cuda/fit_mesh.cu.
  *
  * It is a library of its own, next to librdf_hip.so and librdf_frontend.so, with its own ABI number and build id.
  * Conventions are those of rdf_hip.h: every pointer is caller-owned DEVICE memory; nothing is allocated, freed or
@@ -43,7 +45,8 @@ extern "C" {
 
 /*
  * 1: first version.  The number changes when something declared here is removed or re-typed; a pure addition (as
- * rdf_points_center, rdf_rerender and rdf_hand_scene_render were) keeps it, since every caller of the older entry points still links and runs.
+ * rdf_points_center, rdf_rerender, rdf_hand_scene_render and the pose fit -- rdf_pose_cost, rdf_pose_propose, rdf_pose_select,
+ * rdf_pose_fit_workspace_bytes and rdf_pose_fit -- were) keeps it, since every caller of the older entry points still links and runs.
  * Two builds with the same number are told apart by rdf_labels_build_id().
  */
 #define RDF_LABELS_ABI_VERSION 1
@@ -266,6 +269,136 @@ int rdf_hand_scene_render(int n_frames, int dim_x, int dim_y, int n_verts, const
                           const float *table, float f, float ppx, float ppy, float zmin, float zmax, uint16_t empty_depth,
                           uint32_t seed, uint32_t hole_threshold, int noise_amp, void *workspace, uint16_t *depth_out,
                           uint16_t *labels_out, void *stream);
+
+/*
+ * The pose fit: the hand of hand_model.py fitted to an observed depth frame and its forest labels, on the device.  The
+ * reference's pose_fit.py with cuda/fit_mesh.cu (calc_image_cost) renders one candidate cylinder per GUI frame through
+ * OpenGL, prices it against the frame and keeps a random perturbation whenever the price drops.  Here a generation is K
+ * candidate poses of the whole hand: proposed (rules P and K), drawn by rdf_hand_scene_render, priced (rule C) and selected
+ * (rule S) in five launches with nothing read back; tests/pose_fit_numpy.py restates the rules and the kernels match it bit
+ * for bit.  A pose is the float64 [26] of hand_model.py: wrist x, y, z; yaw, pitch, roll; per finger (thumb to pinky) a
+ * spread and three flexions.
+ *
+ * C. The cost of a candidate (rdf_pose_cost).  depth uint16 [dim_y][dim_x] and labels uint16 [Hl][Wl], Hl = dim_y / r,
+ *    Wl = dim_x / r, r = labels_reduce >= 1, are the observed frame; the observed label of depth pixel (x, y) is
+ *    labels[min(y / r, Hl - 1)][min(x / r, Wl - 1)].  The window (x0, y0, ww, wh), ww, wh >= 1, lies inside the frame.
+ *    cand_depth, cand_labels uint16 [K][wh][ww] are the K candidates as rendered at window size: rendered pixel (i, j) sits
+ *    over observed pixel (x0 + i, y0 + j), and a rendered depth of 0 means that nothing is drawn there.  An observed label l
+ *    is "hand" iff l < 64 and bit l of target_mask is set.  Per pixel, d0 and l0 observed, d1 and l1 rendered:
+ *      d0 == 0                    nothing: missing data is free (fit_mesh.cu:30);
+ *      hand(l0) and d1 == 0       missing += 1;
+ *      not hand(l0) and d1 != 0   extra += 1 (the reference's second test falls through to a third that cannot hold);
+ *      hand(l0) and d1 != 0       sq += (d0 - d1)^2 and, if l1 != l0, label += 1.
+ *    terms uint64 [K][4] = {missing, extra, label, sq}, 8-byte aligned: the call ADDS, the caller zeroes (as
+ *    rdf_score_labels).  Every sum is an integer: the result does not depend on the order of arrival.
+ *    cost = w_boundary * (missing + extra) + w_label * label + sq in uint64 (weights are uint32; it cannot wrap for a window
+ *    of fewer than 2^28 pixels).  With w_label = 0 and one bit in the mask, cost(w_boundary = 10000) is 100 times the
+ *    reference's float 100 * mismatches + 0.01 * diff^2, whose own float32 atomic sum depends on arrival order.
+ *    One launch, (chunks of the window) x K workgroups: a candidate's image is one contiguous run, read eight pixels per
+ *    16-byte load between its first and last 16-byte boundary, one pixel per lane outside; the observed pixels under them
+ *    are re-read from cache by all K candidates.  Counters are 32-bit and sq 64-bit in registers, summed per wave, then
+ *    per workgroup in LDS; a workgroup adds its non-zero sums to terms once, with 64-bit integer atomics.
+ *    K outside 1..RDF_POSE_MAX_CANDIDATES, r < 1, a negative dimension, an empty window or one that leaves the frame, or a
+ *    misaligned pointer is RDF_ERR_BAD_ARG; else a NULL pointer RDF_ERR_NULL_PTR; dim_x or dim_y above 32768
+ *    RDF_ERR_TOO_LARGE.  Rejected arguments leave terms untouched.
+ *
+ * The fit's device state (RdfPoseFitState, 256 bytes, 8-byte aligned) holds the incumbent pose, its cost and terms, the
+ * generation counter g and the number of accepted candidates.  What does not change during a fit is an RdfPoseFitConfig in
+ * HOST memory, read during the call (as rdf_rerender reads its matrix): it is checked on the host and handed to the kernels
+ * by value.  sigma >= 0, lo <= hi, all finite; every angle's range (pose numbers 3..25) lies within [-pi, pi], pi the
+ * nearest double; cam_from_plane: rows 0..2 of the affine plane space -> camera space matrix, row-major (the inverse of the
+ * table plane's matrix); geometry [5][6]: per finger its base x, base y (depth units), rest splay (radians) and three
+ * phalanx lengths (depth units); f, ppx, ppy, zmin, zmax as for rdf_hand_scene_render, of the whole frame; anneal_every >= 1.
+ * Anything else is RDF_ERR_BAD_ARG.
+ *
+ * P. Proposals (rdf_pose_propose).  With mix of rule H, all hashing uint32 and wrapping, candidate k of generation g:
+ *      h = mix(mix(seed + g * 0x9e3779b9) ^ k);  group = h & 7:  0 wrist x, y, z;  1 yaw, pitch, roll;  2..6 one finger's
+ *      spread and three flexions, thumb to pinky;  7 all 26.  For pose number j of the group:
+ *      a = mix(h ^ ((2 j + 1) * 0x85ebca6b)),  b = mix(a ^ 0xc2b2ae35),
+ *      n = (double)((a & 0xffff) + (a >> 16) + (b & 0xffff) + (b >> 16) - 131070) / 65536       exact, within (-2, 2),
+ *      scale = 2^-min(g / anneal_every, 1022)                                                      integer division,
+ *      v = inc[j] + (sigma[j] * scale) * n;   p[j] = v < lo[j] ? lo[j] : v > hi[j] ? hi[j] : v
+ *    where inc is the incumbent; every operation is one rounded fp64 operation.  Numbers outside the group are copied.
+ *    fresh_first != 0 marks the first generation of a fresh fit: it is generation 0 whatever g the state holds, and its
+ *    candidate 0 is the incumbent itself, unperturbed and unclamped, which prices the starting pose against a new frame.
+ *    poses float64 [K][26] receives the candidates; terms (may be NULL) uint64 [K][4] is zeroed by the same launch.
+ * K. Kinematics, in the same launch: part_tforms float32 [K][16][12] of the candidates, what rdf_hand_scene_render takes.
+ *    An affine matrix is 12 doubles, rows 0..2 row-major.  The product C = A B is, for every row i and column j,
+ *      C[i][j] = (A[i][0] * B[0][j] + A[i][1] * B[1][j]) + A[i][2] * B[2][j],   + A[i][3] after that for j = 3,
+ *    with every entry taking part, zeros included.  T(v) is the shift by v; Rx(a), Ry(a), Rz(a) are the rotations of
+ *    hand_model.py, e.g. Rz(a) = [c -s 0; s c 0; 0 0 1] with (s, c) = sincos(a) below.
+ *      B = cam_from_plane (((T(p[0..2]) Rz(p[3])) Rx(p[4])) Ry(p[5]))           the palm, part 0, is B itself;
+ *      finger f: M = T(base x, base y, 0) Rz(rest splay + p[6 + 4 f]);  phalanx 0: M = M Rx(-p[7 + 4 f]);  phalanx q = 1, 2:
+ *      M = (M T(0, length[q - 1], 0)) Rx(-p[7 + 4 f + q]);  part 1 + 3 f + q is B M', M' = M, or with `mirrored` M with the
+ *      entries [0][1], [0][2], [1][0], [2][0] and [0][3] negated (the conjugate by diag(-1, 1, 1)).
+ *    All in fp64, each entry cast to fp32 once (round to nearest even).
+ *    sincos(x), no library call: if not |x| <= 2^20 both are NaN; else k = rint(x * 0x1.45f306dc9c883p-1) (ties to even),
+ *      r = (x - k * 0x1.921fb544p+0) - k * 0x1.0b4611a626331p-34,  z = r * r,
+ *      S = r + (r * z) * (S1 + z * (S2 + z * (S3 + z * (S4 + z * (S5 + z * S6))))),
+ *      C = 1 + z * (-0.5 + z * (C1 + z * (C2 + z * (C3 + z * (C4 + z * (C5 + z * C6)))))),
+ *      (sin, cos) = (S, C), (C, -S), (-S, -C), (-C, S) for k mod 4 = 0, 1, 2, 3 (k as a two's complement integer);
+ *      S1..S6 = -0x1.5555555555549p-3, 0x1.111111110f8a6p-7, -0x1.a01a019c161d5p-13, 0x1.71de357b1fe7dp-19,
+ *               -0x1.ae5e68a2b9cebp-26, 0x1.5d93a5acfd57cp-33;
+ *      C1..C6 = 0x1.555555555554cp-5, -0x1.6c16c16c15177p-10, 0x1.a01a019cb159p-16, -0x1.27e4f809c52adp-22,
+ *               0x1.1ee9ebdb4b1c4p-29, -0x1.8fae9be8838d4p-37    (the coefficients of fdlibm's kernels on [-pi/4, pi/4]).
+ *    Every step is one rounded fp64 operation; the library is built without contraction.
+ * S. Selection (rdf_pose_select, one wave).  cost_k from terms[k] as in rule C; the best candidate has the lowest cost and
+ *    the lowest k among equals.  It replaces the incumbent (pose, cost, terms) iff its cost is strictly lower than the
+ *    incumbent's, or unconditionally when fresh_first != 0.  Then g += 1 and accepted += 1 on a replacement; with
+ *    fresh_first != 0 they become g = 1, accepted = 1: a fresh fit counts from its own start.  The incumbent's cost after
+ *    that is stored to *history_slot when that is not NULL.
+ *
+ * rdf_pose_fit enqueues `generations` generations on the stream: propose (which zeroes the terms), rdf_hand_scene_render of
+ * the K candidates at window size with intrinsics (f, ppx - x0, ppy - y0) in fp32, no table, empty_depth 0, no holes, no
+ * noise, then cost, then select; fresh != 0 makes the first of them a fresh first generation.  history (may be NULL) uint64
+ * [generations] receives the incumbent's cost after each.  No host read, no synchronisation, no allocation.  Because g
+ * lives in the state, a fit of a generations followed by one of b with fresh == 0 is a fit of a + b.  depth, labels: the
+ * observed frame of rule C; the mesh arguments are rdf_hand_scene_render's, with 16 parts.
+ * workspace: rdf_pose_fit_workspace_bytes(K, ww, wh) bytes (0 for rejected arguments), 16-byte aligned: the renderer's key
+ * planes first (rdf_hand_scene_workspace_bytes(K, ww, wh) bytes, EVERY BYTE 0xFF BEFORE THE FIRST CALL, left so by every
+ * call; filling the whole workspace with 0xFF is fine), then the candidates' images, transforms, poses and terms.
+ * Rejected calls leave the state untouched: a negative generations or a config that breaks the rules above is
+ * RDF_ERR_BAD_ARG, as is a misaligned pointer or a window outside the frame; generations == 0 is a successful no-op; else a
+ * NULL pointer is RDF_ERR_NULL_PTR and a dimension above 32768 RDF_ERR_TOO_LARGE.
+ */
+#define RDF_POSE_SIZE 26
+#define RDF_POSE_MAX_CANDIDATES 4096
+
+typedef struct RdfPoseFitState {
+    double pose[RDF_POSE_SIZE];     /* the incumbent */
+    uint64_t cost;
+    uint64_t terms[4];              /* missing, extra, label, sq */
+    uint32_t generation;            /* g */
+    uint32_t accepted;
+} RdfPoseFitState;
+
+typedef struct RdfPoseFitConfig {
+    int32_t candidates;             /* K */
+    int32_t mirrored;
+    int32_t anneal_every;
+    uint32_t seed;
+    int32_t x0, y0, ww, wh;         /* the window */
+    uint32_t w_boundary, w_label;
+    uint64_t target_mask;
+    float f, ppx, ppy, zmin, zmax;
+    float reserved;                 /* 0 */
+    double sigma[RDF_POSE_SIZE], lo[RDF_POSE_SIZE], hi[RDF_POSE_SIZE];
+    double cam_from_plane[12];
+    double geometry[30];
+} RdfPoseFitConfig;
+
+int rdf_pose_cost(int dim_x, int dim_y, const uint16_t *depth, const uint16_t *labels, int labels_reduce, int x0, int y0,
+                  int ww, int wh, int candidates, const uint16_t *cand_depth, const uint16_t *cand_labels,
+                  uint64_t target_mask, uint64_t *terms, void *stream);
+int rdf_pose_propose(const RdfPoseFitConfig *config_host, const RdfPoseFitState *state, int fresh_first, double *poses,
+                     float *part_tforms, uint64_t *terms, void *stream);
+int rdf_pose_select(int candidates, const uint64_t *terms, const double *poses, uint32_t w_boundary, uint32_t w_label,
+                    int fresh_first, RdfPoseFitState *state, uint64_t *history_slot, void *stream);
+size_t rdf_pose_fit_workspace_bytes(int candidates, int ww, int wh);
+int rdf_pose_fit(int generations, int fresh, const RdfPoseFitConfig *config_host, RdfPoseFitState *state, int dim_x,
+                 int dim_y, const uint16_t *depth, const uint16_t *labels, int labels_reduce, int n_verts,
+                 const float *verts, const int32_t *vert_part, int n_tris, const int32_t *tris, const uint16_t *tri_label,
+                 void *workspace, uint64_t *history, void *stream);
 
 int rdf_labels_abi_version(void);
 const char *rdf_labels_build_id(void);
