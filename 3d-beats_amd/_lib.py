@@ -139,6 +139,15 @@ SIGNATURES = {
 
 ABI_VERSION = 5
 
+
+class StereoConfig(ctypes.Structure):
+    """RdfStereoConfig of include/rdf_labels.h, passed by value."""
+    _fields_ = [("fb16", ctypes.c_int32), ("fbp16", ctypes.c_int32), ("max_disparity", ctypes.c_int32),
+                ("dot_threshold", ctypes.c_uint32), ("pattern_seed", ctypes.c_uint32), ("ambient", ctypes.c_int32),
+                ("ir_noise_amp", ctypes.c_int32), ("census_margin", ctypes.c_int32), ("uniqueness", ctypes.c_int32),
+                ("lr_max", ctypes.c_int32), ("dq_min", ctypes.c_int32)]
+
+
 # library (a key of _build.LIBRARIES) -> (the ABI number this binding was written for, name -> (restype, argtypes) of every
 # symbol its header declares)
 BINDINGS = {
@@ -198,6 +207,10 @@ BINDINGS = {
         "rdf_pose_fit_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
         "rdf_pose_fit": (_c_int, [_c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_int,
                                   _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+        "rdf_stereo_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int, _c_int]),
+        "rdf_stereo_ir": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, StereoConfig, ctypes.c_uint32, _c_void_p, _c_void_p]),
+        "rdf_stereo_sense": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, StereoConfig, ctypes.c_uint32,
+                                      ctypes.c_uint16, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
         "rdf_labels_abi_version": (_c_int, []),
         "rdf_labels_build_id": (ctypes.c_char_p, []),
         "rdf_labels_error_string": (ctypes.c_char_p, [_c_int]),

@@ -5,8 +5,9 @@ rigged hand in Blender for this (datagen/) and ships no recordings.
 `HandSceneRenderer.render` draws a batch of poses -- one hand (16 parts) or two (32: a right hand, then its mirror image) --
 into device depth and label images, two launches per chunk of `max_frames` on the current stream, nothing read back.
 `make_dataset` writes a directory that DecisionTreeDatasetConfig, train_forest and score_saved_model read as any other;
-`camera_sequence` gives raw frames with the table under the hand, the input of BeatsSession.run_sequence.  The rasteriser's
-rules are in include/rdf_labels.h.
+`camera_sequence` gives raw frames with the table under the hand, the input of BeatsSession.run_sequence.  With `sensor=` (a
+StereoSensor) all three draw a clean left and a clean right frame and report what the stereo camera makes of them, in place of
+rule H's holes and noise.  The rasteriser's rules are in include/rdf_labels.h.
 """
 import numpy as np
 
@@ -86,12 +87,18 @@ class HandSceneRenderer:
         return np.ascontiguousarray(np.concatenate([t, left], 1))
 
     def render(self, part_tforms, labels='fine', table=None, empty_depth=65535, seed=0, hole_rate=0., noise_amp=0,
-               depth_out=None, labels_out=None):
+               depth_out=None, labels_out=None, sensor=None):
         """part_tforms: host float32 [N, 16, 12] (one hand) or [N, 32, 12] (two).  labels: see tri_labels.  table: None, or
         (nx, ny, nz, d) in camera space as [4] or [N, 4].  empty_depth: 65535 for dataset frames, 0 for raw camera frames.
         hole_rate: the share of drawn pixels dropped (threshold hole_rate * 2^32 of rule H); noise_amp: depth units.
+        sensor: a StereoSensor of this frame size; the clean frame and the same scene from a camera moved by the sensor's
+        baseline along +x go through sensor.sense (seed is then the IR noise's), which replaces rule H: hole_rate and
+        noise_amp must be zero.
         Returns device (depth uint16 [N, H, W], labels uint16 [N, H, W]); every pixel of both is written.  Frame n of a
         long batch gets the same image whatever max_frames is."""
+        if sensor is not None:
+            return self._render_through(sensor, part_tforms, labels, table, empty_depth, seed, hole_rate, noise_amp, depth_out,
+                                        labels_out)
         t = np.ascontiguousarray(part_tforms, np.float32)
         assert t.ndim == 3 and t.shape[1] in self._mesh and t.shape[2] == 12, t.shape
         N, P = int(t.shape[0]), int(t.shape[1])
@@ -124,11 +131,29 @@ class HandSceneRenderer:
                 o.mark_dirty()
         return depth_out, labels_out
 
+    def _render_through(self, sensor, part_tforms, labels, table, empty_depth, seed, hole_rate, noise_amp, depth_out, labels_out):
+        if hole_rate or noise_amp:
+            raise ValueError("a sensor replaces holes and noise: hole_rate and noise_amp must be zero with sensor=")
+        assert (sensor.DIM_Y, sensor.DIM_X) == (self.DIM_Y, self.DIM_X), "the sensor is of another frame size"
+        t = np.ascontiguousarray(part_tforms, np.float32)
+        # the right camera sits at x = +B: every point's x is B less in its space.  float64, cast once
+        right = t.astype(np.float64)
+        right[:, :, 3] -= sensor.baseline
+        right_table = None
+        if table is not None:
+            right_table = np.asarray(table, np.float32).reshape(-1, 4).astype(np.float64)
+            right_table[:, 3] -= right_table[:, 0] * sensor.baseline
+            right_table = right_table.astype(np.float32)
+        depth_l, labels_l = self.render(t, labels, table, empty_depth)
+        depth_r, _ = self.render(right.astype(np.float32), labels, right_table, empty_depth)
+        return sensor.sense(depth_l, labels_l, depth_r, seed, empty_depth, depth_out, labels_out)
+
     def make_dataset(self, dataset_dir, num_images, seed, labels='fine', plane=None, two_hands=False, ranges=None,
-                     hole_rate=0., noise_amp=0):
+                     hole_rate=0., noise_amp=0, sensor=None):
         """Sample `num_images` poses from `seed` (HandModel.sample_poses), render them in dataset convention -- no table,
         background depth 65535, label 0 = none -- and write `dataset_dir` with dataset.write_dataset and the scheme's
-        id_to_color.  plane: the camera's table plane; default look_down_plane(550 mm).  Returns the host (depth, labels)."""
+        id_to_color.  plane: the camera's table plane; default look_down_plane(550 mm).  sensor: see render.  Returns the host
+        (depth, labels)."""
         rng = np.random.default_rng(seed)
         plane = look_down_plane(550. * self.model.units_per_mm) if plane is None else plane
         poses = self.model.sample_poses(num_images, rng, ranges)
@@ -139,13 +164,14 @@ class HandSceneRenderer:
             left = self.left_model.sample_poses(num_images, rng, ranges) - shift
             poses = poses + shift
         depth, lab = self.render(self.transforms(poses, plane, left), labels, None, 65535, int(seed) & 0xFFFFFFFF, hole_rate,
-                                 noise_amp)
+                                 noise_amp, sensor=sensor)
         depth, lab = depth.get(), lab.get()
         scheme = labels if isinstance(labels, str) else 'fine'
         write_dataset(dataset_dir, depth, lab, HandModel.id_to_color(scheme))
         return depth, lab
 
-    def camera_sequence(self, poses, plane, left_poses=None, hole_rate=0., noise_amp=0, seed=0, labels='fine', labels_out=None):
+    def camera_sequence(self, poses, plane, left_poses=None, hole_rate=0., noise_amp=0, seed=0, labels='fine', labels_out=None,
+                        sensor=None):
         """Raw camera frames of `poses` [N, 26] (and the left hand's `left_poses`) over the table of `plane`: the table is
         drawn, empty pixels and holes are 0 -- device uint16 [N, H, W], what BeatsSession.run_sequence takes.  The truth
         labels go to `labels_out` when given.
@@ -153,5 +179,5 @@ class HandSceneRenderer:
         sx = x.  A caller who wants the front end to deproject these frames onto the rendered geometry builds this object
         with (ppx + 0.5, ppy + 0.5)."""
         depth, _ = self.render(self.transforms(poses, plane, left_poses), labels, table_of_plane(plane), 0, seed, hole_rate,
-                               noise_amp, labels_out=labels_out)
+                               noise_amp, labels_out=labels_out, sensor=sensor)
         return depth

@@ -12,6 +12,8 @@
  * plane (rdf_hand_scene_render), the re-render's rasteriser with many frames per call.
  * And the way back from a labelled depth frame to the hand's pose (rdf_pose_fit): candidates proposed, drawn, priced and
  * selected on the device, the reference's pose_fit.py and cuda/fit_mesh.cu.
+ * And what a stereo depth camera makes of those frames (rdf_stereo_sense): a left and a right render through a projected dot
+ * pattern, a census transform and a block matcher, integer like the colour kernels.
  *
  * It is a library of its own, next to librdf_hip.so and librdf_frontend.so, with its own ABI number and build id.
  * Conventions are those of rdf_hip.h: every pointer is caller-owned DEVICE memory; nothing is allocated, freed or
@@ -46,7 +48,7 @@ extern "C" {
 /*
  * 1: first version.  The number changes when something declared here is removed or re-typed; a pure addition (as
  * rdf_points_center, rdf_rerender, rdf_hand_scene_render and the pose fit -- rdf_pose_cost, rdf_pose_propose, rdf_pose_select,
- * rdf_pose_fit_workspace_bytes and rdf_pose_fit -- were) keeps it, since every caller of the older entry points still links and runs.
+ * rdf_pose_fit_workspace_bytes and rdf_pose_fit -- and the stereo sensor's three were) keeps it, since every caller of the older entry points still links and runs.
  * Two builds with the same number are told apart by rdf_labels_build_id().
  */
 #define RDF_LABELS_ABI_VERSION 1
@@ -399,6 +401,79 @@ int rdf_pose_fit(int generations, int fresh, const RdfPoseFitConfig *config_host
                  int dim_y, const uint16_t *depth, const uint16_t *labels, int labels_reduce, int n_verts,
                  const float *verts, const int32_t *vert_part, int n_tris, const int32_t *tris, const uint16_t *tri_label,
                  void *workspace, uint64_t *history, void *stream);
+
+/*
+ * The stereo depth sensor: a clean left-camera render and a clean right-camera render of one scene become the depth frame
+ * an active stereo camera (a projected IR dot pattern, two IR imagers, a census block matcher) would report, n_frames per
+ * call.  It stands behind rdf_hand_scene_render in place of rule H: the holes and errors are those of matching -- a shadow
+ * of missing depth left of whatever stands in front of the table, foreground depth fattened round a silhouette, depth in
+ * steps that grow with Z^2, and no depth where there is no texture.  The reference's datagen/stereo_alg.py runs OpenCV's
+ * StereoSGBM on two Blender renders for this; nothing of that matcher is restated, the rules below are this library's own.
+ * Integer arithmetic throughout; tests/stereo_numpy.py restates the rules and the kernels match it bit for bit.
+ *
+ *   depth_l, labels_l, depth_r uint16 [n_frames][dim_y][dim_x]: the clean renders, depth_r from a camera moved by the
+ *   baseline along +x, labels_l the truth labels of the left frame.  A pixel shows a surface iff 0 < Z < 65535.
+ *   RdfStereoConfig, by value: fb16 = round(16 f B), fbp16 = round(16 f Bp), B the baseline and Bp the projector's offset
+ *   from the left imager, in depth units, 0 <= fbp16 <= fb16 < 2^31 - 2^15; 1 <= max_disparity (D below) <= 256;
+ *   0 <= ambient, ir_noise_amp, census_margin, lr_max <= 255; 0 <= uniqueness <= 100; 1 <= dq_min <= 65535.
+ *   All hashing is rule H's mix, uint32 and wrapping.  The frame is pixel p = y * dim_x + x of frame n.
+ *
+ * I. The two IR images.  Camera c (0 left, 1 right), with Z the depth that camera's render has at (x, y): if the pixel
+ *    shows a surface, s = -((fbp16 + Z / 2) / Z) for the left camera and s = +(((fb16 - fbp16) + Z / 2) / Z) for the right
+ *    (integer divisions), sq = 16 x + s, u = sq >> 4 (arithmetic) as a uint32, fr = sq & 15.  The projector's texel is
+ *      tex(u, y) = h < dot_threshold ? 64 + (h & 127) : 0,   h = mix(mix(pattern_seed + y * 0x9e3779b9) ^ u):
+ *    the pattern belongs to the projector, not to the frame.  The intensity is
+ *      I = ambient + (surface ? ((16 - fr) * tex(u, y) + fr * tex(u + 1, y)) >> 4 : 0) + noise,  clamped to [0, 255],
+ *      noise = (mix(mix(seed + n * 0x9e3779b9 + c * 0x632be5ab) ^ p) % (2 a + 1)) - a  for a = ir_noise_amp > 0, else 0
+ *    (frame n under seed s is frame 0 under seed s + n * 0x9e3779b9, as in rule H).
+ * N. Census.  Bit k of a pixel's 62-bit census, k counting from 0 over dy = -3..3 (outer) and dx = -4..4 (inner) without
+ *    the centre, is set iff I(x + dx, y + dy) > I(x, y) + census_margin; I outside the image is 0.  (With a margin of
+ *    about twice ir_noise_amp, noise alone sets no bit: an untextured surface has an all-zero census.)
+ * M. Cost.  ham(x, y, d) = popcount(censusL(x, y) ^ censusR(x - d, y)) where 0 <= x - d, 0 <= x < dim_x and 0 <= y < dim_y,
+ *    else 62.  C(x, y, d) is the sum of ham over the 5 x 5 box round (x, y), for any integer x (<= 1550).  Disparities are
+ *    0 <= d < D.  The right-referenced cost is C_R(xr, y, d) = C(xr + d, y, d): the box moves with the pixel.
+ * W. Winners and checks, per left pixel.  d* is the d of least C, the lowest among equals.  second is the least C over
+ *    |d - d*| >= 2; the pixel is unique iff there is no such d or C* * 100 < second * (100 - uniqueness).  dR(xr, y) is the
+ *    winner of C_R found the same way; the pixel passes the left-right check iff x - d* >= 0 and |dR(x - d*, y) - d*| <=
+ *    lr_max.  Sub-pixel, the equiangular fit: if 1 <= d* <= D - 2 and C* > 0, with cm = C(d* - 1), cp = C(d* + 1) and den =
+ *    max(cm - C*, cp - C*) > 0, sub = floor((16 * (cm - cp) + den) / (2 * den)) clamped to [-8, 8]; else sub = 0 (C* = 0 is an
+ *    exact match of all 25 windows: the disparity is whole, whatever the neighbours cost).  dq = 16 d* + sub.
+ *    The pixel is valid iff it is unique, passes the left-right check and dq >= dq_min.
+ * Z. Stored values.  A valid pixel gets depth = clamp((fb16 + dq / 2) / dq, 1, 65534) and the label labels_l(x, y); any
+ *    other pixel gets empty_depth and label 0, as in rule E.  Every pixel of depth_out and labels_out is written.
+ *
+ * Optional outputs, each may be NULL: ir_out uint8 [n_frames][2][dim_y][dim_x], the images of rule I; dq_out uint16
+ * [n_frames][dim_y][dim_x], dq of every pixel, valid or not; reason_out uint8 [n_frames][dim_y][dim_x]: 0 for a valid
+ * pixel, else bit 0 not unique, bit 1 left-right check failed, bit 2 dq < dq_min.  rdf_stereo_ir is rule I alone.
+ * n_frames < 1, a negative dimension, a config outside the ranges above or a misaligned pointer is RDF_ERR_BAD_ARG; dim_x or
+ * dim_y above 32768, or 2^39 pixels and more in the batch, RDF_ERR_TOO_LARGE; zero pixels is a successful no-op; else a
+ * NULL input, workspace, depth_out or labels_out (rdf_stereo_ir: ir_out) is RDF_ERR_NULL_PTR.  Rejected arguments leave
+ * the outputs untouched.  Pixel indices are 64-bit.
+ * workspace: rdf_stereo_workspace_bytes(n_frames, dim_x, dim_y, D) bytes (21 per pixel and frame: both census images, the
+ * left winners, the IR images, the right winners; 0 for rejected arguments), 8-byte aligned, contents irrelevant before and
+ * after; a workspace for more frames serves a call with fewer.  Five launches, stream-ordered, nothing read back, none of
+ * which waits for another workgroup: rule I with one lane per pixel and camera; both census images from an LDS tile; the
+ * matcher once per direction (a workgroup of four waves owns 60 columns x 32 rows: the other image's census, widened by
+ * D - 1 columns, is its LDS tile; a lane owns a column, keeps its own census of the wave's 12 rows in registers, takes one
+ * popcount per row and d, slides the vertical 5-sum in registers and takes the horizontal 5-sum from its neighbour lanes;
+ * winner, second, cm and cp stay in registers across the d loop); then the resolve pass of rules W (left-right) and Z.
+ */
+typedef struct RdfStereoConfig {
+    int32_t fb16, fbp16;
+    int32_t max_disparity;          /* D */
+    uint32_t dot_threshold;         /* dot density * 2^32 */
+    uint32_t pattern_seed;
+    int32_t ambient, ir_noise_amp, census_margin;
+    int32_t uniqueness, lr_max, dq_min;
+} RdfStereoConfig;
+
+size_t rdf_stereo_workspace_bytes(int n_frames, int dim_x, int dim_y, int max_disparity);
+int rdf_stereo_ir(int n_frames, int dim_x, int dim_y, const uint16_t *depth_l, const uint16_t *depth_r, RdfStereoConfig config,
+                  uint32_t seed, uint8_t *ir_out, void *stream);
+int rdf_stereo_sense(int n_frames, int dim_x, int dim_y, const uint16_t *depth_l, const uint16_t *labels_l,
+                     const uint16_t *depth_r, RdfStereoConfig config, uint32_t seed, uint16_t empty_depth, void *workspace,
+                     uint16_t *depth_out, uint16_t *labels_out, uint8_t *ir_out, uint16_t *dq_out, uint8_t *reason_out,
+                     void *stream);
 
 int rdf_labels_abi_version(void);
 const char *rdf_labels_build_id(void);
