@@ -11,7 +11,11 @@ Triangles, by name (TRI maps a name to its indices in `tris`):
   behind   a triangle of part 2, label 5: frame 0 puts part 2 behind the camera, later frames in front
   bad      triangles that must be dropped without being read: a vertex index of n_verts, one of -1, and a vertex whose
            part is 99; label 9 appears nowhere
-Frames differ in every part's transform and in the table, so a wrong frame stride or key-plane offset shows."""
+Frames differ in every part's transform and in the table, so a wrong frame stride or key-plane offset shows.
+
+`case`              the scene at the SIZES, one and MAX_FRAMES frames, under every row of VARIANTS.
+`many_frames_case`  the same mesh at 16 x 13 in 65541 frames that cycle through seven settings of the transforms and tables
+                    (`part_tforms_cycle`, `tables_cycle`): more frames than k_hand_raster's grid has rows."""
 import numpy as np
 
 import hand_scene_numpy as hs
@@ -70,6 +74,48 @@ def part_tforms():
 def tables():
     """float32 [3, 4]: facing the camera at depth 1000 in frame 0, tilted in the others."""
     return np.array([(0., 0., 1., 1000.), (0.1, -0.05, 1., 990.), (-0.07, 0.12, 0.98, 1015.)], np.float32)
+
+
+# ------------------------------------------------------------------ more frames than the grid has rows ------------------------
+# k_hand_raster strides frames over gridDim.y, capped at 65535: six frames more make the loop body run twice.  Frame n has
+# the transforms (and the table) of setting n % 7, and 65535 % 7 = 1 (the three settings above would not do: 65535 % 3 = 0),
+# so a kernel that indexed by row of the grid, not by frame, would draw another setting.  No holes and no noise: a frame
+# then does not depend on its index.
+MANY_N, MANY_PERIOD, MANY_ROWS = 65541, 7, 65535
+MANY_SIZE = (16, 13)
+
+
+def part_tforms_cycle(p=MANY_PERIOD):
+    """float32 [p frames, 3 parts, 12]: p distinct settings; part 2 is behind the camera in settings 0 and 4."""
+    out = []
+    for k in range(p):
+        behind = k % 4 == 0
+        out.append(np.stack([_affine(0.03 * k - 0.1, 1. + 0.02 * k, (10. * k - 30., 6. * k - 20., 25. * k - 40.)),
+                             _affine(0.05 * k, 1., (4. * k - 10., 3. * k - 8., 30. - 12. * k)),
+                             _affine(shift=(0., 0., -2048.)) if behind else _affine(0.1 * k, 1., (-60. - 5. * k, -20. + 4. * k, 10. * k))]))
+    return np.stack(out)
+
+
+def tables_cycle(p=MANY_PERIOD):
+    """float32 [p, 4]: the table nearer than part of the quad in every setting, tilted another way in each."""
+    return np.array([(0.03 * k - 0.09, 0.1 - 0.04 * k, 1., 1040. - 15. * k) for k in range(p)], np.float32)
+
+
+# (name, table, empty_depth)
+MANY_VARIANTS = (("without a table", False, 65535), ("with the cycling tables", True, 0))
+
+
+def many_frames_case():
+    """{"cam", "mesh", "tforms" [7, 3, 12], "tables" [7, 4], "index": int [MANY_N] = n % 7,
+    "want": {variant name: (depth, labels, info) of the 7 settings}}, computed once."""
+    if "many" not in _cases:
+        W, H = MANY_SIZE
+        cam, m, t, tb = camera(W, H), mesh(W, H), part_tforms_cycle(), tables_cycle()
+        geometry = hs.rasterise(W, H, m[0], m[1], m[2], t, *cam)
+        want = {name: hs.render(W, H, *m, t, tb if with_table else None, *cam, empty_depth=empty, geometry=geometry)
+                for name, with_table, empty in MANY_VARIANTS}
+        _cases["many"] = {"cam": cam, "mesh": m, "tforms": t, "tables": tb, "index": np.arange(MANY_N) % MANY_PERIOD, "want": want}
+    return _cases["many"]
 
 
 _cases = {}

@@ -1,5 +1,12 @@
 """The scenes and inputs tests/test_pose_fit.py shares between its CPU and GPU tests, and the restated answers, each
-computed once and handed out unchanged (callers copy what they change)."""
+computed once and handed out unchanged (callers copy what they change).
+
+`fit_case`, `self_fit_case`   the 96 x 72 window of a 120 x 90 frame: an offset start, and a frame the true pose costs nothing on.
+`odd_fit_case`                the same frame under a 95 x 71 window: every candidate's images start elsewhere within 16 bytes.
+`cost_case`                   rule C on random images: small windows of every width class, one set per workgroup.
+`chunk_cost_case`             rule C where a workgroup takes several sets in a row (CHUNK_CASES).
+`select_cases`                rule S: ties, the strict "<", the fresh acceptance, RDF_POSE_MAX_CANDIDATES candidates.
+`propose_case`                rules P and K with ranges that clamp."""
 import functools
 import importlib
 
@@ -90,6 +97,26 @@ def fit_reference():
     return {"state": state, "history": history, "after3": after3}
 
 
+# the same frame under a window with an odd pixel count: 95 * 71 = 6745, so candidate k's images start k * 6745 * 2 bytes
+# into their region of the workspace and every candidate of rdf_pose_fit has another head length in rule C
+ODD_WINDOW = (13, 9, 95, 71)
+K_ODD, G_ODD = 5, 2
+
+
+@functools.lru_cache(maxsize=None)
+def odd_fit_case():
+    c = fit_case()
+    return dict(c, cfg=config(c["model"], c["plane"], ODD_WINDOW, K=K_ODD))
+
+
+@functools.lru_cache(maxsize=None)
+def odd_fit_reference():
+    c = odd_fit_case()
+    state = pf.new_state(c["start"])
+    history = pf.fit(state, G_ODD, True, c["cfg"], c["depth"], c["labels"], 1, c["mesh"])
+    return {"state": state, "history": history}
+
+
 @functools.lru_cache(maxsize=None)
 def self_fit_case():
     """A frame on which the true pose costs exactly nothing: the true pose drawn by rule K's own transforms at window
@@ -148,7 +175,43 @@ def cost_case(W, H, r):
     return {"depth": depth, "labels": labels, "runs": runs}
 
 
+# ------------------------------------------------------------------ rule C, several trips per workgroup --------------------
+# launch_cost deals a candidate's groups of eight pixels out in sets of 256 (one per lane): sets = ceil(floor(n_px / 8) / 256),
+# a workgroup takes chunk = clamp(floor(sets * K / 1024), 1, 16) sets in a row, and a candidate gets ceil(sets / chunk)
+# workgroups.  cost_case above never leaves chunk = 1.
+# name: frame, window, K, the r's, the element offsets of the candidates' depth and labels in their arrays (odd; 8 apart
+# in the second row, so that the labels keep the depth's 16-byte boundary and are loaded as vectors), then what the plan must
+# come to: sets, chunk, workgroups per candidate.
+#   the second row: the last workgroup's first trip is full (set 3), its second ends inside wave 1 (set 4 holds groups 1024
+#   to 1123 or 1124), its third is empty;  the third row: three of four trips do nothing, at K = RDF_POSE_MAX_CANDIDATES.
+# The clamp at 16 is left out: it needs sets * K >= 16384, about 33 million candidate pixels, and with ceil(sets / chunk)
+# workgroups it changes only how the same sets are dealt out.
+CHUNK_CASES = {
+    "the benchmarked plan": ((300, 260), (5, 3, 256, 256), 64, (1, 2), (3, 1), (32, 2, 16)),
+    "sets no multiple of chunk": ((120, 100), (7, 4, 100, 90), 615, (1,), (5, 13), (5, 3, 2)),
+    "more trips than sets": ((33, 17), (0, 0, 33, 17), 4096, (1,), (7, 1), (1, 4, 1)),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def chunk_cost_case(name, r):
+    """One run of rule C on random images: what cost_case's runs hold, a base that is nowhere zero, and the offsets."""
+    (W, H), window, K, rs, offsets, _ = CHUNK_CASES[name]
+    assert r in rs
+    rng = np.random.default_rng(7000 + 10 * list(CHUNK_CASES).index(name) + r)
+    depth = rng.choice(DEPTHS, (H, W))
+    labels = rng.choice(OBSERVED_LABELS, (H // r, W // r))
+    cd = rng.choice(DEPTHS, (K, window[3], window[2]))
+    cl = rng.integers(0, 9, (K, window[3], window[2])).astype(np.uint16)
+    base = rng.integers(1, 1 << 40, (K, 4)).astype(np.uint64)
+    return {"depth": depth, "labels": labels, "window": window, "K": K, "cand_depth": cd, "cand_labels": cl, "base": base,
+            "offsets": offsets, "terms": pf.cost_terms(depth, labels, r, window, cd, cl, COST_MASK)}
+
+
 # ------------------------------------------------------------------ rule S --------------------------------------------------
+MAX_CANDIDATES = 4096           # RDF_POSE_MAX_CANDIDATES: every lane of k_pose_select walks 64 of them
+
+
 def _terms(rows):
     return np.array(rows, np.uint64).reshape(-1, 4)
 
@@ -175,6 +238,10 @@ def select_cases():
     add("130 candidates, a tie across the wave", many, 10 ** 12)
     big = np.array([[2 ** 31 - 1, 2 ** 31 - 1, 0, 2 ** 62], [2 ** 31 - 1, 2 ** 31 - 1, 0, 2 ** 62 - 1]], np.uint64)
     add("costs beyond 2^63", big, 2 ** 64 - 1, w_boundary=2 ** 32 - 1)
+    most = rng.integers(50, 1000, (MAX_CANDIDATES, 4))
+    most[61] = most[4032] = most[4095] = (0, 0, 0, 3)       # a low k in lane 61, a high k in lane 0, the last k in lane 63
+    add("4096 candidates, the minimum three times", most, 10 ** 12)
+    add("4096 candidates, all equal", np.tile((1, 2, 3, 4), (MAX_CANDIDATES, 1)), 10 ** 12, w_label=5)
     return out
 
 

@@ -6,6 +6,13 @@ surface at Z = fB / d, the right render is the left one moved by exactly d colum
            left of the box are what the right camera cannot see.
 `layered`  what the GPU comparisons run on: per frame a plane, boxes in front of it at other disparities (one nearer than
            fB / D where asked), a strip of missing depth in both conventions (0 and 65535), different in every frame.
+
+`gpu_case`          a `layered` batch at each of GPU_SHAPES: tile edges, D = 1, 2 and 256, one row; at most 3 frames.
+`many_frames_case`  65541 frames of 13 x 5 that cycle through seven `layered` frames: more frames than the census and the
+                    matcher have planes in their grids, so that their frame loops come round.
+`variant_case`      the second GPU shape under each row of CONFIG_VARIANTS: every field of the config away from its default,
+                    one at a time, and rule I's numerator at its 32-bit limit.
+`box_case`          the `box` with sn.sense's record of its one frame.
 Every expected result is computed once and shared."""
 import numpy as np
 
@@ -85,6 +92,77 @@ def gpu_case(name):
         _cache[name] = {"in": (depth_l, labels, depth_r), "cfg": cfg,
                         "want": sn.sense(depth_l, labels, depth_r, cfg, seed=SEED, empty_depth=EMPTY)}
     return _cache[name]
+
+
+# ------------------------------------------------------------------ more frames than the grid has planes ---------------------
+# k_stereo_census strides images and k_stereo_match frames over gridDim.z, capped at 65535: six frames more make the loop
+# bodies run twice.  Frame n is distinct frame n % 7, and 65535 % 7 = 1: a kernel that indexed by plane, not by frame, would
+# land on another distinct frame.  No IR noise, so that a frame's result does not depend on its index.
+MANY_N, MANY_PERIOD, MANY_PLANES = 65541, 7, 65535
+MANY_W, MANY_H, MANY_D = 13, 5, 6
+MANY_IR_SEED = 0x5EED5
+MANY_IR_FRAMES = (0, 1, 65534, 65535, 65536, MANY_N - 1)
+
+
+def many_frames_case():
+    """{"distinct": the 7 distinct (depth_l, labels_l, depth_r), "cfg" (no IR noise), "want": sn.sense of the 7,
+    "index": int [MANY_N] = n % 7, "cfg_ir" (the default noise), "want_ir": {n: uint8 [2, H, W]} of MANY_IR_FRAMES}."""
+    if "many" not in _cache:
+        depth_l, labels, depth_r, cfg = layered(MANY_W, MANY_H, MANY_PERIOD, MANY_D, 5)
+        cfg = dict(cfg, ir_noise_amp=0)
+        cfg_ir = dict(cfg, ir_noise_amp=sn.DEFAULTS["ir_noise_amp"])
+        index = np.arange(MANY_N) % MANY_PERIOD
+        want_ir = {n: np.stack([sn.ir_image(depth_l[n % MANY_PERIOD], 0, n, cfg_ir, MANY_IR_SEED),
+                                sn.ir_image(depth_r[n % MANY_PERIOD], 1, n, cfg_ir, MANY_IR_SEED)]) for n in MANY_IR_FRAMES}
+        _cache["many"] = {"distinct": (depth_l, labels, depth_r), "cfg": cfg, "index": index, "cfg_ir": cfg_ir, "want_ir": want_ir,
+                          "want": sn.sense(depth_l, labels, depth_r, cfg, seed=SEED, empty_depth=EMPTY)}
+    return _cache["many"]
+
+
+# ------------------------------------------------------------------ every config field ---------------------------------------
+# The second GPU shape under a config changed one row at a time.  The last two rows run rule I's 32-bit numerator at its
+# limit: the largest fb16 the entry points accept, divided by Z = 1, 2 and 3 (and 65534, the largest Z / 2 added to it).
+VARIANT_SHAPE, VARIANT_SEED = (67, 9, 3, 24), 2
+FB16_MAX = 2 ** 31 - 2 ** 15 - 1
+LIMIT_COLUMNS = {"left": ((10, 1), (30, 2)), "right": ((20, 3), (50, 65534))}       # (column, Z)
+CONFIG_VARIANTS = {
+    "uniqueness 0": dict(uniqueness=0),
+    "uniqueness 50": dict(uniqueness=50),
+    "uniqueness 100": dict(uniqueness=100),
+    "lr_max 0": dict(lr_max=0),
+    "lr_max 255": dict(lr_max=255),
+    "dq_min 1": dict(dq_min=1),
+    "dq_min 200": dict(dq_min=200),
+    "dq_min 65535": dict(dq_min=65535),
+    "census_margin 0": dict(census_margin=0),
+    "census_margin 255": dict(census_margin=255),
+    "ambient 255": dict(ambient=255),
+    "ambient 0, ir_noise_amp 255": dict(ambient=0, ir_noise_amp=255),
+    "ir_noise_amp 0": dict(ir_noise_amp=0),
+    "dot_threshold 0": dict(dot_threshold=0),
+    "dot_threshold 0xFFFFFFFF": dict(dot_threshold=0xFFFFFFFF),
+    "fb16 at its limit, fbp16 0": dict(fb16=FB16_MAX, fbp16=0),
+    "fb16 at its limit, fbp16 = fb16": dict(fb16=FB16_MAX, fbp16=FB16_MAX),
+}
+LIMIT_VARIANTS = ("fb16 at its limit, fbp16 0", "fb16 at its limit, fbp16 = fb16")
+
+
+def variant_case(name=None):
+    """gpu_case's record (with sn.sense's "frames") of one row of CONFIG_VARIANTS; of the unchanged base without a name."""
+    key = ("variant", name)
+    if key not in _cache:
+        W, H, N, D = VARIANT_SHAPE
+        depth_l, labels, depth_r, cfg = layered(W, H, N, D, VARIANT_SEED)
+        if name is not None:
+            cfg = dict(cfg, **CONFIG_VARIANTS[name])
+        if name in LIMIT_VARIANTS:
+            for x, z in LIMIT_COLUMNS["left"]:
+                depth_l[:, :, x] = z
+            for x, z in LIMIT_COLUMNS["right"]:
+                depth_r[:, :, x] = z
+        _cache[key] = {"in": (depth_l, labels, depth_r), "cfg": cfg,
+                       "want": sn.sense(depth_l, labels, depth_r, cfg, seed=SEED, empty_depth=EMPTY, keep=True)}
+    return _cache[key]
 
 
 def box_case():

@@ -205,6 +205,32 @@ def test_the_gpu_scenes_exercise_what_they_are_meant_to():
     assert 0.15 < (holes == 0).mean() < 0.35 and not np.array_equal(holes[0] == 0, holes[1] == 0)
 
 
+def test_the_many_frames_case_reaches_the_frame_loop_and_its_settings_differ():
+    c = hc.many_frames_case()
+    N, p = hc.MANY_N, hc.MANY_PERIOD
+    assert N > hc.MANY_ROWS and N - hc.MANY_ROWS == 6 and hc.MANY_ROWS % p == 1 and hc.MANY_ROWS % 3 == 0
+    assert len(c["index"]) == N and c["index"][hc.MANY_ROWS] == 1 and c["tforms"].shape == (p, 3, 12) and c["tables"].shape == (p, 4)
+    verts, part, tris, label = c["mesh"]
+    (behind,) = hc.TRI["behind"]
+    z = [hs.vertices(verts, part, c["tforms"][k], *c["cam"])[2][tris[behind]] for k in range(p)]
+    assert [bool((v < 0).all()) for v in z] == [True, False, False, False, True, False, False] and all((v > 0).all() for v in z[1:4])
+    for name, with_table, empty in hc.MANY_VARIANTS:
+        depth, labels, info = c["want"][name]
+        assert depth.shape == (p,) + hc.MANY_SIZE[::-1]
+        for a in range(p):
+            assert (labels[a] > 0).sum() > 20 and info[a]["mesh"].any(), (name, a)
+            for b in range(a + 1, p):
+                assert not np.array_equal(depth[a], depth[b]) and not np.array_equal(labels[a], labels[b]), (name, a, b)
+        shown = {k for k in range(p) if (labels[k] == label[behind]).any()}
+        assert shown and not shown & {0, 4}, name
+        if with_table:      # mesh beats table and table beats mesh, in every setting
+            assert all((i["mesh"] & i["table"]).any() and ((i["winner"] >= 0) & ~i["mesh"]).any() for i in info)
+            assert ((labels == 0) & (depth != empty)).any()
+        else:
+            assert np.array_equal(depth == empty, labels == 0)
+    assert not np.array_equal(c["want"]["without a table"][0], c["want"]["with the cycling tables"][0])
+
+
 # ------------------------------------------------------------------ CPU: the model ------------------------------------------
 def test_every_part_is_a_closed_consistently_wound_mesh():
     hm = _hm()
@@ -448,6 +474,24 @@ def test_hand_built_scenes_match_the_restatement_bit_for_bit(W, H, n_frames, rdf
         # the workspace is left empty: the second call on it gives the same images
         assert np.array_equal(runs[1][0], runs[0][0]) and np.array_equal(runs[1][1], runs[0][1]), name
         assert (keys == 0xFF).all(), name
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,with_table,empty", hc.MANY_VARIANTS)
+def test_more_frames_than_the_grid_has_rows_match_the_restatement_bit_for_bit(name, with_table, empty, rdf, gpu_runtime):
+    c = hc.many_frames_case()
+    W, H = hc.MANY_SIZE
+    N = hc.MANY_N
+    want_depth, want_labels, _ = c["want"][name]
+    want_depth, want_labels = np.take(want_depth, c["index"], axis=0), np.take(want_labels, c["index"], axis=0)
+    tforms = np.take(c["tforms"], c["index"], axis=0)
+    tables = np.take(c["tables"], c["index"], axis=0) if with_table else None
+    runs, keys = _render_raw(rdf, W, H, c["mesh"], tforms, tables, c["cam"], empty, hc.SEED, 0, 0)
+    depth, labels = runs[0]
+    wrong = np.nonzero(((depth != want_depth) | (labels != want_labels)).reshape(N, -1).any(1))[0]
+    print(f"{name}: {len(wrong)} of {N} frames differ" + (f", the first {wrong[:8].tolist()}" if len(wrong) else ""))
+    assert depth.shape == (N, H, W) and np.array_equal(depth, want_depth) and np.array_equal(labels, want_labels)
+    assert keys.size == N * W * H * 8 and (keys == 0xFF).all()
 
 
 @pytest.mark.gpu

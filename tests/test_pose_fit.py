@@ -88,6 +88,49 @@ def test_the_gpu_cost_cases_reach_every_branch():
     assert 200 * 70 // 8 > 256          # more than one workgroup's groups per candidate
 
 
+def _cost_plan(n_px, K):
+    """The three plan lines of launch_cost: (sets, chunk, workgroups per candidate)."""
+    sets = (n_px // 8 + 255) // 256
+    chunk = min(max(sets * K // 1024, 1), 16)
+    return sets, chunk, (sets + chunk - 1) // chunk if sets else 1
+
+
+def _groups(n_px, offset, k):
+    """The full groups of eight of candidate k, whose image starts offset + k * n_px elements into a 16-byte aligned array."""
+    head = min(((16 - 2 * (offset + k * n_px) % 16) % 16) // 2, n_px)
+    return (n_px - head) // 8
+
+
+def test_the_chunked_cost_cases_make_the_trips_they_claim():
+    for name, ((W, H), window, K, rs, offsets, plan) in pc.CHUNK_CASES.items():
+        x0, y0, ww, wh = window
+        n_px = ww * wh
+        sets, chunk, gx = _cost_plan(n_px, K)
+        assert (sets, chunk, gx) == plan and 1 < chunk < 16, name
+        assert x0 + ww <= W and y0 + wh <= H and 2e6 < K * n_px < 6e6, name
+        assert offsets[0] % 2 == 1 and offsets[1] % 2 == 1 and offsets[0] != offsets[1], name
+        # the odd offset moves at most one group from the full groups to the head
+        groups = {_groups(n_px, offsets[0], k) for k in range(K)}
+        assert groups <= {n_px // 8 - 1, n_px // 8} and n_px // 8 - 1 in groups, name
+        last = [[min(max(g - ((gx - 1) * chunk + trip) * 256, 0), 256) for trip in range(chunk)] for g in sorted(groups)]
+        if name == "the benchmarked plan":
+            assert K == 64 and (ww, wh) == (256, 256) and rs == (1, 2)          # what profiles/pose_fit_bench.json measures
+            assert all(trips[0] == 256 and 192 < trips[1] <= 256 for trips in last), last   # every workgroup's second trip works
+        elif name == "sets no multiple of chunk":
+            assert sets % chunk and all(trips[0] == 256 and 64 < trips[1] < 128 and trips[2] == 0 for trips in last), last
+            assert (offsets[1] - offsets[0]) % 8 == 0                           # the labels are loaded as vectors
+        else:
+            assert K == pc.MAX_CANDIDATES and all(0 < trips[0] < 256 and trips[1:] == [0, 0, 0] for trips in last), last
+            assert len({(16 - 2 * (offsets[0] + k * n_px) % 16) % 16 for k in range(K)}) == 8       # every head length
+        for r in rs:
+            c = pc.chunk_cost_case(name, r)
+            assert c["terms"].shape == (K, 4) and (c["terms"] > 0).all() and (c["base"] > 0).all(), (name, r)
+            assert c["depth"].shape == (H, W) and c["labels"].shape == (H // r, W // r)
+    # the chunk is the same whichever way the sets are counted; cost_case never reaches a second trip
+    assert all(_cost_plan(w[2] * w[3], K)[1] == 1 for W, H in pc.COST_FRAMES for w in pc.cost_windows(W, H) for K in pc.COST_K)
+    assert _cost_plan(96 * 72, 16)[1] == 1 and _cost_plan(95 * 71, pc.K_ODD)[1] == 1
+
+
 # ------------------------------------------------------------------ CPU: rule P ---------------------------------------------
 def test_rule_p_draws_are_exact_and_centred():
     n = np.array([pf.draw(pf.candidate_hash(11, g, k), j) for g in range(20) for k in range(25) for j in range(20)])
@@ -188,7 +231,8 @@ def test_rule_s_ties_strictness_and_the_fresh_acceptance():
     want = {"the lowest cost wins": (1, True), "of equal costs the lowest k": (0, True), "equal to the incumbent is not better": (None, False),
             "one below the incumbent is": (1, True), "nothing better: only g moves": (None, False),
             "a fresh first generation takes the best although it is worse": (1, True), "one candidate": (0, True),
-            "130 candidates, a tie across the wave": (6, True), "costs beyond 2^63": (1, True)}
+            "130 candidates, a tie across the wave": (6, True), "costs beyond 2^63": (1, True),
+            "4096 candidates, the minimum three times": (61, True), "4096 candidates, all equal": (0, True)}
     cases = pc.select_cases()
     assert {c[0] for c in cases} == set(want)
     for name, K, terms, before, wb, wl, fresh in cases:
@@ -209,6 +253,14 @@ def test_rule_s_ties_strictness_and_the_fresh_acceptance():
         else:
             assert (state["g"], state["accepted"]) == (before["g"] + 1, before["accepted"] + int(replaced)), name
     assert pf.cost(np.array([[2 ** 31 - 1, 2 ** 31 - 1, 0, 2 ** 62]], np.uint64), 2 ** 32 - 1, 0)[0] < 2 ** 63     # it wrapped
+    # the cases at RDF_POSE_MAX_CANDIDATES: a lane of k_pose_select takes k = lane, lane + 64, ...
+    by_name = {c[0]: c for c in cases}
+    _, K, terms, _, wb, wl, _ = by_name["4096 candidates, the minimum three times"]
+    costs = pf.cost(terms, wb, wl)
+    at = [k for k in range(K) if costs[k] == min(costs)]
+    assert K == pc.MAX_CANDIDATES == 64 * 64 and at == [61, 4032, 4095] and [k % 64 for k in at] == [61, 0, 63]
+    _, K, terms, _, wb, wl, _ = by_name["4096 candidates, all equal"]
+    assert K == pc.MAX_CANDIDATES and len(set(pf.cost(terms, wb, wl))) == 1
 
 
 # ------------------------------------------------------------------ CPU: the whole fit --------------------------------------
@@ -238,6 +290,22 @@ def test_a_fit_from_an_offset_start_only_ever_gets_cheaper():
     assert ref["state"]["accepted"] >= 1 and ref["state"]["g"] == 8 and ref["state"]["cost"] == h[-1]
     assert ref["after3"]["g"] == 3 and ref["after3"]["cost"] == h[2]
     assert (ref["state"]["pose"] >= c["cfg"]["lo"]).all() and (ref["state"]["pose"] <= c["cfg"]["hi"]).all()
+
+
+def test_the_odd_window_fit_gives_every_candidate_another_head():
+    c, ref = pc.odd_fit_case(), pc.odd_fit_reference()
+    x0, y0, ww, wh = c["cfg"]["window"]
+    assert (x0, y0, ww, wh) == (13, 9, 95, 71) and c["cfg"]["K"] == 5 and ww * wh == 6745 and x0 + ww <= pc.FRAME_W and y0 + wh <= pc.FRAME_H
+    # candidate k's images start k * 6745 * 2 bytes into a 256-byte aligned region: the pixels in front of the first 16-byte
+    # boundary are 0, 7, 6, 5 and 4; under the 96 x 72 window every candidate starts on a boundary
+    heads = [((16 - (k * ww * wh * 2) % 16) % 16) // 2 for k in range(5)]
+    assert heads == [0, 7, 6, 5, 4] and all((k * 96 * 72 * 2) % 16 == 0 for k in range(pc.K_FIT))
+    hand = c["labels"] > 0
+    assert 400 < hand.sum() == hand[y0:y0 + wh, x0:x0 + ww].sum()
+    h = ref["history"]
+    print(f"restated fit on the odd window: history {h}, accepted {ref['state']['accepted']}")
+    assert len(h) == pc.G_ODD == 2 and h[1] <= h[0] and h[1] > 0 and ref["state"]["g"] == 2 and ref["state"]["accepted"] >= 1
+    assert ref["state"]["terms"][3] > 0 and ref["state"]["cost"] == h[1]
 
 
 # ------------------------------------------------------------------ CPU: the interface --------------------------------------
@@ -403,6 +471,30 @@ def test_rdf_pose_cost_matches_the_restatement_bit_for_bit(W, H, r, rdf, gpu_run
         assert np.array_equal(terms.get(), want)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,r", [(name, r) for name, case in pc.CHUNK_CASES.items() for r in case[3]])
+def test_rdf_pose_cost_over_several_trips_matches_the_restatement_bit_for_bit(name, r, rdf, gpu_runtime):
+    _lib, lib = _labels_lib()
+    (W, H), window, K, _, (off_d, off_l), plan = pc.CHUNK_CASES[name]
+    c = pc.chunk_cost_case(name, r)
+    depth, labels = rdf.to_device(c["depth"]), rdf.to_device(c["labels"])
+    n = K * window[2] * window[3]
+    cd, cl = rdf.DeviceArray((n + 16,), np.uint16), rdf.DeviceArray((n + 16,), np.uint16)
+    cd[off_d:off_d + n].set(c["cand_depth"].reshape(-1))
+    cl[off_l:off_l + n].set(c["cand_labels"].reshape(-1))
+    assert cd.ptr % 16 == 0 and cl.ptr % 16 == 0            # what the CPU test's head lengths assume
+    terms = rdf.to_device(c["base"])
+    rc = lib.rdf_pose_cost(W, H, depth.ptr, labels.ptr, r, *window, K, cd.ptr + 2 * off_d, cl.ptr + 2 * off_l, pc.COST_MASK, terms.ptr,
+                           gpu_runtime.stream())
+    _lib.check(lib, rc, "rdf_pose_cost")
+    got = terms.get()
+    want = c["base"] + c["terms"]
+    bad = int((got != want).sum())
+    print(f"{name} r={r}: plan (sets, chunk, workgroups) {plan}: {bad} of {want.size} terms differ; first candidate got "
+          f"{(got[0] - c['base'][0]).tolist()} want {c['terms'][0].tolist()}")
+    assert np.array_equal(got, want)
+
+
 def _state_bytes(state):
     raw = np.zeros(256, np.uint8)
     raw[:208] = np.asarray(state["pose"], np.float64).view(np.uint8)
@@ -494,6 +586,17 @@ def test_rdf_pose_fit_matches_the_restated_fit(rdf, gpu_runtime):
     # numpy frames are uploaded; no generations is a no-op that reports the state
     same = two.fit(c["depth"], c["labels"], generations=0, fresh=False).get()
     assert same.cost == ref["state"]["cost"] and same.generation == 8 and len(same.history) == 0
+
+
+@pytest.mark.gpu
+def test_rdf_pose_fit_on_a_window_with_an_odd_pixel_count_matches_the_restated_fit(rdf, gpu_runtime):
+    c, ref = pc.odd_fit_case(), pc.odd_fit_reference()
+    f = rdf.PoseFitter((pc.FRAME_H, pc.FRAME_W), pc.CAM, c["plane"], candidates=pc.K_ODD, window=pc.ODD_WINDOW, seed=pc.SEED)
+    got = f.fit(rdf.to_device(c["depth"]), rdf.to_device(c["labels"]), c["start"], generations=pc.G_ODD)
+    print(f"device fit on the odd window: history {got.get().history.tolist()}; restated {ref['history']}")
+    _assert_state(got, ref["state"], ref["history"])
+    keys = f._lb.rdf_hand_scene_workspace_bytes(pc.K_ODD, pc.ODD_WINDOW[2], pc.ODD_WINDOW[3])
+    assert keys == pc.K_ODD * 95 * 71 * 8 and (f._dev["workspace"].get()[:keys] == 0xFF).all()
 
 
 @pytest.mark.gpu

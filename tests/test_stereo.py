@@ -283,6 +283,147 @@ def test_the_gpu_cases_decide_something():
     assert ((near["in"][1] == 9) & (near["want"]["reason"] != 0)).sum() > 20
 
 
+def test_the_many_frames_case_reaches_the_frame_loops_and_its_frames_differ():
+    c = sc.many_frames_case()
+    N, p = sc.MANY_N, sc.MANY_PERIOD
+    assert N > sc.MANY_PLANES and 2 * N > sc.MANY_PLANES and N - sc.MANY_PLANES == 6        # frames and images both wrap
+    assert sc.MANY_PLANES % p == 1 and len(c["index"]) == N and c["index"][sc.MANY_PLANES] == 1 and c["index"][-1] == (N - 1) % p
+    assert c["cfg"]["ir_noise_amp"] == 0 and c["cfg_ir"]["ir_noise_amp"] == 6 and sc.MANY_IR_SEED != 0
+    want = c["want"]
+    assert want["depth"].shape == (p, sc.MANY_H, sc.MANY_W)
+    for a in range(p):
+        for b in range(a + 1, p):
+            assert not np.array_equal(want["depth"][a], want["depth"][b]), (a, b)
+            assert not np.array_equal(want["reason"][a], want["reason"][b]), (a, b)
+            assert not np.array_equal(want["ir"][a], want["ir"][b]) and not np.array_equal(want["dq"][a], want["dq"][b]), (a, b)
+    assert (want["reason"] == 0).sum() > 50 and (want["labels"] > 0).any()
+    for bit in (sn.REASON_UNIQUE, sn.REASON_LR, sn.REASON_DQ_MIN):
+        assert (want["reason"] & bit).any(), bit
+    # without noise a frame does not depend on its index: the restated sense of frames 65535.. is that of frames 1..
+    cfg = c["cfg"]
+    for k in range(p):
+        for camera in (0, 1):
+            depth = c["distinct"][2 * camera][k]
+            assert np.array_equal(sn.ir_image(depth, camera, k + p * 9362, cfg, sc.SEED), want["ir"][k, camera])
+    # with noise it does: the frames rdf_stereo_ir is compared on differ although their depth repeats
+    ir = c["want_ir"]
+    assert sorted(ir) == [0, 1, 65534, 65535, 65536, N - 1] and 65535 % p == 1 and not np.array_equal(ir[1], ir[65535])
+    assert all(not np.array_equal(ir[n], want["ir"][n % p]) for n in ir)
+
+
+def test_the_config_variants_do_what_their_names_say():
+    base = sc.variant_case()
+    assert base["cfg"] == dict(sn.DEFAULTS, fb16=base["cfg"]["fb16"], fbp16=base["cfg"]["fbp16"], max_disparity=24,
+                               pattern_seed=base["cfg"]["pattern_seed"])
+    print(f"base: reasons {np.bincount(base['want']['reason'].reshape(-1), minlength=8).tolist()}")
+    x = np.arange(sc.VARIANT_SHAPE[0])[None, :]
+    for name, over in sc.CONFIG_VARIANTS.items():
+        v = sc.variant_case(name)
+        assert all(v["cfg"][k] == over[k] for k in over) and all(v["cfg"][k] == base["cfg"][k] for k in base["cfg"] if k not in over)
+        differing = [k for k in OUTPUTS if not np.array_equal(v["want"][k], base["want"][k])]
+        print(f"{name}: {int((v['want']['reason'] == 0).sum())} valid, reasons "
+              f"{np.bincount(v['want']['reason'].reshape(-1), minlength=8).tolist()}, differs from the base in {differing}")
+        assert differing, name
+    want = {name: sc.variant_case(name)["want"] for name in sc.CONFIG_VARIANTS}
+    # uniqueness 0: best * 100 < second * 100 wherever C* < second; uniqueness 100: best * 100 < 0 never, and every pixel of a
+    # D = 24 frame has a d two away
+    for m, reason in zip(want["uniqueness 0"]["frames"], want["uniqueness 0"]["reason"]):
+        strictly = (m["second"] != sn.NONE) & (m["c"] < m["second"])
+        assert strictly.sum() > 500 and not (reason[strictly] & sn.REASON_UNIQUE).any()
+        assert (reason[m["c"] == m["second"]] & sn.REASON_UNIQUE).all()          # a tie is still not unique
+    assert any((m["c"] == m["second"]).any() for m in want["uniqueness 0"]["frames"])
+    assert all((m["second"] != sn.NONE).all() for m in want["uniqueness 100"]["frames"])
+    assert (want["uniqueness 100"]["reason"] & sn.REASON_UNIQUE).all() and not (want["uniqueness 100"]["reason"] == 0).any()
+    assert 0 < (want["uniqueness 50"]["reason"] == 0).sum() < (base["want"]["reason"] == 0).sum()
+    # lr_max 255: |dR - d| <= 255 always, so only a partner left of the image fails; lr_max 0 rejects more than 1 does
+    for m, reason in zip(want["lr_max 255"]["frames"], want["lr_max 255"]["reason"]):
+        assert np.array_equal((reason & sn.REASON_LR) != 0, x - m["d"] < 0) and (x - m["d"] >= 0).sum() > 500
+        assert (np.abs(np.take_along_axis(m["dR"], np.maximum(x - m["d"], 0), 1) - m["d"]) > 1).any()      # lr_max 1 rejects here
+    assert((want["lr_max 0"]["reason"] & sn.REASON_LR) != 0).sum() > ((base["want"]["reason"] & sn.REASON_LR) != 0).sum()
+    # dq_min
+    assert (want["dq_min 65535"]["reason"] & sn.REASON_DQ_MIN).all() and (want["dq_min 200"]["reason"] & sn.REASON_DQ_MIN).all()
+    assert not (want["dq_min 1"]["reason"][want["dq_min 1"]["dq"] >= 1] & sn.REASON_DQ_MIN).any()
+    assert ((want["dq_min 1"]["dq"] >= 1) & (want["dq_min 1"]["dq"] < 16)).any() and (want["dq_min 1"]["dq"] == 0).any()
+    # a margin of 255 and no dots (ambient and noise alone, below the default margin) empty every census
+    for name in ("census_margin 255", "dot_threshold 0"):
+        margin = sc.variant_case(name)["cfg"]["census_margin"]
+        assert not any(sn.census(image, margin).any() for frame in want[name]["ir"] for image in frame), name
+        assert not (want[name]["reason"] == 0).any(), name
+    assert any(sn.census(image, 16).any() for frame in base["want"]["ir"] for image in frame)
+    assert want["dot_threshold 0"]["ir"].min() >= 16 - 6 and want["dot_threshold 0"]["ir"].max() <= 16 + 6
+    surface = np.stack([(d > 0) & (d < 65535) for d in (base["in"][0], base["in"][2])], 1)
+    everywhere, nowhere = want["dot_threshold 0xFFFFFFFF"]["ir"].astype(int), want["dot_threshold 0"]["ir"].astype(int)
+    assert (everywhere[surface] - nowhere[surface] >= 64).all() and np.array_equal(everywhere[~surface], nowhere[~surface])
+    # the clamp at 255: the base's IR image is nowhere clamped (10 <= 16 + dots + noise <= 16 + 191 + 6), so ambient 255 is the
+    # base moved up by 239 and cut off.  A surface pixel is 255 unless it has no dot to outweigh a negative noise draw (the
+    # noise keeps its default of 6 in this row, so 249 is the least)
+    assert base["want"]["ir"].max() <= 16 + 191 + 6 and base["want"]["ir"].min() >= 16 - 6
+    bright = want["ambient 255"]["ir"]
+    assert np.array_equal(bright, np.minimum(base["want"]["ir"].astype(int) + 239, 255))
+    assert (bright[surface & (base["want"]["ir"] >= 16)] == 255).all() and (bright[surface] == 255).mean() > 0.5 and bright.min() == 249
+    # the clamp at 0 and at 255 in one image
+    wild = want["ambient 0, ir_noise_amp 255"]["ir"]
+    assert (wild == 0).sum() > 1000 and (wild == 255).sum() > 100 and ((wild > 0) & (wild < 255)).any()
+    quiet = want["ir_noise_amp 0"]["ir"]
+    assert (quiet[~surface] == 16).all() and np.abs(quiet.astype(int) - base["want"]["ir"]).max() == 6
+    # the numeric limit: valid pixels, all at the clamp of rule Z, and columns at Z = 1, 2, 3 and 65534
+    for name in sc.LIMIT_VARIANTS:
+        v = sc.variant_case(name)
+        valid = v["want"]["reason"] == 0
+        assert valid.sum() > 100 and (v["want"]["depth"][valid] == 65534).all(), name
+        assert v["cfg"]["fb16"] == 2 ** 31 - 2 ** 15 - 1 and v["cfg"]["fb16"] + 32767 == 2 ** 31 - 2         # the numerator's limit
+        assert (v["in"][0][:, :, 10] == 1).all() and (v["in"][0][:, :, 30] == 2).all()
+        assert (v["in"][2][:, :, 20] == 3).all() and (v["in"][2][:, :, 50] == 65534).all()
+    assert sc.variant_case(sc.LIMIT_VARIANTS[0])["cfg"]["fbp16"] == 0
+    assert sc.variant_case(sc.LIMIT_VARIANTS[1])["cfg"]["fbp16"] == sc.FB16_MAX
+
+
+@pytest.mark.gpu
+def test_more_frames_than_the_grid_has_planes_match_the_restatement_bit_for_bit(rdf, gpu_runtime):
+    _lib = importlib.import_module("3d-beats_amd._lib")
+    lib = _lib.load("labels")
+    c = sc.many_frames_case()
+    N, H, W = sc.MANY_N, sc.MANY_H, sc.MANY_W
+    arrays = [np.take(a, c["index"], axis=0) for a in c["distinct"]]
+    rc, got = _sense_raw(rdf, arrays, c["cfg"], sc.SEED, sc.EMPTY)
+    assert rc == 0
+    for k in OUTPUTS:
+        want = np.take(c["want"][k], c["index"], axis=0)
+        wrong = np.nonzero((got[k] != want).reshape(N, -1).any(1))[0]
+        print(f"{k}: {len(wrong)} of {N} frames differ" + (f", the first {wrong[:8].tolist()}" if len(wrong) else ""))
+        assert got[k].shape == want.shape and np.array_equal(got[k], want), k
+    # rule I's per-frame hash at large n: the default noise, on its own
+    dl, dr = rdf.to_device(arrays[0]), rdf.to_device(arrays[2])
+    ir = rdf.DeviceArray((N, 2, H, W), np.uint8).fill(7)
+    _lib.check(lib, lib.rdf_stereo_ir(N, W, H, dl.ptr, dr.ptr, _config(_lib, c["cfg_ir"]), sc.MANY_IR_SEED, ir.ptr,
+                                      gpu_runtime.stream()), "rdf_stereo_ir")
+    ir = ir.get()
+    for n in sc.MANY_IR_FRAMES:
+        assert np.array_equal(ir[n], c["want_ir"][n]), n
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(sc.CONFIG_VARIANTS))
+def test_every_config_field_matches_the_restatement_bit_for_bit(name, rdf, gpu_runtime):
+    _lib = importlib.import_module("3d-beats_amd._lib")
+    lib = _lib.load("labels")
+    c = sc.variant_case(name)
+    want = c["want"]
+    N, H, W = c["in"][0].shape
+    dl, dr = rdf.to_device(c["in"][0]), rdf.to_device(c["in"][2])
+    ir = rdf.DeviceArray((N, 2, H, W), np.uint8).fill(7)
+    _lib.check(lib, lib.rdf_stereo_ir(N, W, H, dl.ptr, dr.ptr, _config(_lib, c["cfg"]), sc.SEED, ir.ptr, gpu_runtime.stream()),
+               "rdf_stereo_ir")
+    assert np.array_equal(ir.get(), want["ir"])
+    rc, got = _sense_raw(rdf, c["in"], c["cfg"], sc.SEED, sc.EMPTY)
+    assert rc == 0
+    bad = {k: int((got[k] != want[k]).sum()) for k in OUTPUTS}
+    print(f"{name}: {int((want['reason'] == 0).sum())} of {N * H * W} valid, reasons "
+          f"{np.bincount(want['reason'].reshape(-1), minlength=8).tolist()}, differing {bad}")
+    for k in OUTPUTS:
+        assert np.array_equal(got[k], want[k]), k
+
+
 @pytest.mark.gpu
 def test_rejected_arguments_leave_the_outputs_untouched(rdf, gpu_runtime):
     c = sc.gpu_case("D = 2")
