@@ -18,6 +18,7 @@ from .decision_tree import (DecisionForest, DecisionTree, DecisionTreeEvaluator,
 from .device import DeviceArray, HipRuntime, device_ptr, get_runtime, host_mapped_array, set_runtime, to_device  # noqa: F401
 from .engine.buffer import GpuBuffer  # noqa: F401
 from .frontend import FrameFrontEnd  # noqa: F401
+from .depth_filter import DepthPostFilter  # noqa: F401
 from .grouping import HandGrouping  # noqa: F401
 from .hand_model import HandModel  # noqa: F401
 from .hand_scene import HandSceneRenderer  # noqa: F401
@@ -58,6 +59,6 @@ def install_reference_aliases(force=False):
 
 
 __all__ = ["DecisionTree", "DecisionForest", "LayeredDecisionForest", "DecisionTreeEvaluator", "DecisionTreeTrainer",
-           "GpuBuffer", "CalibratedPlane", "ColorLabeler", "RecordingConverter", "SceneRerender", "HandModel", "HandSceneRenderer", "StereoSensor", "PoseFitter", "LabelScorer", "Score", "FrameFrontEnd", "HandGrouping", "HandPipeline", "HandState", "BeatsSession", "HostFramesEvaluator",
+           "GpuBuffer", "CalibratedPlane", "ColorLabeler", "RecordingConverter", "SceneRerender", "HandModel", "HandSceneRenderer", "StereoSensor", "PoseFitter", "LabelScorer", "Score", "FrameFrontEnd", "DepthPostFilter", "HandGrouping", "HandPipeline", "HandState", "BeatsSession", "HostFramesEvaluator",
            "DeviceArray", "HipRuntime", "MAX_UINT16", "RdfError", "device_ptr", "get_runtime", "set_runtime",
            "to_device", "host_mapped_array", "library_path", "synth", "install_reference_aliases"]

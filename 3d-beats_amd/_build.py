@@ -26,9 +26,10 @@ class Library(NamedTuple):
 # Each library has its own sources and build id, so adding one leaves the others' binaries as they were.
 LIBRARIES = {lib.key: lib for lib in (
     Library("hip", SO, SOURCES, HEADERS, "rdf_"),
-    # the depth front end, and the note state machine behind the fingertip heights
+    # the depth front end, the note state machine behind the fingertip heights, and the depth post-filter in front of both
     Library("frontend", os.path.join(HERE, "csrc", "librdf_frontend.so"),
-            [os.path.join(HERE, "csrc", "frontend_hip.hip"), os.path.join(HERE, "csrc", "hand_state_hip.hip")],
+            [os.path.join(HERE, "csrc", "frontend_hip.hip"), os.path.join(HERE, "csrc", "hand_state_hip.hip"),
+             os.path.join(HERE, "csrc", "depth_filter_hip.hip")],
             [os.path.join(HERE, "..", "include", "rdf_frontend.h")], "rdf_frontend_"),
     # glove-colour recordings to training labels, the re-render that augments them, the score of predicted label maps, and
     # labelled frames of the articulated hand, the fit of that hand's pose to a labelled depth frame, and the stereo depth

@@ -148,6 +148,12 @@ class StereoConfig(ctypes.Structure):
                 ("lr_max", ctypes.c_int32), ("dq_min", ctypes.c_int32)]
 
 
+class DepthFilterConfig(ctypes.Structure):
+    """RdfDepthFilterConfig of include/rdf_frontend.h, passed by address (host memory)."""
+    _fields_ = [(name, ctypes.c_int32) for name in ("spatial_radius", "spatial_delta", "temporal", "temporal_alpha", "temporal_delta",
+                                                    "persist_need", "persist_span", "fill_mode", "max_gap")]
+
+
 # library (a key of _build.LIBRARIES) -> (the ABI number this binding was written for, name -> (restype, argtypes) of every
 # symbol its header declares)
 BINDINGS = {
@@ -172,6 +178,9 @@ BINDINGS = {
         "rdf_hand_state_set": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p]),
         "rdf_hand_state_step": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, ctypes.c_uint32,
                                          _c_void_p]),
+        "rdf_depth_filter_state_bytes": (_c_size_t, [_c_int, _c_int]),
+        "rdf_depth_filter": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, ctypes.POINTER(DepthFilterConfig), _c_void_p, _c_void_p,
+                                      _c_void_p, _c_void_p]),
         "rdf_frontend_abi_version": (_c_int, []),
         "rdf_frontend_build_id": (ctypes.c_char_p, []),
         "rdf_frontend_error_string": (ctypes.c_char_p, [_c_int]),

@@ -6,6 +6,9 @@
 and ONE `HandState` of ten fingertips (right 0-4, left 5-9).  Everything runs on the current stream; a frame is enqueued by
 `tick()` and nothing is read until `poll()`.  The fingertip heights are looked up in the raw camera frame, as the reference
 does (3d_bz.py:517), and the heights read the front end's plane on the device, so a recalibration reaches them.
+
+With `post_filter=` (a `DepthPostFilter`) every raw frame goes through the depth post-filter first, and "the raw frame" above
+is the filtered one: the front end, both hands and the fingertip heights see it.
 """
 import numpy as np
 
@@ -35,10 +38,12 @@ class BeatsSession:
                  mean_shift_variances=(50., 8., 8., 8., 8., 8., 8.), fingertip_idxes=(2, 3, 4, 5, 6), z_thresh_offset=25.,
                  min_velocity=10., max_velocity=120., velocity_sensitive=True, scale_factor=None,
                  fingertip_thresholds=(200., 160., 160., 160., 160.), first_notes=(36, 41), max_frames=8,
-                 num_random_guesses=25000, seed=None, fused_io=True, capacity=4096):
+                 num_random_guesses=25000, seed=None, fused_io=True, capacity=4096, post_filter=None):
         """layered_rdf: a LayeredDecisionForest built for depth_dims = (DIM_Y, DIM_X) and labels_reduce; intrinsics = (focal,
         ppx, ppy) of the depth camera.  The other defaults are the app's (3d_bz.py:49-124); scale_factor = DIM_X / 848 when
-        None.  max_frames = the batch of run_sequence's front end and grouping."""
+        None.  max_frames = the batch of run_sequence's front end and grouping.  post_filter: a DepthPostFilter of the same
+        depth_dims that calibrate, tick and run_sequence pass their frames through first; its temporal state runs on from
+        call to call (post_filter.reset() starts it afresh).  Without one nothing is allocated or launched for it."""
         self._rt = get_runtime()
         self.DIM_Y, self.DIM_X = int(depth_dims[0]), int(depth_dims[1])
         self.max_frames = int(max_frames)
@@ -65,6 +70,10 @@ class BeatsSession:
         hm, wm = self.grouping.depth_mm_dims
         self._raw = DeviceArray((self.max_frames, self.DIM_Y, self.DIM_X), np.uint16)
         self._clean = DeviceArray((self.max_frames, self.DIM_Y, self.DIM_X), np.uint16)
+        self.post_filter = post_filter
+        if post_filter is not None:
+            assert (post_filter.DIM_Y, post_filter.DIM_X) == (self.DIM_Y, self.DIM_X), "post_filter is of another frame size"
+            self._filtered = DeviceArray((self.max_frames, self.DIM_Y, self.DIM_X), np.uint16)
         self._groups = DeviceArray((self.max_frames, hm, wm), np.uint16)
         self._clean_f = [_Frame(self._clean[i]) for i in range(self.max_frames)]
         self._groups_f = [_Frame(self._groups[i]) for i in range(self.max_frames)]
@@ -72,7 +81,7 @@ class BeatsSession:
     # -- the plane --
     def calibrate(self, depth):
         """Fit the table plane to a frame (host or device uint16 [DIM_Y, DIM_X]); returns the 4x4 plane."""
-        return self.front_end.calibrate(self._on_device(depth, 1)[0])
+        return self.front_end.calibrate(self._camera_frames(depth, 1)[0])
 
     def set_plane(self, plane):
         self.front_end.set_plane(plane)
@@ -86,12 +95,19 @@ class BeatsSession:
         self._raw[:n].set(np.ascontiguousarray(frames, np.uint16).reshape(n, self.DIM_Y, self.DIM_X))
         return self._raw[:n]
 
+    def _camera_frames(self, frames, n):
+        """_on_device, then the post-filter when there is one: what the rest of the frame takes for the camera's frames."""
+        raw = self._on_device(frames, n)
+        if self.post_filter is None:
+            return raw
+        return self.post_filter.run(raw, self._filtered[:n])
+
     # -- live --
     def tick(self, depth):
         """Enqueues one whole frame (uint16 [DIM_Y, DIM_X]) on the current stream and returns nothing: front end, grouping,
         both hands, the note step.  A device frame is only enqueued and the stream is never waited for; a host frame is
         copied to the device first."""
-        raw = self._on_device(depth, 1)
+        raw = self._camera_frames(depth, 1)
         self.front_end.run(raw, self._clean[:1])
         self.grouping.make_group_image(self._clean[:1], self._groups[:1])
         raw = _Frame(raw[0])
@@ -122,7 +138,7 @@ class BeatsSession:
         lib, stream = self._rt.lib, self._rt.stream
         for a in range(0, F, self.max_frames):
             b = min(F - a, self.max_frames)
-            raw = self._on_device(frames[a:a + b], b)
+            raw = self._camera_frames(frames[a:a + b], b)
             self.front_end.run(raw, self._clean[:b])
             self.grouping.make_group_image(self._clean[:b], self._groups[:b])
             if batched:

@@ -4,6 +4,8 @@
  * the reference's CalibratedPlane (src/calibrated_plane.py, src/cuda/calibrated_plane.cu) and the per-frame chain
  * deproject_points -> transform_points -> filter_points_by_plane -> remove_missing_3d_points_from_depth_image ->
  * gaussian_depth_filter of src/3d_bz.py:163-212 (src/cuda/points_ops.cu:5-36, 63-73, 131-146, 327-373).
+ * Also in this library: the note state machine behind the fingertip heights (rdf_hand_state_*), and the depth post-filter that
+ * stands in front of rdf_frame_front when the frames come from a stereo camera (rdf_depth_filter).
  *
  * It is a library of its own, next to librdf_hip.so, with its own ABI number and build id.  Conventions are those of
  * rdf_hip.h: every pointer is caller-owned DEVICE memory unless stated; nothing is allocated, freed or synchronised
@@ -30,7 +32,8 @@
 extern "C" {
 #endif
 
-/* 1: first version.  2: rdf_hand_state_* (the note state machine behind the fingertip heights), RDF_ERR_CAPTURE. */
+/* 1: first version.  2: rdf_hand_state_* (the note state machine behind the fingertip heights), RDF_ERR_CAPTURE.
+ * rdf_depth_filter and rdf_depth_filter_state_bytes are a pure addition to 2. */
 #define RDF_FRONTEND_ABI_VERSION 2
 
 #define RDF_OK 0
@@ -224,6 +227,69 @@ int rdf_hand_state_set(void *state, int field, int tip_first, int n, const doubl
  * fit the block's n_tips does nothing.  capacity >= 1.  Can be captured into a graph. */
 int rdf_hand_state_step(void *state, const double *heights, int n_frames, int tip_first, int n, int32_t *events,
                         uint32_t *head, uint32_t capacity, void *stream);
+
+/*
+ * ---- Depth post-filter: what stands between a stereo camera's raw frames and rdf_frame_front.  Three stages in the order
+ * S -> T -> F, each of which can be switched off; integer arithmetic throughout (the reference has no counterpart: these
+ * rules are this project's own).  Depth is uint16, 0 = no reading (a "hole"), as rdf_frame_front takes it. ----
+ *
+ * Rule S, spatial (spatial_radius r in 0 .. 2, 0 = off; spatial_delta in 0 .. 65535 depth units).  A hole stays a hole.  For
+ * a reading c: of the (2r+1)^2 window round it, the readings n != 0 that lie inside the frame and have |n - c| <=
+ * spatial_delta (the centre is always one of them); s is their sum and k their number; out = (2 s + k) / (2 k), integer
+ * division: their mean, rounded half up.
+ *
+ * Rule T, temporal (temporal in 0 .. 1, 0 = off; temporal_alpha in 0 .. 256, the new reading's weight in 256ths;
+ * temporal_delta in 0 .. 65535 depth units; persist_need in 0 .. 9, persist_span in 1 .. 8).  One uint32 of state per pixel:
+ * bits 31..8 are v, the filtered value in sixteenths of a depth unit, 0 = none; bits 7..0 are hist, bit j = "the frame j + 1
+ * frames ago had a reading".  With c the output of S and c16 = 16 c:
+ *   on a reading (c != 0):  nv = (alpha * c16 + (256 - alpha) * v + 128) >> 8  when v != 0 and |c16 - v| <= 16 temporal_delta
+ *                           ("blended"), nv = c16 otherwise; out = (nv + 8) >> 4; v' = nv.
+ *   on a hole (c == 0):     out = (v + 8) >> 4 when v != 0 and popcount(hist & (2^span - 1)) >= need ("persisted"), else 0;
+ *                           v' = v.
+ *   then hist' = ((hist << 1) | (c != 0)) & 255, and on a hole with hist' == 0: v' = 0 -- a value is forgotten after eight
+ *   frames without a reading.
+ * alpha = 256 with need = 9 is the identity.  With T off the state is neither read nor written.
+ *
+ * Rule F, hole filling, row by row on T's output t (fill_mode 0 = off, 1 = "left", 2 = "farthest"; max_gap in 0 .. 65535
+ * columns).  A reading is unchanged.  For a hole at x: L = t[x - k] for the smallest k in 1 .. max_gap with x - k >= 0 and
+ * t[x - k] != 0, or 0 when there is none; R the same with x + k <= dim_x - 1.  Mode 1 gives L, mode 2 max(L, R).  Only
+ * readings of t are sources, never filled values, and filled values do not enter T's state.
+ *
+ * flags (uint8 per pixel and frame): bit 0 = T blended, bit 1 = T persisted, bit 2 = F wrote a value other than 0 into a hole.
+ *
+ * The n frames of a call are consecutive in time: frame i + 1 sees the state frame i left, and the state after the call is
+ * what the next call starts from, so the result of a sequence does not depend on how it is cut into calls.
+ */
+typedef struct RdfDepthFilterConfig {
+    int32_t spatial_radius;
+    int32_t spatial_delta;
+    int32_t temporal;
+    int32_t temporal_alpha;
+    int32_t temporal_delta;
+    int32_t persist_need;
+    int32_t persist_span;
+    int32_t fill_mode;
+    int32_t max_gap;
+} RdfDepthFilterConfig;
+
+#define RDF_DEPTH_FILTER_MAX_WIDTH 2048    /* a workgroup holds whole rows */
+
+/* 4 * dim_x * dim_y: one uint32 per pixel, 4-byte aligned.  All zero = no history (the caller resets by zeroing it);
+ * 0 for a negative size. */
+size_t rdf_depth_filter_state_bytes(int dim_x, int dim_y);
+
+/*
+ * depth, depth_out uint16 [n][dim_y][dim_x]; state uint32 [dim_y][dim_x], read at the start of the call and written at its
+ * end (may be NULL with T off); flags_out uint8 [n][dim_y][dim_x] or NULL.  config is HOST memory, read during the call and
+ * passed to the kernel by value.  ONE launch whatever n is; no synchronous HIP call, nothing read back.
+ * RDF_ERR_BAD_ARG: a negative n, dim_x or dim_y; a config field outside its range; dim_x > RDF_DEPTH_FILTER_MAX_WIDTH; a
+ * depth or depth_out that is not 2-byte aligned, a state that is not 4-byte aligned; depth_out overlapping depth (a pixel's
+ * window reaches into its neighbours' rows).  RDF_ERR_NULL_PTR: config, depth or depth_out NULL, state NULL with T on.
+ * RDF_ERR_TOO_LARGE: n * dim_x * dim_y >= 2^31.  n = 0, dim_x = 0 or dim_y = 0 does nothing and returns 0 (after the
+ * config's ranges have been checked).
+ */
+int rdf_depth_filter(int n, int dim_x, int dim_y, const uint16_t *depth, const RdfDepthFilterConfig *config, uint32_t *state,
+                     uint16_t *depth_out, uint8_t *flags_out, void *stream);
 
 int rdf_frontend_abi_version(void);
 const char *rdf_frontend_build_id(void);
