@@ -30,7 +30,8 @@ LIBRARIES = {lib.key: lib for lib in (
     Library("frontend", os.path.join(HERE, "csrc", "librdf_frontend.so"),
             [os.path.join(HERE, "csrc", "frontend_hip.hip"), os.path.join(HERE, "csrc", "hand_state_hip.hip"),
              os.path.join(HERE, "csrc", "depth_filter_hip.hip")],
-            [os.path.join(HERE, "..", "include", "rdf_frontend.h")], "rdf_frontend_"),
+            [os.path.join(HERE, "..", "include", "rdf_frontend.h"), os.path.join(HERE, "csrc", "rdf_kernel_util.hpp")],
+            "rdf_frontend_"),
     # glove-colour recordings to training labels, the re-render that augments them, the score of predicted label maps, and
     # labelled frames of the articulated hand, the fit of that hand's pose to a labelled depth frame, and the stereo depth
     # sensor that turns a left and a right render of those frames into what a camera would report
@@ -38,7 +39,8 @@ LIBRARIES = {lib.key: lib for lib in (
             [os.path.join(HERE, "csrc", "labels_hip.hip"), os.path.join(HERE, "csrc", "rerender_hip.hip"),
              os.path.join(HERE, "csrc", "score_hip.hip"), os.path.join(HERE, "csrc", "hand_scene_hip.hip"),
              os.path.join(HERE, "csrc", "pose_fit_hip.hip"), os.path.join(HERE, "csrc", "stereo_sensor_hip.hip")],
-            [os.path.join(HERE, "..", "include", "rdf_labels.h")], "rdf_labels_"),
+            [os.path.join(HERE, "..", "include", "rdf_labels.h"), os.path.join(HERE, "csrc", "rdf_kernel_util.hpp"),
+             os.path.join(HERE, "csrc", "rdf_raster.hpp")], "rdf_labels_"),
 )}
 
 # No -ffast-math, no -fgpu-flush-denormals-to-zero: the fp32 divide must stay IEEE-correct

@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "../../include/rdf_frontend.h"
+#include "rdf_kernel_util.hpp"
 
 namespace {
 
@@ -325,8 +326,6 @@ inline size_t lds_bytes(int W, int R)
 
 inline bool in_range(int v, int lo, int hi) { return v >= lo && v <= hi; }
 
-inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -351,13 +350,13 @@ int rdf_depth_filter(int n, int dim_x, int dim_y, const uint16_t *depth, const R
     const unsigned long long pixels = (unsigned long long)n * (unsigned long long)dim_x * (unsigned long long)dim_y;
     if (pixels >= (1ull << 31)) return RDF_ERR_TOO_LARGE;
     if (!depth || !depth_out || (cfg.temporal && !state)) return RDF_ERR_NULL_PTR;
-    if (!aligned(depth, 2) || !aligned(depth_out, 2) || (state && !aligned(state, 4))) return RDF_ERR_BAD_ARG;
+    if (misaligned(depth, 2) || misaligned(depth_out, 2) || misaligned(state, 4)) return RDF_ERR_BAD_ARG;
     const uintptr_t a = reinterpret_cast<uintptr_t>(depth), b = reinterpret_cast<uintptr_t>(depth_out), bytes = (uintptr_t)pixels * 2;
     if (a < b + bytes && b < a + bytes) return RDF_ERR_BAD_ARG;
-    const int vec = dim_x % kChunk == 0 && aligned(depth, 16) && aligned(depth_out, 16) && (!state || aligned(state, 16)) &&
-                    (!flags_out || aligned(flags_out, 8));
+    const int vec = dim_x % kChunk == 0 && !misaligned(depth, 16) && !misaligned(depth_out, 16) && !misaligned(state, 16) &&
+                    !misaligned(flags_out, 8);
     const dim3 grid((unsigned)dim_y), block(kThreads);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t s = S(stream);
     uint32_t *st = cfg.temporal ? state : nullptr;
     switch (cfg.spatial_radius) {
     case 0: hipLaunchKernelGGL(k_depth_filter<0>, grid, block, lds_bytes(dim_x, 0), s, n, dim_x, dim_y, depth, cfg, st, depth_out, flags_out, vec); break;

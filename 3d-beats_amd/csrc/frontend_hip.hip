@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "../../include/rdf_frontend.h"
+#include "rdf_kernel_util.hpp"
 
 namespace {
 
@@ -308,8 +309,6 @@ __global__ void k_remove_missing(int n, const float4 *__restrict__ pts, uint16_t
     if (pts[i].w == 0.f) depth[i] = 0;
 }
 
-inline hipStream_t S(void *s) { return reinterpret_cast<hipStream_t>(s); }
-inline unsigned blocks(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 constexpr long long kMaxElems = 1ll << 31;
 
 }  // namespace
@@ -360,7 +359,7 @@ int rdf_calibrate_plane(int G, float threshold, int dim_x, int dim_y, const floa
 {
     if (G <= 0 || dim_x <= 0 || dim_y <= 0) return RDF_ERR_BAD_ARG;
     if (!rand || !pts || !workspace || !plane_inout) return RDF_ERR_NULL_PTR;
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return RDF_ERR_BAD_ARG;
+    if (misaligned(workspace, 16)) return RDF_ERR_BAD_ARG;
     float *cand = static_cast<float *>(workspace);
     int32_t *counts = reinterpret_cast<int32_t *>(static_cast<char *>(workspace) + (size_t)G * 64);
     int rc = rdf_make_plane_candidates(G, dim_x, dim_y, rand, pts, start_mat, cand, counts, stream);

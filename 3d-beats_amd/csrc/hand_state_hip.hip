@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/rdf_frontend.h"
+#include "rdf_kernel_util.hpp"
 
 namespace {
 
@@ -218,8 +219,6 @@ __global__ void __launch_bounds__(kWave) k_hand_state_step(uint8_t *state, const
     }
 }
 
-inline hipStream_t S(void *s) { return reinterpret_cast<hipStream_t>(s); }
-
 }  // namespace
 
 extern "C" {
@@ -234,7 +233,7 @@ int rdf_hand_state_init(void *state, int n_tips, int num_positions, const double
 {
     if (!dims_ok(n_tips, num_positions)) return RDF_ERR_BAD_ARG;
     if (!state || !z_thresh || !midi_notes) return RDF_ERR_NULL_PTR;
-    if ((reinterpret_cast<uintptr_t>(state) & 7) != 0) return RDF_ERR_BAD_ARG;
+    if (misaligned(state, 8)) return RDF_ERR_BAD_ARG;
     TipValues tv = {};
     for (int t = 0; t < n_tips; ++t) {
         tv.z_thresh[t] = z_thresh[t];

@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "../../include/rdf_labels.h"
+#include "rdf_kernel_util.hpp"
 
 namespace {
 
@@ -25,7 +26,6 @@ constexpr int kAccThreads = 512;
 constexpr int kAccMaxBlocks = 512;
 constexpr int kUpdThreads = kMaxK * kMaxTries;      // one lane per (try, colour)
 constexpr int kFlatThreads = 256;
-typedef unsigned long long u64;
 
 // 4 pixels of group g as r | g << 8 | b << 16 each; pixels past the end read as black (skipped everywhere).
 // A full group is three aligned dwords; only the image's last, partial group is read by bytes.
@@ -82,13 +82,6 @@ __device__ __forceinline__ int nearest(const int *col, int K, uint32_t px, uint3
     }
     *cost = bd;
     return best;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);
-    return v;
 }
 
 // sums[t][k][5] += {pixels, sum r, sum g, sum b, sum cost} of the pixels nearest to colour k of try t.  DOUBLE_COST: word 4
@@ -254,9 +247,6 @@ __global__ void __launch_bounds__(kFlatThreads) k_depths_from_points(long long n
     depth[i] = !(z > 0.f) ? (uint16_t)0 : z >= 65535.f ? (uint16_t)65535 : (uint16_t)(uint32_t)z;
 }
 
-inline hipStream_t S(void *s) { return reinterpret_cast<hipStream_t>(s); }
-inline unsigned blocks(long long n, int per) { return (unsigned)((n + per - 1) / per); }
-inline bool misaligned(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 constexpr long long kMaxElems = 1ll << 31;
 
 inline unsigned accum_blocks(long long n_px)

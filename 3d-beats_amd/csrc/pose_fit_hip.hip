@@ -23,10 +23,10 @@
 #include <stdint.h>
 
 #include "../../include/rdf_labels.h"
+#include "rdf_kernel_util.hpp"
 
 namespace {
 
-typedef unsigned long long u64;
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kMaxDim = 32768;
@@ -40,16 +40,6 @@ static_assert(sizeof(RdfPoseFitState) == 256, "RdfPoseFitState is 256 bytes");
 static_assert(sizeof(RdfPoseFitConfig) == 1032, "RdfPoseFitConfig is 1032 bytes");
 
 // ------------------------------------------------------------------ rules P and K ------------------------------------------
-__host__ __device__ __forceinline__ uint32_t mix32(uint32_t x)
-{
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
 __host__ __device__ __forceinline__ double bits_to_double(u64 b)
 {
     double d;
@@ -241,31 +231,6 @@ __device__ __forceinline__ uint32_t observed_label(const CostGeo &g, const uint1
     return labels[(size_t)min(y / g.r, g.Hl - 1) * g.Wl + min(x / g.r, g.Wl - 1)];
 }
 
-__device__ __forceinline__ void unpack8(const uint4 v, uint32_t out[8])
-{
-    out[0] = v.x & 0xffffu; out[1] = v.x >> 16;
-    out[2] = v.y & 0xffffu; out[3] = v.y >> 16;
-    out[4] = v.z & 0xffffu; out[5] = v.z >> 16;
-    out[6] = v.w & 0xffffu; out[7] = v.w >> 16;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);
-    return v;
-}
-
-__device__ __forceinline__ u64 wave_sum64(u64 v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 64);
-        v += ((u64)hi << 32) | lo;
-    }
-    return v;
-}
-
 // Every index is inside its array: a window pixel idx < n_px gives (x, y) inside the window, the window is inside the frame
 // (checked by the host), and a label position is clamped to [0, Wl) x [0, Hl).
 template <bool R1>
@@ -356,12 +321,6 @@ __global__ void __launch_bounds__(kThreads) k_pose_cost(CostGeo g, const uint16_
 }
 
 // ------------------------------------------------------------------ rule S ------------------------------------------------
-__device__ __forceinline__ u64 shfl_xor64(u64 v, int m)
-{
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, 64);
-    return ((u64)hi << 32) | lo;
-}
-
 __global__ void __launch_bounds__(64) k_pose_select(int K, const u64 *__restrict__ terms, const double *__restrict__ poses,
                                                     uint32_t w_boundary, uint32_t w_label, int fresh_first,
                                                     RdfPoseFitState *__restrict__ state, u64 *__restrict__ history_slot)
@@ -405,10 +364,7 @@ __global__ void __launch_bounds__(64) k_pose_select(int K, const u64 *__restrict
 }
 
 // ------------------------------------------------------------------ host --------------------------------------------------
-inline hipStream_t S(void *s) { return reinterpret_cast<hipStream_t>(s); }
-inline bool misaligned(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 inline bool finite_d(double v) { return __builtin_fabs(v) <= 1.7e308; }
-inline bool finite_f(float v) { return __builtin_fabsf(v) <= 3.0e38f; }
 inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 struct Layout {

@@ -16,24 +16,21 @@
 #include <stdint.h>
 
 #include "../../include/rdf_labels.h"
+#include "rdf_kernel_util.hpp"
+#include "rdf_raster.hpp"
 
 namespace {
 
-typedef unsigned long long u64;
-constexpr u64 kEmptyKey = ~0ull;
 constexpr int kTileX = 64, kTileY = 4;                  // quads per workgroup
 constexpr int kVtxX = kTileX + 1, kVtxY = kTileY + 1;   // their corner points
 constexpr int kRasterThreads = kTileX * kTileY;
 constexpr int kFlatThreads = 256;
-constexpr int kSubPixel = 256, kHalfPixel = 128;        // 8 sub-pixel bits
-constexpr float kMaxSnapped = 1048576.f;                // 2^20
-constexpr int kMaxDim = 32768;                          // per axis: keeps 256 * dim in an int and the grid small
 constexpr int kCenterThreads = 256, kCenterMaxBlocks = 1024;
 constexpr uint32_t kHasPoint = 1u, kDrawable = 2u;      // vertex flags, bits 24 and 25 of Vtx::c
 
 struct Camera {
     float m[12];                    // the first three rows of obj_tform
-    float f, ppx, ppy, zmin, zmax;
+    Pinhole p;
 };
 
 struct Vtx {
@@ -42,107 +39,33 @@ struct Vtx {
     uint32_t c;                     // r | g << 8 | b << 16 | flags << 24
 };
 
-struct Tri {
-    int X[3], Y[3];
-    float z[3];
-    uint32_t c[3];
-    int sgn;                        // the sign of the area
-    int need[3];                    // e_k >= need[k]: 0 on a top or left edge, else 1
-};
-
-// rules 2 and 3
-__device__ __forceinline__ Vtx make_vertex(const float4 p, uint32_t rgb, const Camera &cam)
-{
-    const float *m = cam.m;
-    const float x = ((m[0] * p.x + m[1] * p.y) + m[2] * p.z) + m[3];
-    const float y = ((m[4] * p.x + m[5] * p.y) + m[6] * p.z) + m[7];
-    const float z = ((m[8] * p.x + m[9] * p.y) + m[10] * p.z) + m[11];
-    Vtx v;
-    v.X = v.Y = 0;
-    v.z = z;
-    uint32_t flags = p.w > 0.f ? kHasPoint : 0u;
-    if (z > 0.f) {
-        const float fx = floorf(((cam.f * x) / z + cam.ppx) * (float)kSubPixel + 0.5f);
-        const float fy = floorf(((cam.f * y) / z + cam.ppy) * (float)kSubPixel + 0.5f);
-        if (fabsf(fx) <= kMaxSnapped && fabsf(fy) <= kMaxSnapped) {     // (false for NaN)
-            v.X = (int)fx;
-            v.Y = (int)fy;
-            flags |= kDrawable;
-        }
-    }
-    v.c = rgb | (flags << 24);
-    return v;
-}
-
+// rules 2 and 3, with the point's colour and what rules 1 and 3 ask of it packed beside them
 __device__ __forceinline__ Vtx load_vertex(const float4 *__restrict__ pts, const uint8_t *__restrict__ color, long long at,
                                            const Camera &cam)
 {
+    const float4 p = pts[at];
     const uint8_t *c = color + at * 3;
-    return make_vertex(pts[at], (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16), cam);
+    const Snapped v = project_point(cam.m, p.x, p.y, p.z, cam.p);
+    const uint32_t flags = (p.w > 0.f ? kHasPoint : 0u) | (v.drawable ? kDrawable : 0u);
+    return {v.X, v.Y, v.z, (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | (flags << 24)};
 }
 
-__device__ __forceinline__ long long edge(int ax, int ay, int bx, int by, long long px, long long py)
+__device__ __forceinline__ bool all_drawable(const Vtx &a, const Vtx &b, const Vtx &c)
 {
-    return (long long)(bx - ax) * (py - ay) - (long long)(by - ay) * (px - ax);
+    return (((a.c & b.c & c.c) >> 24) & kDrawable) != 0u;
 }
 
-// rule 4, the part that does not depend on the pixel.  False: the triangle is dropped.
-__device__ __forceinline__ bool setup_triangle(const Vtx &a, const Vtx &b, const Vtx &c, Tri &t)
-{
-    if ((((a.c & b.c & c.c) >> 24) & kDrawable) == 0u) return false;
-    t.X[0] = a.X, t.X[1] = b.X, t.X[2] = c.X;
-    t.Y[0] = a.Y, t.Y[1] = b.Y, t.Y[2] = c.Y;
-    t.z[0] = a.z, t.z[1] = b.z, t.z[2] = c.z;
-    t.c[0] = a.c, t.c[1] = b.c, t.c[2] = c.c;
-    const long long area = edge(a.X, a.Y, b.X, b.Y, c.X, c.Y);
-    if (area == 0) return false;
-    t.sgn = area > 0 ? 1 : -1;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {       // edge k runs from vertex k + 1 to vertex k + 2, opposite vertex k
-        const int i0 = (k + 1) % 3, i1 = (k + 2) % 3;
-        const int dx = t.sgn * (t.X[i1] - t.X[i0]), dy = t.sgn * (t.Y[i1] - t.Y[i0]);
-        t.need[k] = (dy < 0 || (dy == 0 && dx > 0)) ? 0 : 1;
-    }
-    return true;
-}
-
-// rules 4 and 5 at pixel (i, j).  False: not covered, or discarded by the depth range.
-__device__ __forceinline__ bool fragment(const Tri &t, int i, int j, const Camera &cam, float *z, float q[3], float *s)
-{
-    const long long px = (long long)i * kSubPixel + kHalfPixel, py = (long long)j * kSubPixel + kHalfPixel;
-    float w[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int i0 = (k + 1) % 3, i1 = (k + 2) % 3;
-        const long long e = t.sgn * edge(t.X[i0], t.Y[i0], t.X[i1], t.Y[i1], px, py);
-        if (e < t.need[k]) return false;
-        w[k] = (float)e;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) q[k] = w[k] / t.z[k];
-    *s = (q[0] + q[1]) + q[2];
-    *z = ((w[0] + w[1]) + w[2]) / *s;
-    return *z >= cam.zmin && *z <= cam.zmax;
-}
-
-__device__ __forceinline__ int imin3(int a, int b, int c) { return min(a, min(b, c)); }
-__device__ __forceinline__ int imax3(int a, int b, int c) { return max(a, max(b, c)); }
-
-__device__ __forceinline__ void raster_triangle(const Vtx &a, const Vtx &b, const Vtx &c, u64 id, int W, int H,
+__device__ __forceinline__ void raster_triangle(const Vtx &a, const Vtx &b, const Vtx &c, uint32_t id, int W, int H,
                                                 const Camera &cam, u64 *__restrict__ keys)
 {
     Tri t;
-    if (!setup_triangle(a, b, c, t)) return;
-    // the pixels whose centre 256 i + 128 lies within [min, max] (>> floors, also below zero), clipped to the frame
-    const int i0 = max(0, (imin3(a.X, b.X, c.X) - kHalfPixel + kSubPixel - 1) >> 8);
-    const int i1 = min(W - 1, (imax3(a.X, b.X, c.X) - kHalfPixel) >> 8);
-    const int j0 = max(0, (imin3(a.Y, b.Y, c.Y) - kHalfPixel + kSubPixel - 1) >> 8);
-    const int j1 = min(H - 1, (imax3(a.Y, b.Y, c.Y) - kHalfPixel) >> 8);
-    for (int j = j0; j <= j1; ++j)
-        for (int i = i0; i <= i1; ++i) {
+    if (!setup_triangle(a, b, c, all_drawable(a, b, c), t)) return;
+    const PixelBox box = clipped_box(t, W, H);
+    for (int j = box.j0; j <= box.j1; ++j)
+        for (int i = box.i0; i <= box.i1; ++i) {
             float z, q[3], s;
-            if (!fragment(t, i, j, cam, &z, q, &s)) continue;
-            atomicMin(&keys[(long long)j * W + i], ((u64)__float_as_uint(z) << 32) | id);       // rule 6
+            if (!fragment(t, i, j, cam.p, &z, q, &s)) continue;
+            atomicMin(&keys[(long long)j * W + i], depth_key(z, id));       // rule 6
         }
 }
 
@@ -164,7 +87,7 @@ __global__ void __launch_bounds__(kRasterThreads) k_raster(int W, int H, const f
     const Vtx p00 = vs[ly * kVtxX + lx], p01 = vs[ly * kVtxX + lx + 1];
     const Vtx p10 = vs[(ly + 1) * kVtxX + lx], p11 = vs[(ly + 1) * kVtxX + lx + 1];
     if ((((p00.c & p01.c & p10.c & p11.c) >> 24) & kHasPoint) == 0u) return;       // rule 1
-    const u64 id = 2ull * ((u64)y * (u64)(W - 1) + (u64)x);
+    const uint32_t id = (uint32_t)(2ull * ((u64)y * (u64)(W - 1) + (u64)x));      // rule 1; below 2^32 at kMaxDim
     raster_triangle(p00, p01, p10, id, W, H, cam, keys);
     raster_triangle(p01, p10, p11, id + 1, W, H, cam, keys);
 }
@@ -190,7 +113,7 @@ __global__ void __launch_bounds__(kFlatThreads) k_resolve(int W, int H, const fl
     uint32_t r = 0u, g = 0u, b = 0u;
     if (key != kEmptyKey) {
         keys[p] = kEmptyKey;
-        const u64 id = key & 0xffffffffull;
+        const u64 id = key_id(key);
         const u64 n_tri = W > 1 && H > 1 ? 2ull * (u64)(W - 1) * (u64)(H - 1) : 0ull;
         if (id < n_tri) {
             const long long quad = (long long)(id >> 1), x = quad % (W - 1), y = quad / (W - 1);
@@ -199,13 +122,15 @@ __global__ void __launch_bounds__(kFlatThreads) k_resolve(int W, int H, const fl
             const Vtx v0 = load_vertex(pts, color, k ? at + 1 : at, cam);
             const Vtx v1 = load_vertex(pts, color, k ? at + W : at + 1, cam);
             const Vtx v2 = load_vertex(pts, color, k ? at + W + 1 : at + W, cam);
+            const uint32_t c[3] = {v0.c, v1.c, v2.c};
             Tri t;
             float z, q[3], s;
-            if (setup_triangle(v0, v1, v2, t) && fragment(t, (int)(p % W), (int)(p / W), cam, &z, q, &s)) {
-                d = z >= 65535.f ? (uint16_t)65535 : (uint16_t)(uint32_t)z;
-                r = channel(q, s, t.c, 0);
-                g = channel(q, s, t.c, 8);
-                b = channel(q, s, t.c, 16);
+            if (setup_triangle(v0, v1, v2, all_drawable(v0, v1, v2), t) &&
+                fragment(t, (int)(p % W), (int)(p / W), cam.p, &z, q, &s)) {
+                d = depth_u16(z);
+                r = channel(q, s, c, 0);
+                g = channel(q, s, c, 8);
+                b = channel(q, s, c, 16);
             }
         }
     }
@@ -262,10 +187,6 @@ __global__ void __launch_bounds__(kCenterThreads) k_center_final(int n_partial, 
     if (threadIdx.x < 4) sums[threadIdx.x] = sum;
 }
 
-inline hipStream_t S(void *s) { return reinterpret_cast<hipStream_t>(s); }
-inline unsigned blocks(long long n, int per) { return (unsigned)((n + per - 1) / per); }
-inline bool misaligned(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 inline int center_blocks(long long n)
 {
     const long long b = (n + kCenterThreads - 1) / kCenterThreads;
@@ -309,9 +230,9 @@ int rdf_rerender(int dim_x, int dim_y, const float *pts, const uint8_t *color, c
 {
     if (dim_x < 0 || dim_y < 0) return RDF_ERR_BAD_ARG;
     if (dim_x > kMaxDim || dim_y > kMaxDim) return RDF_ERR_TOO_LARGE;
-    if (!(f > 0.f) || !(zmin > 0.f) || !(zmax >= zmin) || !(zmax <= 3.0e38f) || !(fabsf(ppx) <= 3.0e38f) ||
-        !(fabsf(ppy) <= 3.0e38f) || !(f <= 3.0e38f))
-        return RDF_ERR_BAD_ARG;
+    Camera cam;
+    cam.p = {f, ppx, ppy, zmin, zmax};
+    if (!pinhole_ok(cam.p)) return RDF_ERR_BAD_ARG;
     const long long n_px = (long long)dim_x * dim_y;
     if (n_px == 0) return RDF_OK;
     if (!pts || !color || !obj_tform_host || !workspace || !depth_out || !color_out) return RDF_ERR_NULL_PTR;
@@ -319,9 +240,7 @@ int rdf_rerender(int dim_x, int dim_y, const float *pts, const uint8_t *color, c
         return RDF_ERR_BAD_ARG;
     const float *m = obj_tform_host;
     if (m[12] != 0.f || m[13] != 0.f || m[14] != 0.f || m[15] != 1.f) return RDF_ERR_BAD_ARG;      // affine only
-    Camera cam;
     for (int k = 0; k < 12; ++k) cam.m[k] = m[k];
-    cam.f = f, cam.ppx = ppx, cam.ppy = ppy, cam.zmin = zmin, cam.zmax = zmax;
     u64 *keys = static_cast<u64 *>(workspace);
     const float4 *p4 = reinterpret_cast<const float4 *>(pts);
     if (dim_x > 1 && dim_y > 1)

@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "../../include/rdf_labels.h"
+#include "rdf_kernel_util.hpp"
 
 namespace {
 
@@ -33,7 +34,6 @@ constexpr int kMaxBlocks = 512;       // larger calls stride over the grid
 constexpr int kMaxChunk = 16;
 constexpr int kMaxCells = (RDF_SCORE_MAX_CLASSES + 1) * (RDF_SCORE_MAX_CLASSES + 1);
 constexpr uint32_t kNoImage = 0xffffffffu;
-typedef unsigned long long u64;
 
 // label map [n][Hl][Wl] against truth [n][H][W] sampled at (x * r, y * r)
 struct Geometry {
@@ -46,21 +46,6 @@ struct Geometry {
     uint32_t pix_t;             // H * W
     uint32_t r;
 };
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);
-    return v;
-}
-
-__device__ __forceinline__ void unpack8(const uint4 v, uint32_t out[8])
-{
-    out[0] = v.x & 0xffffu; out[1] = v.x >> 16;
-    out[2] = v.y & 0xffffu; out[3] = v.y >> 16;
-    out[4] = v.z & 0xffffu; out[5] = v.z >> 16;
-    out[6] = v.w & 0xffffu; out[7] = v.w >> 16;
-}
 
 struct LaneSums {
     uint32_t dominant, equal, labelled;
@@ -264,8 +249,6 @@ __global__ void __launch_bounds__(kThreads) k_score(Geometry geo, int C, const u
     if (tid < 2 && tail_sums[1 + tid]) atomicAdd(counts + cells + tid, (u64)tail_sums[1 + tid]);
 }
 
-inline bool misaligned(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 template <bool R1, bool TRUTH_VEC>
 void launch(unsigned grid, hipStream_t stream, const Geometry &geo, int C, const uint16_t *pred, const uint16_t *truth,
             u64 *counts, uint32_t *per_image)
@@ -316,7 +299,7 @@ int rdf_score_labels(int n_img, int dim_x, int dim_y, int labels_reduce, int num
     grid = grid < 1u ? 1u : grid > (unsigned)kMaxBlocks ? (unsigned)kMaxBlocks : grid;
     geo.chunk = geo.n_groups / ((uint32_t)kThreads * grid);         // the trips every workgroup makes
     geo.chunk = geo.chunk < 1u ? 1u : geo.chunk > (uint32_t)kMaxChunk ? (uint32_t)kMaxChunk : geo.chunk;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t s = S(stream);
     u64 *c = reinterpret_cast<u64 *>(counts);
     if (labels_reduce != 1)
         launch<false, false>(grid, s, geo, num_classes, pred, truth, c, per_image);

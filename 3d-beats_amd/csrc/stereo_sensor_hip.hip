@@ -20,10 +20,10 @@
 #include <stdint.h>
 
 #include "../../include/rdf_labels.h"
+#include "rdf_kernel_util.hpp"
 
 namespace {
 
-typedef unsigned long long u64;
 constexpr int kThreads = 256;
 constexpr int kMaxDim = 32768;                          // per axis, as the renderer: a frame's pixels stay below 2^31
 constexpr int kMaxDisparity = 256;
@@ -43,16 +43,6 @@ constexpr int kTileRows = kTileY + 4;                   // rows of the LDS tile
 
 // bit layout of a left winner in the workspace: d* | (sub + 8) << 8 | not unique << 15
 constexpr int kSubShift = 8, kNotUniqueShift = 15;
-
-__device__ __forceinline__ uint32_t mix32(uint32_t x)
-{
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
 
 __device__ __forceinline__ uint32_t texel(uint32_t row, uint32_t u, uint32_t threshold)
 {
@@ -263,8 +253,6 @@ __global__ void __launch_bounds__(kThreads) k_stereo_resolve(long long n_total, 
     }
 }
 
-inline hipStream_t S(void *s) { return reinterpret_cast<hipStream_t>(s); }
-inline bool misaligned(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 inline unsigned blocks_for(long long n) { return (unsigned)min((n + kThreads - 1) / kThreads, (long long)kMaxGrid); }
 
 // what both entry points check alike; > 0: the batch's pixels, 0: no pixels, < 0: rejected

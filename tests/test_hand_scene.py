@@ -580,3 +580,76 @@ def test_camera_sequence_shows_a_finger_come_down_on_the_table(rdf, gpu_runtime)
     assert np.array_equal(depth, want)
     holes = r.camera_sequence(poses, plane, hole_rate=0.05, seed=3).get()
     assert 0.02 < (holes == 0).mean() < 0.08
+
+
+# ------------------------------------------------------------------ two rasterisers, one rule set --------------------------------
+_same = {}
+
+
+def _same_triangles():
+    """One grid of points as the re-render's frame and as the hand scene's mesh, and the two restatements' images.  67 x 6
+    points: the quads cross the re-render's 64-quad tile edge in x and its 4-quad edge in y.  Two points without w and one
+    behind the camera; an affine transform with a small rotation about y and a shift."""
+    if not _same:
+        import rerender_numpy as rn
+        W, H = 67, 6
+        f, ppx, ppy = 50., (W - 1) / 2., (H - 1) / 2.
+        rng = np.random.default_rng(67 * 6)
+        j, i = np.mgrid[:H, :W]
+        pts = np.empty((H, W, 4), np.float32)
+        pts[..., 0] = (i - ppx) * 60. + rng.uniform(-25., 25., (H, W))          # 60 units are one pixel at z = 3000
+        pts[..., 1] = (j - ppy) * 60. + rng.uniform(-25., 25., (H, W))
+        pts[..., 2] = 3000. + rng.uniform(-40., 40., (H, W))
+        pts[..., 3] = 1.
+        pts[2, 20, 3] = pts[4, 65, 3] = 0.
+        pts[1, 40, 2] = -3000.
+        a = np.deg2rad(4.)
+        M = np.array([[np.cos(a), 0., np.sin(a), 45.], [0., 1., 0., -20.], [-np.sin(a), 0., np.cos(a), 120.], [0., 0., 0., 1.]],
+                     np.float32)
+        color = rng.integers(0, 256, (H, W, 3)).astype(np.uint8)
+        # rule 1's triangles in rule 1's order, so that an index into tris is the re-render's triangle id
+        at = (j[:-1, :-1] * W + i[:-1, :-1]).reshape(-1)
+        tris = np.stack([np.stack([at, at + 1, at + W], 1), np.stack([at + 1, at + W, at + W + 1], 1)], 1)
+        has = pts[..., 3] > 0
+        quad = (has[:-1, :-1] & has[:-1, 1:] & has[1:, :-1] & has[1:, 1:]).reshape(-1)
+        tris[~quad] = 0                                                         # (0, 0, 0): no area, dropped
+        tris = tris.reshape(-1, 3)
+        mesh = (pts[..., :3].reshape(-1, 3).copy(), np.zeros(W * H, np.int32), tris.astype(np.int32),
+                np.ones(len(tris), np.uint16))
+        tforms = M[:3].reshape(1, 1, 12).copy()
+        cam = (f, ppx, ppy)
+        want_rr = rn.rerender(pts, color, M, *cam)
+        want_hs = hs.render(W, H, *mesh, tforms, None, *cam, empty_depth=0)
+        _same.update(W=W, H=H, pts=pts, color=color, M=M, mesh=mesh, tforms=tforms, cam=cam, want_rr=want_rr, want_hs=want_hs)
+    return _same
+
+
+def test_the_two_restatements_draw_the_same_triangles_alike():
+    c = _same_triangles()
+    depth_rr, depth_hs, labels_hs = c["want_rr"][0], c["want_hs"][0][0], c["want_hs"][1][0]
+    assert len(c["mesh"][2]) == 2 * (c["W"] - 1) * (c["H"] - 1) and (c["mesh"][2] == 0).all(1).sum() == 2 * 8     # four quads a point
+    drawn = int((depth_rr > 0).sum())
+    print(f"{drawn} of {depth_rr.size} pixels drawn")
+    assert 2 * drawn >= depth_rr.size and drawn < depth_rr.size
+    assert np.array_equal(depth_rr, depth_hs)
+    assert np.array_equal(labels_hs > 0, depth_rr > 0)
+
+
+@pytest.mark.gpu
+def test_rerender_and_hand_scene_draw_the_same_triangles_alike(rdf, gpu_runtime):
+    c = _same_triangles()
+    W, H = c["W"], c["H"]
+    rr = rdf.SceneRerender((H, W), c["cam"])
+    depth, out = rdf.DeviceArray((H, W), np.uint16).fill(7), rdf.DeviceArray((H, W, 3), np.uint8).fill(7)
+    rr.run(rdf.to_device(c["pts"]), rdf.to_device(c["color"]), c["M"], depth, out)
+    depth_rr = depth.get()
+    runs, _ = _render_raw(rdf, W, H, c["mesh"], c["tforms"], None, c["cam"], 0, 0, 0, 0)
+    depth_hs, labels_hs = runs[0][0][0], runs[0][1][0]
+    drawn = int((depth_rr > 0).sum())
+    print(f"{drawn} of {depth_rr.size} pixels drawn; {int((depth_rr != depth_hs).sum())} depths differ between the entry points, "
+          f"{int((depth_rr != c['want_rr'][0]).sum())} from the restatement")
+    assert 2 * drawn >= depth_rr.size
+    assert np.array_equal(depth_rr, depth_hs)
+    assert np.array_equal(depth_rr, c["want_rr"][0]) and np.array_equal(depth_hs, c["want_hs"][0][0])
+    assert np.array_equal(out.get(), c["want_rr"][1])
+    assert np.array_equal(labels_hs > 0, depth_rr > 0)
