@@ -34,13 +34,15 @@ LIBRARIES = {lib.key: lib for lib in (
             "rdf_frontend_"),
     # glove-colour recordings to training labels, the re-render that augments them, the score of predicted label maps, and
     # labelled frames of the articulated hand, the fit of that hand's pose to a labelled depth frame, and the stereo depth
-    # sensor that turns a left and a right render of those frames into what a camera would report
+    # sensor that turns a left and a right render of those frames into what a camera would report, and the refit of a trained
+    # forest's leaf distributions on such frames (its walk takes floor_i32 and add_wrap from the forest kernels' header)
     Library("labels", os.path.join(HERE, "csrc", "librdf_labels.so"),
             [os.path.join(HERE, "csrc", "labels_hip.hip"), os.path.join(HERE, "csrc", "rerender_hip.hip"),
              os.path.join(HERE, "csrc", "score_hip.hip"), os.path.join(HERE, "csrc", "hand_scene_hip.hip"),
-             os.path.join(HERE, "csrc", "pose_fit_hip.hip"), os.path.join(HERE, "csrc", "stereo_sensor_hip.hip")],
+             os.path.join(HERE, "csrc", "pose_fit_hip.hip"), os.path.join(HERE, "csrc", "stereo_sensor_hip.hip"),
+             os.path.join(HERE, "csrc", "forest_refit_hip.hip")],
             [os.path.join(HERE, "..", "include", "rdf_labels.h"), os.path.join(HERE, "csrc", "rdf_kernel_util.hpp"),
-             os.path.join(HERE, "csrc", "rdf_raster.hpp")], "rdf_labels_"),
+             os.path.join(HERE, "csrc", "rdf_raster.hpp"), os.path.join(HERE, "csrc", "rdf_device.hpp")], "rdf_labels_"),
 )}
 
 # No -ffast-math, no -fgpu-flush-denormals-to-zero: the fp32 divide must stay IEEE-correct

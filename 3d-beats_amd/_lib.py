@@ -220,6 +220,11 @@ BINDINGS = {
         "rdf_stereo_ir": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, StereoConfig, ctypes.c_uint32, _c_void_p, _c_void_p]),
         "rdf_stereo_sense": (_c_int, [_c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, StereoConfig, ctypes.c_uint32,
                                       ctypes.c_uint16, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+        "rdf_labels_refit_count": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_float,
+                                            _c_void_p, _c_void_p, _c_void_p]),
+        "rdf_labels_refit_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
+        "rdf_labels_refit_apply": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, ctypes.c_uint64, _c_int, _c_void_p,
+                                            _c_void_p, _c_void_p]),
         "rdf_labels_abi_version": (_c_int, []),
         "rdf_labels_build_id": (ctypes.c_char_p, []),
         "rdf_labels_error_string": (ctypes.c_char_p, [_c_int]),

@@ -213,8 +213,34 @@ def score_layered_model(config_filename, dataset_dir, num_images, labels_reduce=
     return scorer.add(composite, truth, labels_reduce, per_image=True).result()
 
 
+def _refit_on_dataset(forest, dataset_dir, num_images, min_count, fallback):
+    """Refit `forest` (a DecisionForest) on `num_images` random images of a dataset directory (0: all of them); returns the
+    LeafRefitter's report."""
+    from .device import DeviceArray
+    from .refit import LeafRefitter
+    num_images = num_images or DecisionTreeDatasetConfig(dataset_dir).total_available_images
+    ds = DecisionTreeDatasetConfig(dataset_dir, num_images=num_images, imgs_name='refit')
+    assert ds.num_classes() <= int(forest.num_classes), "the dataset has classes the forest does not have"
+    depth, labels = DeviceArray(ds.images_shape(), np.uint16), DeviceArray(ds.images_shape(), np.uint16)
+    ds.get_depth_block_cu(0, depth)
+    ds.get_labels_block_cu(0, labels)
+    return LeafRefitter(forest).add(depth, labels).apply(min_count, fallback)
+
+
+def refit_saved_model(model_path, dataset_dir, num_images, out_path, min_count=1, fallback='keep'):
+    """Leaf refit of a saved forest (refit.LeafRefitter): the model's leaf PDFs re-estimated on `num_images` random images (0: all) of
+    a dataset directory, read as score_saved_model reads them, and saved as the reference's .npy at `out_path`.  The tree
+    structure is the model's own.  Returns the report of LeafRefitter.apply."""
+    from .decision_tree import DecisionForest
+    forest = DecisionForest.load(model_path)
+    report = _refit_on_dataset(forest, dataset_dir, num_images, min_count, fallback)
+    np.save(out_path, forest.forest_cu.get())
+    return report
+
+
 def train_forest(dataset_dir, num_train, num_test, proposals, proposals_block, out_trees, max_depth, out_path=None,
-                 trees_to_try=None, train_block=None, log=print, tree_seed=None, group=None, device_score=False):
+                 trees_to_try=None, train_block=None, log=print, tree_seed=None, group=None, device_score=False,
+                 refit_dir=None, refit_images=0, refit_min_count=1, refit_fallback='keep'):
     """The flow of src/train_model.py:52-139 without its GLFW window: train `trees_to_try` candidate trees, keep
     the `out_trees` best by test accuracy, evaluate the forest, save it as the reference's .npy.
 
@@ -227,7 +253,12 @@ def train_forest(dataset_dir, num_train, num_test, proposals, proposals_block, o
     device_score (not in the reference): score every candidate and the forest with score.LabelScorer on the device instead
     of reading the test set's label maps back for a numpy comparison; the truth is not copied to the host either.  The log
     lines, the selection, the return value and the saved file are the same.  The forest's Score (confusion matrix, per-class
-    and per-image figures) is then kept as train_forest.last_score, None after a run without device_score."""
+    and per-image figures) is then kept as train_forest.last_score, None after a run without device_score.
+
+    refit_dir (not in the reference): the finished forest's leaf PDFs are re-estimated on `refit_images` random images (0: all) of that
+    dataset directory (refit.LeafRefitter, with refit_min_count and refit_fallback) before the forest is scored and saved:
+    train on clean renders, refit on what the camera reports.  The candidates are selected as trained.  Without it nothing
+    changes."""
     from .decision_tree import DecisionForest, DecisionTree, DecisionTreeEvaluator, DecisionTreeTrainer
     from .device import DeviceArray
     from .util import MAX_UINT16
@@ -286,6 +317,11 @@ def train_forest(dataset_dir, num_train, num_test, proposals, proposals_block, o
             forest_cpu[slot] = tree_np
     forest = DecisionForest(out_trees, max_depth, test_data.num_classes())
     forest.forest_cu.set(forest_cpu)
+    if refit_dir is not None:
+        report = _refit_on_dataset(forest, refit_dir, refit_images, refit_min_count, refit_fallback)
+        forest_cpu = forest.forest_cu.get()
+        log(f'refit on {refit_images or "all"} images: {report["own"]} of {report["leaf_slots"]} leaf slots from their own counts, '
+            f'{report["ancestor"]} from an ancestor, {report["kept"]} kept')
     out_cu.fill(MAX_UINT16)
     evaluator.get_labels_forest(forest, test_depth, out_cu)
     if device_score:

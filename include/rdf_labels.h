@@ -14,6 +14,8 @@
  * selected on the device, the reference's pose_fit.py and cuda/fit_mesh.cu.
  * And what a stereo depth camera makes of those frames (rdf_stereo_sense): a left and a right render through a projected dot
  * pattern, a census transform and a block matcher, integer like the colour kernels.
+ * And the leaf refit (rdf_labels_refit_count, rdf_labels_refit_apply): a trained forest's leaf distributions re-estimated
+ * from labelled frames, in integer counts.
  *
  * It is a library of its own, next to librdf_hip.so and librdf_frontend.so, with its own ABI number and build id.
  * Conventions are those of rdf_hip.h: every pointer is caller-owned DEVICE memory; nothing is allocated, freed or
@@ -48,7 +50,7 @@ extern "C" {
 /*
  * 1: first version.  The number changes when something declared here is removed or re-typed; a pure addition (as
  * rdf_points_center, rdf_rerender, rdf_hand_scene_render and the pose fit -- rdf_pose_cost, rdf_pose_propose, rdf_pose_select,
- * rdf_pose_fit_workspace_bytes and rdf_pose_fit -- and the stereo sensor's three were) keeps it, since every caller of the older entry points still links and runs.
+ * rdf_pose_fit_workspace_bytes and rdf_pose_fit --, the stereo sensor's three and the leaf refit's three were) keeps it, since every caller of the older entry points still links and runs.
  * Two builds with the same number are told apart by rdf_labels_build_id().
  */
 #define RDF_LABELS_ABI_VERSION 1
@@ -474,6 +476,66 @@ int rdf_stereo_sense(int n_frames, int dim_x, int dim_y, const uint16_t *depth_l
                      const uint16_t *depth_r, RdfStereoConfig config, uint32_t seed, uint16_t empty_depth, void *workspace,
                      uint16_t *depth_out, uint16_t *labels_out, uint8_t *ir_out, uint16_t *dq_out, uint8_t *reason_out,
                      void *stream);
+
+/*
+ * Leaf refit: the leaf distributions of a trained forest re-estimated from labelled depth frames -- the frames the camera
+ * will really deliver, or more of them than the trainer can hold -- while the tree structure stays as it is.  The reference
+ * has no counterpart; the rules below are this library's own, tests/refit_numpy.py restates them, and the kernels match that
+ * bit for bit: every count is an integer, so no result depends on the order in which pixels are visited.
+ *
+ *   forest  float32 [T][N][E], N = 2^D - 1 nodes in heap order, E = 7 + 2C: the reference layout, what rdf_eval_forest takes
+ *           (ux, uy, vx, vy, thresh, l_next, r_next, l_pdf[C], r_pdf[C]).  1 <= T, 1 <= D <= 30, 1 <= C <= 65535.
+ *   slot    (t, n, s): side s (0 left, 1 right) of node n of tree t.  It is a LEAF SLOT iff floor(rec[5 + s]) != -1 with the
+ *           floor of rule R2 -- the test inference makes, at every level, D - 1 included.
+ *   counts  uint64 [T][N][2][C];  totals uint64 [4].  Both 8-byte aligned.
+ *
+ * R1. Pixels (rdf_labels_refit_count).  depth, labels uint16 [n_img][dim_y][dim_x].  For every pixel, with l its label and
+ *     d its depth:  l == 0: ignored.  l >= C: totals[1] += 1, ignored.  d == 0 or d == 65535: totals[2] += 1, ignored (what
+ *     inference skips: a leaf's PDF only matters for pixels inference evaluates).  Else totals[0] += 1 and the pixel walks
+ *     every tree from the root.
+ * R2. The walk, as inference walks (rdf_eval_forest): at node rec, for each of the offsets o = rec[0..3], q = floor((scale_factor
+ *     * o) / (float)d) -- one multiply and one IEEE divide, each rounded to nearest, then floor to int32 with saturation and NaN
+ *     -> 0; the probes are at (x + q_ux, y + q_uy) and (x + q_vx, y + q_vy), the adds wrapping in int32; a probe outside
+ *     [0, dim_x) x [0, dim_y), checked per axis (no wrap into the next row or image), reads 65535.0, any other reads the
+ *     frame's value as a float, a 0 included; f = du - dv.  f < rec[4] goes to side 0, anything else (NaN included) to side
+ *     1.  If that side is a leaf slot, counts[t][n][s][l] += 1 and the walk ends; else it goes on at child 2g + s of the
+ *     next level (g the node's index within its level), and if there is no next level totals[3] += 1 and nothing is counted.
+ *     So counts sums to T * totals[0] - totals[3].
+ *     The call ADDS onto counts and totals; the caller zeroes them (as rdf_score_labels).  A negative dimension, T, D or C
+ *     outside the ranges above or a misaligned pointer is RDF_ERR_BAD_ARG; zero pixels is a successful no-op; else a NULL
+ *     pointer is RDF_ERR_NULL_PTR; n_img * dim_y * dim_x >= 2^31 (callers split the batch by images) or N * 2 * C >= 2^32 is
+ *     RDF_ERR_TOO_LARGE.  Rejected arguments leave counts and totals untouched.
+ *     One launch, nothing read back.  A wave whose 64 pixels carry no label does nothing.  Leaf slots of the first L levels
+ *     (L the largest with T * (2^L - 1) * 2 * C <= 4096) are counted in a 32-bit LDS histogram that a workgroup adds to counts
+ *     once; below that the lanes of a wave that reached the same (slot, class) share one add, into a hashed table of 2048
+ *     (cell, count) pairs in LDS that a workgroup also adds to counts once, or, where another cell holds the bucket, as a
+ *     64-bit atomic straight into counts.
+ * R3. PDFs (rdf_labels_refit_apply).  A leaf slot is REACHABLE iff every ancestor's flag on the way to it floors to -1.  The
+ *     call rewrites rec[7 + s * C + c], c = 0..C-1, of reachable leaf slots and nothing else: rec[0..6], unreachable nodes and
+ *     "go on" sides keep their bytes.  With S the sum of the slot's own counts over the classes and min_count >= 1:
+ *       S >= min_count:  pdf[c] = (float)cnt[c] / (float)S -- uint64 to fp32 rounded to nearest even, one IEEE divide, the
+ *                        trainer's expression.  No pixel has label 0, so entry 0 is 0.
+ *       else, fallback RDF_REFIT_FALLBACK_KEEP:  the old entries stay, bit for bit.
+ *       else, RDF_REFIT_FALLBACK_ANCESTOR:  sub[t][a][c] = over both sides s of node a, cnt[t][a][s][c] where (a, s) is a leaf
+ *                        slot, else sub[t][child 2g + s][c], else (level D - 1) nothing: the class counts of the leaf slots
+ *                        below a, in integers.  Of the chain n, parent(n), ..., root the nearest a with Z = sum_c sub[t][a][c]
+ *                        >= min_count gives pdf[c] = (float)sub[t][a][c] / (float)Z; if not even the root has that many, the
+ *                        old entries stay.
+ *     report uint64 [4], overwritten: leaf slots written from their own counts, written from an ancestor, kept, and reachable
+ *     leaf slots (the sum of the three).  workspace: rdf_labels_refit_workspace_bytes(T, D, C) bytes (0 for a rejected
+ *     shape), 8-byte aligned, contents irrelevant before and after.  min_count == 0, an unknown fallback, a shape outside the
+ *     ranges or a misaligned pointer is RDF_ERR_BAD_ARG, else a NULL pointer RDF_ERR_NULL_PTR; nothing is launched then.
+ *     One launch per level top-down, after one per level bottom-up with the ancestor fallback; stream-ordered, nothing read
+ *     back.  A packed table made of this forest (rdf_forest_pack) holds the old PDFs: pack again.
+ */
+#define RDF_REFIT_FALLBACK_KEEP 0
+#define RDF_REFIT_FALLBACK_ANCESTOR 1
+int rdf_labels_refit_count(const uint16_t *depth, const uint16_t *labels, int n_img, int dim_x, int dim_y, const float *forest,
+                           int n_trees, int max_depth, int n_classes, float scale_factor, uint64_t *counts, uint64_t *totals,
+                           void *stream);
+size_t rdf_labels_refit_workspace_bytes(int n_trees, int max_depth, int n_classes);
+int rdf_labels_refit_apply(float *forest, int n_trees, int max_depth, int n_classes, const uint64_t *counts, uint64_t min_count,
+                           int fallback, void *workspace, uint64_t *report, void *stream);
 
 int rdf_labels_abi_version(void);
 const char *rdf_labels_build_id(void);
