@@ -11,7 +11,7 @@ SRC = os.path.join(HERE, "csrc", "rdf_hip.hip")
 SOURCES = [SRC, os.path.join(HERE, "csrc", "mean_shift_hip.hip"), os.path.join(HERE, "csrc", "points_ops_hip.hip"),
            os.path.join(HERE, "csrc", "tree_train_hip.hip"), os.path.join(HERE, "csrc", "grouping_hip.hip")]
 HEADERS = [os.path.join(HERE, "..", "include", "rdf_hip.h"), os.path.join(HERE, "csrc", "rdf_device.hpp"),
-           os.path.join(HERE, "csrc", "rdf_host_state.hpp")]
+           os.path.join(HERE, "csrc", "rdf_host_state.hpp"), os.path.join(HERE, "csrc", "rdf_kernel_util.hpp")]
 SO = os.path.join(HERE, "csrc", "librdf_hip.so")
 
 
@@ -35,7 +35,8 @@ LIBRARIES = {lib.key: lib for lib in (
     # glove-colour recordings to training labels, the re-render that augments them, the score of predicted label maps, and
     # labelled frames of the articulated hand, the fit of that hand's pose to a labelled depth frame, and the stereo depth
     # sensor that turns a left and a right render of those frames into what a camera would report, and the refit of a trained
-    # forest's leaf distributions on such frames (its walk takes floor_i32 and add_wrap from the forest kernels' header)
+    # forest's leaf distributions on such frames (its walk takes the reference-layout feature step -- the offset coordinate and
+    # the bounds-checked read -- from rdf_device.hpp, the forest and training kernels' header)
     Library("labels", os.path.join(HERE, "csrc", "librdf_labels.so"),
             [os.path.join(HERE, "csrc", "labels_hip.hip"), os.path.join(HERE, "csrc", "rerender_hip.hip"),
              os.path.join(HERE, "csrc", "score_hip.hip"), os.path.join(HERE, "csrc", "hand_scene_hip.hip"),

@@ -14,7 +14,7 @@
 //     sees < 2^31 pixels) and a workgroup adds each non-zero cell to global memory once, at its end: atomics of a million
 //     waves on one cache line would run at about 90 per microsecond.
 //   - deeper leaf slots: the lanes of a wave that hold the same (slot, class) key go through ONE add, for the first
-//     kAggIters distinct keys of the wave (as k_train_sort of tree_train_hip.hip does); the lanes left after that hold keys
+//     kAggIters distinct keys of the wave (wave_key_group, as in the trainer's k_train_sort); the lanes left after that hold keys
 //     of their own -- at depth a wave's 64 pixels sit in up to 64 slots -- and add 1 each.  An add goes to the workgroup's
 //     table of 2048 (cell, count) pairs in LDS, hashed by the cell's index in counts, when the cell's bucket is free or its
 //     own, else to global memory as a 64-bit atomic: whatever the forest's shape, the slots that take most pixels end up in
@@ -52,13 +52,6 @@ struct CountArgs {
     float scale;
     u64 *counts, *totals;
 };
-
-// Array3d::get with the default 65535: per-axis bounds check, no wrap into the next row or image
-__device__ __forceinline__ float probe(const uint16_t *__restrict__ frame, int W, int H, int x, int y)
-{
-    if ((uint32_t)x >= (uint32_t)W || (uint32_t)y >= (uint32_t)H) return (float)kNoPixel;
-    return (float)frame[(uint32_t)y * (uint32_t)W + (uint32_t)x];
-}
 
 // n pixels of one (slot, class) below the histogram's levels: cell = its index in counts.  The workgroup's table takes it
 // when the cell's bucket is free or already the cell's own; a bucket that another cell holds sends it to global memory.
@@ -132,9 +125,9 @@ __global__ void __launch_bounds__(kThreads) k_refit_count(const CountArgs a)
                 const float s = a.scale;
                 // `uv_scale * u.x / d_f`: one multiply and one IEEE divide, both rounded to nearest (no contraction, no
                 // reciprocal: the library's flags); floor with saturation, NaN -> 0; a wrapping add
-                const int ux = add_wrap(x, floor_i32((s * rec[0]) / df)), uy = add_wrap(y, floor_i32((s * rec[1]) / df));
-                const int vx = add_wrap(x, floor_i32((s * rec[2]) / df)), vy = add_wrap(y, floor_i32((s * rec[3]) / df));
-                const float f = probe(frame, a.W, a.H, ux, uy) - probe(frame, a.W, a.H, vx, vy);
+                const int ux = offset_coord(x, s * rec[0], df), uy = offset_coord(y, s * rec[1], df);
+                const int vx = offset_coord(x, s * rec[2], df), vy = offset_coord(y, s * rec[3], df);
+                const float f = depth_or_no_pixel<uint32_t>(frame, a.W, a.H, ux, uy) - depth_or_no_pixel<uint32_t>(frame, a.W, a.H, vx, vy);
                 const uint32_t side = f < rec[4] ? 0u : 1u;         // NaN goes right
                 if (floor_i32(rec[5 + side]) != -1) {               // a leaf slot, at every level
                     walking = false;
@@ -155,12 +148,10 @@ __global__ void __launch_bounds__(kThreads) k_refit_count(const CountArgs a)
             if (todo == 0ull) continue;
             const size_t cell0 = (size_t)t * N * 2u * (size_t)C;   // of the tree's first cell in counts
             for (int it = 0; it < kAggIters && todo != 0ull; ++it) {
-                const int src = __ffsll((long long)todo) - 1;
-                const uint32_t k0 = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)key, src, 64));
-                const u64 m = __ballot(has_key && key == k0);
-                if (lane == src) add_deep(tags, vals, use_table, a.counts, cell0 + k0, (uint32_t)__popcll(m));
-                if (has_key && key == k0) has_key = false;
-                todo &= ~m;
+                const KeyGroup grp = wave_key_group(todo, (int)key, has_key);
+                if (lane == grp.src) add_deep(tags, vals, use_table, a.counts, cell0 + (uint32_t)grp.key, (uint32_t)__popcll(grp.lanes));
+                if (has_key && key == (uint32_t)grp.key) has_key = false;
+                todo &= ~grp.lanes;
             }
             if (has_key) add_deep(tags, vals, use_table, a.counts, cell0 + key, 1u);   // deep levels: every pixel a slot of its own
         }

@@ -1,7 +1,7 @@
-// rdf_device.hpp -- device helpers shared by the forest-evaluation and the training kernels:
-// the reference's __float2int_rd, wrapping coordinate adds, the verified shared-reciprocal divide, the
-// two-source depth probe (staged LDS tile / global memory) in its round-1 form (ProbeCtx) and in round 3's (TileCtx: tile at
-// LDS address 0, x doubled), the rounding-mode switches of the one-fma divide-and-floor.
+// rdf_device.hpp -- device helpers shared by the forest-evaluation, the training and the refit kernels:
+// the reference's __float2int_rd, wrapping coordinate adds and the reference-layout feature step built from them, the
+// two-source depth probe (staged LDS tile / global memory; TileCtx: tile at LDS address 0, x doubled) and the rounding-mode
+// switches of the one-fma divide-and-floor.  (The probe's round-1 form is in tree_train_hip.hip, its only user.)
 #ifndef RDF_DEVICE_HPP
 #define RDF_DEVICE_HPP
 
@@ -24,77 +24,17 @@ __device__ __forceinline__ int floor_i32(float f)
     return r;
 }
 
-// Same result for every non-NaN input (checked on gfx950, tests/test_gpu_parity.py); one VALU op.
-__device__ __forceinline__ int floor_i32_not_nan(float f)
-{
-    int r;
-    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(r) : "v"(f));
-    return r;
-}
-
 __device__ __forceinline__ int add_wrap(int a, int b) { return (int)((uint32_t)a + (uint32_t)b); }
 
-// floor((a.x)/d), floor((a.y)/d) for a pair of numerators with the pixel's refined reciprocal rcp2 = (r, r),
-// ndf2 = (-d, -d): q0 = a*r; rem = a - d*q0 (exact, fma); q = q0 + rem*r.  Equal to the IEEE divide in
-// floor-to-int for every depth 1..65535 and every numerator that is +-0 or has a biased exponent in
-// [40, 230] (tools/verify_fastdiv.hip, exhaustive on gfx950).  Packed f32: two quotients per instruction.
-__device__ __forceinline__ f2 fast_quotient2(f2 a, f2 rcp2, f2 ndf2)
+// The feature step on the reference's layout: a probe's coordinate is the pixel's plus floor(o / d) (a caller with a scale
+// multiplies o first), and Array3d::get answers 65535 outside the frame: per-axis bounds check, no wrap into the next row or image.
+// Index: uint32_t where the caller's entry point has checked W * H < 2^32 (two instructions fewer in a level loop), else size_t.
+__device__ __forceinline__ int offset_coord(int x, float o, float df) { return add_wrap(x, floor_i32(o / df)); }
+template <typename Index>
+__device__ __forceinline__ float depth_or_no_pixel(const uint16_t *__restrict__ frame, int W, int H, int x, int y)
 {
-    const f2 q0 = a * rcp2;
-    return __builtin_elementwise_fma(__builtin_elementwise_fma(ndf2, q0, a), rcp2, q0);
-}
-
-__device__ __forceinline__ bool fast_divide_ok(float a)   // the verified numerator range
-{
-    const uint32_t b = __float_as_uint(a);
-    return (b << 1) == 0u || (((b >> 23) & 0xFFu) - 40u) <= 190u;
-}
-
-// A depth probe at (x, y) of the current image is answered by the staged LDS tile when the coordinate
-// falls inside it (cells outside the image already hold 65535), else by global memory with the
-// per-axis bounds check of cu_utils.hpp:79-86.  The loads are only ISSUED here; their values are
-// consumed after all probes of the level have been issued, so every probe of a level is in flight
-// together and nothing waits inside a divergent branch (an earlier version waited vmcnt(0) per probe).
-// `img_b` is the wave-uniform base of the current image (a scalar register pair, so a far probe's address is
-// one 32-bit byte offset: a call addresses < 2^31 pixels); multiplies are 24-bit (full rate; every factor is
-// < 2^24 when used).  tile[-1] must hold 65535: lanes that leave the tile read that cell, so a probe outside
-// the image needs no separate constant.
-struct ProbeCtx {
-    const uint16_t *tile;   // LDS; tile[-1] == 65535
-    const char *img_b;
-    int tx0, ty0, tw, th, twp, W, H;
-};
-
-struct Probe {
-    uint32_t lds_v, glb_v;   // the two candidate values
-    bool from_global;
-};
-
-// (cx, cy) = probe position RELATIVE TO THE STAGED TILE (the caller adds the offsets to the pixel's own
-// tile-relative position); image coordinates are only rebuilt for lanes that leave the tile.
-__device__ __forceinline__ Probe probe_issue(const ProbeCtx &c, int cx, int cy)
-{
-    const bool in_tile = (uint32_t)cx < (uint32_t)c.tw && (uint32_t)cy < (uint32_t)c.th;
-    const int li = in_tile ? (int)(__umul24((uint32_t)cy, (uint32_t)c.twp) + (uint32_t)cx) : -1;
-    uint32_t undefined;
-    asm("" : "=v"(undefined));   // glb_v is only read where from_global is set
-    Probe p = {c.tile[li], undefined, false};
-    if (!in_tile) {
-        const int x = add_wrap(cx, c.tx0), y = add_wrap(cy, c.ty0);
-        if ((uint32_t)x < (uint32_t)c.W && (uint32_t)y < (uint32_t)c.H) {
-            // only far lanes touch global memory; the value is consumed after the branch
-            const uint32_t go = (__umul24((uint32_t)y, (uint32_t)c.W) + (uint32_t)x) << 1;
-            p.glb_v = *reinterpret_cast<const uint16_t *>(c.img_b + go);
-            p.from_global = true;
-        }
-    }
-    return p;
-}
-
-__device__ __forceinline__ int probe_value(const Probe &p)
-{
-    const uint32_t g = p.glb_v, l = p.lds_v;
-    return (int)(p.from_global ? g : l);
+    if ((uint32_t)x >= (uint32_t)W || (uint32_t)y >= (uint32_t)H) return (float)kNoPixel;
+    return (float)frame[(Index)y * (Index)W + (Index)x];
 }
 
 // ---- round 3: divide, floor and add in one fma (rdf_hip.hip, NodeRec16; tools/verify_magic.hip) ----

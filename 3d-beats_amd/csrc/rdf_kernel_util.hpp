@@ -1,7 +1,7 @@
-// rdf_kernel_util.hpp -- the small helpers that the sources of librdf_labels.so and librdf_frontend.so have in common: the
-// 32-bit mix behind every hash rule of include/rdf_labels.h, the wave-wide sums and the 64-bit shuffle, the unpacking of
-// eight 16-bit pixels, and the host one-liners of the entry points.  A helper that only one file uses stays in that file;
-// so do constants that mean different things in different files (kThreads, kMaxGrid*).
+// rdf_kernel_util.hpp -- the small helpers that sources of the three libraries have in common: the 32-bit mix behind every
+// hash rule of include/rdf_labels.h, the wave-wide sums and the 64-bit shuffle, the lanes of a wave that share a key, the
+// unpacking of eight 16-bit pixels, and the host one-liners of the entry points.  A helper that only one file uses stays in
+// that file; so do constants that mean different things in different files (kThreads, kMaxGrid*).
 #ifndef RDF_KERNEL_UTIL_HPP
 #define RDF_KERNEL_UTIL_HPP
 
@@ -43,6 +43,16 @@ __device__ __forceinline__ u64 wave_sum64(u64 v)
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v += shfl_xor64(v, m);
     return v;
+}
+
+// The lanes of the wave that hold the first pending lane's key.  `pending` is wave-uniform and not zero; `has` says whether
+// this lane holds a key at all.  A wave that serves its keys group by group clears `lanes` from `pending` after each.
+struct KeyGroup { int src, key; u64 lanes; };   // the first pending lane, its key (both wave-uniform), the lanes that hold it
+__device__ __forceinline__ KeyGroup wave_key_group(u64 pending, int key, bool has)
+{
+    const int src = __ffsll((long long)pending) - 1;
+    const int k0 = __builtin_amdgcn_readfirstlane(__shfl(key, src, 64));
+    return {src, k0, __ballot(has && key == k0)};
 }
 
 // eight uint16 pixels of one 16-byte load

@@ -29,10 +29,10 @@
 
 #include "../../include/rdf_hip.h"
 #include "rdf_device.hpp"
+#include "rdf_kernel_util.hpp"
 
 namespace {
 
-typedef unsigned long long u64;
 constexpr int kHalo = 16;
 // A wave covers a kBW x kBH block of pixels rather than a 64 x 1 row segment: pixels of the same (node, class) are
 // compact in 2-D, so a block holds fewer distinct groups -- and issues fewer atomics -- than a strip.  The
@@ -53,6 +53,47 @@ constexpr int kBatch = 4;                     // proposals evaluated together: 8
 // (SQ_WAVE_CYCLES / GRBM_GUI_ACTIVE, level 0: 3.2 ms against a 1.4 ms VALU floor).
 __device__ unsigned int g_train_queue[2];
 
+// ---- the tile front end of k_train_histogram and k_train_bits (each pulls its tile itself: a static word there, the mailbox here) ----
+struct TilePos { size_t img_off; int x, y, tx0, ty0; };   // the image's first pixel; the lane's pixel and the staged tile's first cell in it
+template <int HALO>
+__device__ __forceinline__ TilePos tile_decode(uint32_t tile, uint32_t tiles_x, uint32_t tiles_y, int W, int H, int lane, int wave)
+{
+    const uint32_t per = tiles_x * tiles_y;
+    const uint32_t img = tile / per, rem = tile - img * per;
+    const uint32_t ty = rem / tiles_x, tx = rem - ty * tiles_x;
+    return {(size_t)img * ((uint32_t)W * (uint32_t)H), (int)(tx * kCols) + wave * kBW + (lane % kBW), (int)(ty * kRows) + lane / kBW,
+            (int)(tx * kCols) - HALO, (int)(ty * kRows) - HALO};
+}
+// the depth tile with its halo into LDS, 65535 outside the image; a wave takes every fourth row
+template <int TW, int TH>
+__device__ __forceinline__ void tile_stage(uint16_t *s_tile, const uint16_t *depth, const TilePos &t, int W, int H, int lane, int wave)
+{
+    for (int row = wave; row < TH; row += 4) {
+        const int gy = t.ty0 + row;
+        const bool row_in = (uint32_t)gy < (uint32_t)H;
+        for (int col = lane; col < TW; col += 64) {
+            const int gx = t.tx0 + col;
+            uint32_t v = kNoPixel;
+            if (row_in && (uint32_t)gx < (uint32_t)W) v = depth[t.img_off + (size_t)gy * W + gx];
+            s_tile[row * TW + col] = (uint16_t)v;
+        }
+    }
+}
+// the pixel's reciprocal for the one-reciprocal divides: v_rcp_f32 and one Newton step, both in round-to-nearest
+__device__ __forceinline__ float refined_rcp(float df)
+{
+    const float r0 = __builtin_amdgcn_rcpf(df);
+    return __builtin_fmaf(__builtin_fmaf(-df, r0, 1.0f), r0, r0);
+}
+// one thread of every workgroup, after its final, failing pull: the last workgroup of the launch puts the queue back to zero
+__device__ __forceinline__ void tile_queue_done()
+{
+    if (atomicAdd(&g_train_queue[1], 1u) == gridDim.x - 1u) {
+        atomicExch(&g_train_queue[0], 0u);
+        atomicExch(&g_train_queue[1], 0u);
+    }
+}
+
 // ---- root counts + nodes_by_pixel initialisation (decision_tree.py:452-468, done on the host there) ----
 __global__ __launch_bounds__(256) void k_train_init(const uint16_t *labels, size_t n_px, int C, int32_t *nodes, u64 *root)
 {
@@ -66,6 +107,78 @@ __global__ __launch_bounds__(256) void k_train_init(const uint16_t *labels, size
     }
     __syncthreads();
     if (threadIdx.x < C && s_cnt[threadIdx.x]) atomicAdd(root + threadIdx.x, (u64)s_cnt[threadIdx.x]);
+}
+
+// ---- the histogram kernel's divide and depth probe in their round-1 form (k_train_bits uses round 3's, rdf_device.hpp) ----
+// Same result for every non-NaN input (checked on gfx950, tests/test_gpu_parity.py); one VALU op.
+__device__ __forceinline__ int floor_i32_not_nan(float f)
+{
+    int r;
+    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(r) : "v"(f));
+    return r;
+}
+
+// floor((a.x)/d), floor((a.y)/d) for a pair of numerators with the pixel's refined reciprocal rcp2 = (r, r),
+// ndf2 = (-d, -d): q0 = a*r; rem = a - d*q0 (exact, fma); q = q0 + rem*r.  Equal to the IEEE divide in
+// floor-to-int for every depth 1..65535 and every numerator that is +-0 or has a biased exponent in
+// [40, 230] (tools/verify_fastdiv.hip, exhaustive on gfx950).  Packed f32: two quotients per instruction.
+__device__ __forceinline__ f2 fast_quotient2(f2 a, f2 rcp2, f2 ndf2)
+{
+    const f2 q0 = a * rcp2;
+    return __builtin_elementwise_fma(__builtin_elementwise_fma(ndf2, q0, a), rcp2, q0);
+}
+
+__device__ __forceinline__ bool fast_divide_ok(float a)   // the verified numerator range
+{
+    const uint32_t b = __float_as_uint(a);
+    return (b << 1) == 0u || (((b >> 23) & 0xFFu) - 40u) <= 190u;
+}
+
+// A depth probe at (x, y) of the current image is answered by the staged LDS tile when the coordinate
+// falls inside it (cells outside the image already hold 65535), else by global memory with the
+// per-axis bounds check of cu_utils.hpp:79-86.  The loads are only ISSUED here; their values are
+// consumed after all probes of the level have been issued, so every probe of a level is in flight
+// together and nothing waits inside a divergent branch (an earlier version waited vmcnt(0) per probe).
+// `img_b` is the wave-uniform base of the current image (a scalar register pair, so a far probe's address is
+// one 32-bit byte offset: a call addresses < 2^31 pixels); multiplies are 24-bit (full rate; every factor is
+// < 2^24 when used).  tile[-1] must hold 65535: lanes that leave the tile read that cell, so a probe outside
+// the image needs no separate constant.
+struct ProbeCtx {
+    const uint16_t *tile;   // LDS; tile[-1] == 65535
+    const char *img_b;
+    int tx0, ty0, tw, th, twp, W, H;
+};
+
+struct Probe {
+    uint32_t lds_v, glb_v;   // the two candidate values
+    bool from_global;
+};
+
+// (cx, cy) = probe position RELATIVE TO THE STAGED TILE (the caller adds the offsets to the pixel's own
+// tile-relative position); image coordinates are only rebuilt for lanes that leave the tile.
+__device__ __forceinline__ Probe probe_issue(const ProbeCtx &c, int cx, int cy)
+{
+    const bool in_tile = (uint32_t)cx < (uint32_t)c.tw && (uint32_t)cy < (uint32_t)c.th;
+    const int li = in_tile ? (int)(__umul24((uint32_t)cy, (uint32_t)c.twp) + (uint32_t)cx) : -1;
+    uint32_t undefined;
+    asm("" : "=v"(undefined));   // glb_v is only read where from_global is set
+    Probe p = {c.tile[li], undefined, false};
+    if (!in_tile) {
+        const int x = add_wrap(cx, c.tx0), y = add_wrap(cy, c.ty0);
+        if ((uint32_t)x < (uint32_t)c.W && (uint32_t)y < (uint32_t)c.H) {
+            // only far lanes touch global memory; the value is consumed after the branch
+            const uint32_t go = (__umul24((uint32_t)y, (uint32_t)c.W) + (uint32_t)x) << 1;
+            p.glb_v = *reinterpret_cast<const uint16_t *>(c.img_b + go);
+            p.from_global = true;
+        }
+    }
+    return p;
+}
+
+__device__ __forceinline__ int probe_value(const Probe &p)
+{
+    const uint32_t g = p.glb_v, l = p.lds_v;
+    return (int)(p.from_global ? g : l);
 }
 
 struct HistArgs {
@@ -94,7 +207,6 @@ __global__ __launch_bounds__(256) void k_train_histogram(const HistArgs a)
     __shared__ uint16_t s_buf[8 + kTH * kTW];
     uint16_t *s_tile = s_buf + 8;   // s_tile[-1] = 65535: what a probe outside the tile reads (rdf_device.hpp)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t per_img = (uint32_t)a.W * (uint32_t)a.H;
 
     // Are all numerators of all proposals inside the range the shared-reciprocal divide is verified for?  (They
     // are, for anything make_random_features draws.)  Decided once per workgroup: testing 4 numerators per
@@ -105,7 +217,6 @@ __global__ __launch_bounds__(256) void k_train_histogram(const HistArgs a)
         if (i % 5 != 4) mine_ok = mine_ok && fast_divide_ok(a.props[i]);
     const bool all_fast = __syncthreads_and(mine_ok ? 1 : 0) != 0;
 
-    const int j0 = 0, j1 = a.P;
     __shared__ uint32_t s_next;
     for (;;) {
         if (tid == 0) s_next = atomicAdd(&g_train_queue[0], 1u);
@@ -113,18 +224,13 @@ __global__ __launch_bounds__(256) void k_train_histogram(const HistArgs a)
         const uint32_t tile = s_next;
         __syncthreads();   // (s_next is rewritten in the next round)
         if (tile >= a.n_tiles) break;
-        const uint32_t per = a.tiles_x * a.tiles_y;
-        const uint32_t img = tile / per, rem = tile - img * per;
-        const uint32_t ty = rem / a.tiles_x, tx = rem - ty * a.tiles_x;
-        const int x = (int)(tx * kCols) + wave * kBW + (lane % kBW), y = (int)(ty * kRows) + lane / kBW;
-        const int tx0 = (int)(tx * kCols) - kHalo, ty0 = (int)(ty * kRows) - kHalo;
-        const size_t img_off = (size_t)img * per_img;
+        const TilePos t = tile_decode<kHalo>(tile, a.tiles_x, a.tiles_y, a.W, a.H, lane, wave);
 
         // does this tile hold any pixel that counts?  (most of a frame is unlabelled background)
         int node = -1;
         uint32_t label = 0u;
-        if (x < a.W && y < a.H) {
-            const size_t i = img_off + (size_t)y * a.W + x;
+        if (t.x < a.W && t.y < a.H) {
+            const size_t i = t.img_off + (size_t)t.y * a.W + t.x;
             node = a.nodes[i];
             if (node >= 0 && (node * 2 < a.node_start || node * 2 + 1 >= a.node_end)) node = -1;
             if (node >= 0) label = a.labels[i];
@@ -132,58 +238,45 @@ __global__ __launch_bounds__(256) void k_train_histogram(const HistArgs a)
         }
         if (!__syncthreads_or(node >= 0 ? 1 : 0)) continue;   // (also: the previous tile's readers are done)
 
-        for (int row = wave; row < kTH; row += 4) {
-            const int gy = ty0 + row;
-            const bool row_in = (uint32_t)gy < (uint32_t)a.H;
-            for (int col = lane; col < kTW; col += 64) {
-                const int gx = tx0 + col;
-                uint32_t v = kNoPixel;
-                if (row_in && (uint32_t)gx < (uint32_t)a.W) v = a.depth[img_off + (size_t)gy * a.W + gx];
-                s_tile[row * kTW + col] = (uint16_t)v;
-            }
-        }
+        tile_stage<kTW, kTH>(s_tile, a.depth, t, a.W, a.H, lane, wave);
         __syncthreads();
 
         const bool live = node >= 0;
         if (!__any(live)) continue;   // wave-uniform; no barrier below this point in the iteration
-        const int xl = x - tx0, yl = y - ty0;
+        const int xl = t.x - t.tx0, yl = t.y - t.ty0;
         const uint32_t d = live ? s_tile[yl * kTW + xl] : 1u;
         const float df = (float)(d == 0u ? 1u : d);
-        const float r0 = __builtin_amdgcn_rcpf(df);
-        const float rcp = __builtin_fmaf(__builtin_fmaf(-df, r0, 1.0f), r0, r0);
+        const float rcp = refined_rcp(df);
         const bool zero_depth = d == 0u;              // compute_feature returns 0.f (decision_tree_common.hpp:12)
 
         // Lanes that share (node, class) form a group; per proposal each group splits into a left and a right
         // part and only the lowest lane of each part adds the part's size.  That is the fewest atomics a wave
         // can issue without knowing the bins in advance: one per (node, class, side) it touches instead of one
         // per pixel (deep levels were bound by ~1e9 global atomics per level before).
-        const u64 live_mask = __ballot(live);
         const int key = node * a.C + (int)label;
         u64 peers = 0ull;
-        for (u64 todo = live_mask; todo;) {               // wave-uniform loop, once per tile
-            const int src = __ffsll((long long)todo) - 1;
-            const int k0 = __builtin_amdgcn_readfirstlane(__shfl(key, src));
-            const u64 m = __ballot(live && key == k0);
-            if (key == k0) peers = m;
-            todo &= ~m;
+        for (u64 todo = __ballot(live); todo;) {             // wave-uniform loop, once per tile
+            const KeyGroup grp = wave_key_group(todo, key, live);
+            if (key == grp.key) peers = grp.lanes;
+            todo &= ~grp.lanes;
         }
         const int bin0 = (node * 2 - a.node_start) * a.C + (int)label;   // left child's bin; right child's is + C
         // a (node, class) with at most 65535 pixels can count four proposals in the 16-bit fields of one word
         const bool small = PAIRS && a.parent_counts != nullptr && live &&
                            a.parent_counts[(size_t)node * a.C + label] <= 65535ull;
 
-        const ProbeCtx pc = {s_tile, reinterpret_cast<const char *>(a.depth) + img_off * 2, tx0, ty0, kTW, kTH, kTW,
+        const ProbeCtx pc = {s_tile, reinterpret_cast<const char *>(a.depth) + t.img_off * 2, t.tx0, t.ty0, kTW, kTH, kTW,
                              a.W, a.H};
         const f2 r2 = {rcp, rcp}, nd = {-df, -df};
 
         // kBatch proposals at a time: all their probes are issued before any is consumed (a far probe is a
         // global round trip; waiting for each one inside its branch made this kernel 10x slower)
-        for (int jb = j0; jb < j1; jb += kBatch) {
+        for (int jb = 0; jb < a.P; jb += kBatch) {
             Probe pu[kBatch], pv[kBatch];
             float thr[kBatch];
 #pragma unroll
             for (int k = 0; k < kBatch; ++k) {
-                const int j = min(jb + k, j1 - 1);               // tail: repeat the last proposal, result unused
+                const int j = min(jb + k, a.P - 1);              // tail: repeat the last proposal, result unused
                 const float *p = a.props + (size_t)j * 5;
                 const float ux = p[0], uy = p[1], vx = p[2], vy = p[3];
                 thr[k] = p[4];
@@ -205,7 +298,7 @@ __global__ __launch_bounds__(256) void k_train_histogram(const HistArgs a)
                 for (int k = 0; k < kBatch; ++k) {
                     const float f = zero_depth ? 0.0f : (float)(probe_value(pu[k]) - probe_value(pv[k]));
                     const u64 left = __ballot(live && f < thr[k]);      // tree_train.cu:57-58
-                    n[k] = (jb + k) < j1 ? (unsigned)__popcll(peers & left) : 0u;
+                    n[k] = (jb + k) < a.P ? (unsigned)__popcll(peers & left) : 0u;
                 }
                 // the lowest lane of each (node, class) group adds the group's left counts, two proposals at a time
                 if (live && lane == __ffsll((long long)peers) - 1) {
@@ -230,7 +323,7 @@ __global__ __launch_bounds__(256) void k_train_histogram(const HistArgs a)
 #pragma unroll
             for (int k = 0; k < kBatch; ++k) {
                 const int j = jb + k;
-                if (j >= j1) break;                              // wave-uniform
+                if (j >= a.P) break;                             // wave-uniform
                 const float f = zero_depth ? 0.0f : (float)(probe_value(pu[k]) - probe_value(pv[k]));
                 const bool is_left_px = f < thr[k];              // tree_train.cu:57-58
                 const u64 left = __ballot(live && is_left_px);
@@ -243,13 +336,7 @@ __global__ __launch_bounds__(256) void k_train_histogram(const HistArgs a)
             }
         }
     }
-    if (tid == 0) {   // every workgroup has made its final, failing pull before it gets here
-        const unsigned int done = atomicAdd(&g_train_queue[1], 1u);
-        if (done == gridDim.x - 1u) {
-            atomicExch(&g_train_queue[0], 0u);
-            atomicExch(&g_train_queue[1], 0u);
-        }
-    }
+    if (tid == 0) tile_queue_done();
 }
 
 // tmp[pair][bin][2] (32-bit halves, written by k_train_histogram<true>) -> counts[j][bin] (64-bit, the layout of the
@@ -445,19 +532,15 @@ __global__ __launch_bounds__(256) void k_train_update_pixels(const uint16_t *dep
     const int parent = nodes[i];
     if (parent == -1) return;
     const size_t per = (size_t)W * H;
-    const size_t img_off = (i / per) * per;
-    const int y = (int)((i % per) / W), x = (int)((i % per) % W);
+    const uint16_t *frame = depth + (i / per) * per;   // the pixel's image
+    const int y =(int)((i % per) / W), x = (int)((i % per) % W);
     const float *rec = tree + ((size_t)((1 << level) - 1) + parent) * (7 + 2 * C);
     const uint32_t d = depth[i];
     float f = 0.f;
     if (d != 0u) {
         const float df = (float)d;
-        auto at = [&](float ox, float oy) -> float {
-            const int px = add_wrap(x, floor_i32(ox / df)), py = add_wrap(y, floor_i32(oy / df));
-            if ((uint32_t)px < (uint32_t)W && (uint32_t)py < (uint32_t)H) return (float)depth[img_off + (size_t)py * W + px];
-            return 65535.0f;
-        };
-        f = at(rec[0], rec[1]) - at(rec[2], rec[3]);
+        f = depth_or_no_pixel<size_t>(frame, W, H, offset_coord(x, rec[0], df), offset_coord(y, rec[1], df)) -
+            depth_or_no_pixel<size_t>(frame, W, H, offset_coord(x, rec[2], df), offset_coord(y, rec[3], df));
     }
     const bool left = f < rec[4];
     const int status = floor_i32(rec[left ? 5 : 6]);
@@ -513,19 +596,17 @@ __global__ __launch_bounds__(256) void k_train_sort(const SortArgs a)
         int my_pos = -1;
         bool mine_done = key < 0;
         for (int it = 0; it < kSortIters && todo; ++it) {
-            const int src = __ffsll((long long)todo) - 1;
-            const int k0 = __builtin_amdgcn_readfirstlane(__shfl(key, src));
-            const u64 m = __ballot(key == k0);
-            const unsigned n = (unsigned)__popcll(m);
+            const KeyGroup g = wave_key_group(todo, key, true);   // (a lane without a key holds -1: no pending lane's key)
+            const unsigned n = (unsigned)__popcll(g.lanes);
             unsigned base = 0;
-            const size_t c0 = ((size_t)k0 << a.slot_shift) + slot;
-            if (lane == src) base = POSITIONS ? atomicAdd(a.cursor + c0, n) : atomicAdd(a.sizes + c0, n);
+            const size_t c0 = ((size_t)g.key << a.slot_shift) + slot;
+            if (lane == g.src) base = POSITIONS ? atomicAdd(a.cursor + c0, n) : atomicAdd(a.sizes + c0, n);
             if (POSITIONS) {
-                base = (unsigned)__shfl((int)base, src);
-                if (key == k0) my_pos = (int)(a.offsets[c0] + base + (unsigned)__popcll(m & ((1ull << lane) - 1ull)));
+                base = (unsigned)__shfl((int)base, g.src);
+                if (key == g.key) my_pos = (int)(a.offsets[c0] + base + (unsigned)__popcll(g.lanes & ((1ull << lane) - 1ull)));
             }
-            if (key == k0) mine_done = true;
-            todo &= ~m;
+            if (key == g.key) mine_done = true;
+            todo &= ~g.lanes;
         }
         if (!mine_done) {                              // deep levels: every pixel its own group
             const size_t c = ((size_t)key << a.slot_shift) + slot;
@@ -613,7 +694,6 @@ __global__ __launch_bounds__(256) void k_train_bits(const BitsArgs a)
     uint16_t *s_tile = reinterpret_cast<uint16_t *>(s_dyn);                                      // at LDS address 0 (TileCtx)
     uint32_t *s_mail = reinterpret_cast<uint32_t *>(s_dyn + kTHb * kTWb * 2);                    // next tile, "any live" x 2
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t per_img = (uint32_t)a.W * (uint32_t)a.H;
     const float *nprops = a.props + (size_t)a.P * 5;
     const bool all_fast = nprops[(size_t)a.P * 5] != 0.0f;          // (wave-uniform, scalar load)
     const int words_used = (a.P + 31) >> 5;
@@ -624,15 +704,10 @@ __global__ __launch_bounds__(256) void k_train_bits(const BitsArgs a)
         __syncthreads();
         const uint32_t tile = s_mail[0];
         if (tile >= a.n_tiles) break;
-        const uint32_t per = a.tiles_x * a.tiles_y;
-        const uint32_t img = tile / per, rem = tile - img * per;
-        const uint32_t ty = rem / a.tiles_x, tx = rem - ty * a.tiles_x;
-        const int x = (int)(tx * kCols) + wave * kBW + (lane % kBW), y = (int)(ty * kRows) + lane / kBW;
-        const int tx0 = (int)(tx * kCols) - kHaloB, ty0 = (int)(ty * kRows) - kHaloB;
-        const size_t img_off = (size_t)img * per_img;
+        const TilePos t = tile_decode<kHaloB>(tile, a.tiles_x, a.tiles_y, a.W, a.H, lane, wave);
 
         int row = -1;
-        if (x < a.W && y < a.H) row = a.pos[img_off + (size_t)y * a.W + x];
+        if (t.x < a.W && t.y < a.H) row = a.pos[t.img_off + (size_t)t.y * a.W + t.x];
         const bool live = row >= 0;
         // workgroup-wide OR through two alternating words (no static LDS: see the forest kernel's empty-tile test)
         if (__any(live) && lane == 0) s_mail[1u + (it & 1u)] = 1u;
@@ -641,28 +716,17 @@ __global__ __launch_bounds__(256) void k_train_bits(const BitsArgs a)
         if (tid == 0) s_mail[1u + ((it + 1u) & 1u)] = 0u;
         if (any_live == 0u) continue;
 
-        for (int r = wave; r < kTHb; r += 4) {
-            const int gy = ty0 + r;
-            const bool row_in = (uint32_t)gy < (uint32_t)a.H;
-            for (int col = lane; col < kTWb; col += 64) {
-                const int gx = tx0 + col;
-                uint32_t v = kNoPixel;
-                if (row_in && (uint32_t)gx < (uint32_t)a.W) v = a.depth[img_off + (size_t)gy * a.W + gx];
-                s_tile[r * kTWb + col] = (uint16_t)v;
-            }
-        }
+        tile_stage<kTWb, kTHb>(s_tile, a.depth, t, a.W, a.H, lane, wave);
         __syncthreads();
 
         if (!__any(live)) continue;   // wave-uniform; no barrier below this point in the iteration
-        const int xl = x - tx0, yl = y - ty0;
+        const int xl = t.x - t.tx0, yl = t.y - t.ty0;
         const uint32_t d = live ? s_tile[yl * kTWb + xl] : 1u;
         const float df = (float)(d == 0u ? 1u : d);
-        const float r0 = __builtin_amdgcn_rcpf(df);
-        const float rcp = __builtin_fmaf(__builtin_fmaf(-df, r0, 1.0f), r0, r0);
-        float rcp_s = rcp * (1.0f / kNumScale);
+        float rcp_s = refined_rcp(df) * (1.0f / kNumScale);   // (rounds before the switch below: rcp_s is its operand)
         const bool zero_depth = d == 0u;              // compute_feature returns 0.f (decision_tree_common.hpp:12)
-        const TileCtx pc = {reinterpret_cast<const char *>(a.depth) + img_off * 2, (uint32_t)kTWb * 2u, (uint32_t)kTHb,
-                            (uint32_t)kTWb * 2u, (uint32_t)a.W * 2u, (uint32_t)a.H, (uint32_t)tx0 * 2u, (uint32_t)ty0};
+        const TileCtx pc = {reinterpret_cast<const char *>(a.depth) + t.img_off * 2, (uint32_t)kTWb * 2u, (uint32_t)kTHb,
+                            (uint32_t)kTWb * 2u, (uint32_t)a.W * 2u, (uint32_t)a.H, (uint32_t)t.tx0 * 2u, (uint32_t)t.ty0};
         uint32_t kx2 = ((uint32_t)xl - kMagicBits) * 2u;
         const uint32_t ky = (uint32_t)yl - kMagicBits;
         pin(kx2);
@@ -728,13 +792,7 @@ __global__ __launch_bounds__(256) void k_train_bits(const BitsArgs a)
             }
         }
     }
-    if (tid == 0) {   // every workgroup has made its final, failing pull before it gets here
-        const unsigned int done = atomicAdd(&g_train_queue[1], 1u);
-        if (done == gridDim.x - 1u) {
-            atomicExch(&g_train_queue[0], 0u);
-            atomicExch(&g_train_queue[1], 0u);
-        }
-    }
+    if (tid == 0) tile_queue_done();
 }
 
 struct CountArgs {
@@ -795,6 +853,32 @@ __global__ __launch_bounds__(256) void k_train_count_rows(const CountArgs a)
     flush(cur_key);
 }
 
+// ---- host: what the launchers share ----
+bool bad_node_block(int start, int end, int per_block) { return per_block < 1 || end - start > per_block || start < 0; }
+int device_cus()
+{
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    return cus;
+}
+// kCols x kRows tiles over every image, numbered as tile_decode takes them apart
+int tile_geometry(int n_img, int dim_x, int dim_y, uint32_t &tiles_x, uint32_t &tiles_y, uint32_t &n_tiles)
+{
+    tiles_x = (uint32_t)(dim_x + kCols - 1) / kCols;
+    tiles_y = (uint32_t)(dim_y + kRows - 1) / kRows;
+    const long long n = (long long)n_img * tiles_x * tiles_y;
+    n_tiles = (uint32_t)n;
+    return n >= (1ll << 31) ? RDF_ERR_TOO_LARGE : RDF_OK;
+}
+// The kernels leave their tile queue at zero; clearing it before a launch as well keeps a launch that died half-way from
+// silently shortening the next one.
+int clear_tile_queue(hipStream_t st)
+{
+    void *q = nullptr;
+    if (hipGetSymbolAddress(&q, HIP_SYMBOL(g_train_queue)) != hipSuccess || !q) return RDF_ERR_NO_DEVICE;
+    return (int)hipMemsetAsync(q, 0, sizeof(unsigned int) * 2, st);
+}
+
 } // namespace
 
 extern "C" {
@@ -807,7 +891,7 @@ int rdf_train_init(const uint16_t *labels, size_t n_px, int n_classes, int32_t *
     if (!labels || !nodes_by_pixel || !root_counts) return RDF_ERR_NULL_PTR;
     size_t blocks = (n_px + 255) / 256;
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(k_train_init, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), labels, n_px,
+    hipLaunchKernelGGL(k_train_init, dim3((unsigned)blocks), dim3(256), 0, S(stream), labels, n_px,
                        n_classes, nodes_by_pixel, root_counts);
     return (int)hipGetLastError();
 }
@@ -820,7 +904,7 @@ static int train_histogram(const uint16_t *depth, const uint16_t *labels, const 
                            const unsigned long long *parent_counts, void *stream)
 {
     if (n_img < 0 || dim_x < 0 || dim_y < 0 || n_proposals < 0 || n_classes < 1 || n_classes > kMaxClasses ||
-        nodes_per_block < 1 || node_end - node_start > nodes_per_block || node_start < 0)
+        bad_node_block(node_start, node_end, nodes_per_block))
         return RDF_ERR_BAD_ARG;
     if ((long long)n_img * dim_x * dim_y >= (1ll << 31)) return RDF_ERR_TOO_LARGE;
     if (n_img == 0 || dim_x == 0 || dim_y == 0 || n_proposals == 0) return RDF_OK;
@@ -833,23 +917,11 @@ static int train_histogram(const uint16_t *depth, const uint16_t *labels, const 
     a.tmp = reinterpret_cast<uint32_t *>(workspace);
     a.Ppad = pairs_ppad(n_proposals);
     a.parent_counts = parent_counts;
-    a.tiles_x = (uint32_t)(dim_x + kCols - 1) / kCols;
-    a.tiles_y = (uint32_t)(dim_y + kRows - 1) / kRows;
-    const long long n_tiles = (long long)n_img * a.tiles_x * a.tiles_y;
-    if (n_tiles >= (1ll << 31)) return RDF_ERR_TOO_LARGE;
-    a.n_tiles = (uint32_t)n_tiles;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    long long grid = (long long)cus * 8;
-    if (grid > n_tiles) grid = n_tiles;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    {   // the kernel leaves its tile queue at zero; clearing it here as well keeps a launch that died half-way from
-        // silently shortening the next one
-        void *q = nullptr;
-        if (hipGetSymbolAddress(&q, HIP_SYMBOL(g_train_queue)) != hipSuccess || !q) return RDF_ERR_NO_DEVICE;
-        const hipError_t eq = hipMemsetAsync(q, 0, sizeof(unsigned int) * 2, st);
-        if (eq != hipSuccess) return (int)eq;
-    }
+    if (tile_geometry(n_img, dim_x, dim_y, a.tiles_x, a.tiles_y, a.n_tiles) != RDF_OK) return RDF_ERR_TOO_LARGE;
+    const long long grid = min((long long)device_cus() * 8, (long long)a.n_tiles);
+    hipStream_t st = S(stream);
+    const int eq = clear_tile_queue(st);
+    if (eq != RDF_OK) return eq;
     if (!workspace) {
         hipLaunchKernelGGL(k_train_histogram<false>, dim3((unsigned)grid), dim3(256), 0, st, a);
         return (int)hipGetLastError();
@@ -861,13 +933,13 @@ static int train_histogram(const uint16_t *depth, const uint16_t *labels, const 
     const int n_bins = (node_end - node_start) * n_classes;
     const long long n = (long long)n_bins * a.Ppad;
     if (n > 0) {
-        hipLaunchKernelGGL(k_train_unpack_pairs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.tmp, n_bins, n_proposals,
+        hipLaunchKernelGGL(k_train_unpack_pairs, dim3(blocks(n, 256)), dim3(256), 0, st, a.tmp, n_bins, n_proposals,
                            a.Ppad, nodes_per_block, n_classes, counts);
         e = hipGetLastError();
         if (e == hipSuccess && parent_counts) {
             u64 *quads = reinterpret_cast<u64 *>(a.tmp) + (size_t)(a.Ppad / 2) * nodes_per_block * n_classes;
             const long long nq = (long long)n_bins * (a.Ppad / 4);
-            hipLaunchKernelGGL(k_train_unpack_quads, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, quads, n_bins,
+            hipLaunchKernelGGL(k_train_unpack_quads, dim3(blocks(nq, 256)), dim3(256), 0, st, quads, n_bins,
                                n_proposals, a.Ppad, nodes_per_block, n_classes, counts);
             e = hipGetLastError();
         }
@@ -953,7 +1025,7 @@ int rdf_train_sort_pixels(const uint16_t *labels, const int32_t *nodes_by_pixel,
     if (!workspace) return RDF_ERR_NULL_PTR;
     const int shift = sort_slot_shift((long long)n_nodes * n_classes);
     const int n_keys = (n_nodes * n_classes) << shift;        // counters
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = S(stream);
     hipError_t e = hipMemsetAsync(workspace, 0, ((size_t)n_keys * 3u + 4u) * sizeof(uint32_t), st);
     if (e != hipSuccess) return (int)e;
     if (n_px == 0) return RDF_OK;
@@ -965,11 +1037,10 @@ int rdf_train_sort_pixels(const uint16_t *labels, const int32_t *nodes_by_pixel,
     a.cursor = a.offsets + n_keys;
     a.n_rows = a.cursor + n_keys;
     a.pos = pos; a.rowkey = rowkey;
-    size_t blocks = (n_px + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(k_train_sort<false>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    const unsigned grid = min(blocks((long long)n_px, 256), 8192u);
+    hipLaunchKernelGGL(k_train_sort<false>, dim3(grid), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_train_sort_scan, dim3(1), dim3(1024), 0, st, a.sizes, a.offsets, a.n_rows, n_keys);
-    hipLaunchKernelGGL(k_train_sort<true>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_train_sort<true>, dim3(grid), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
 
@@ -980,7 +1051,7 @@ int rdf_train_decision_bits(const uint16_t *depth, const int32_t *pos, int n_img
     if ((long long)n_img * dim_x * dim_y >= (1ll << 31)) return RDF_ERR_TOO_LARGE;
     if (n_img == 0 || dim_x == 0 || dim_y == 0 || n_proposals == 0) return RDF_OK;
     if (!depth || !pos || !proposals || !bits || !workspace) return RDF_ERR_NULL_PTR;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = S(stream);
     // the proposals as drawn, then in the form the one-fma divide wants, then the "all in range" flag
     float *props2 = reinterpret_cast<float *>(workspace);
     hipError_t ec = hipMemcpyAsync(props2, proposals, (size_t)n_proposals * 5 * sizeof(float), hipMemcpyDeviceToDevice, st);
@@ -989,17 +1060,9 @@ int rdf_train_decision_bits(const uint16_t *depth, const int32_t *pos, int n_img
     BitsArgs a;
     a.depth = depth; a.pos = pos; a.props = props2; a.bits = reinterpret_cast<uint32_t *>(bits);
     a.W = dim_x; a.H = dim_y; a.P = n_proposals; a.words = bits_words(n_proposals);
-    a.tiles_x = (uint32_t)(dim_x + kCols - 1) / kCols;
-    a.tiles_y = (uint32_t)(dim_y + kRows - 1) / kRows;
-    const long long n_tiles = (long long)n_img * a.tiles_x * a.tiles_y;
-    if (n_tiles >= (1ll << 31)) return RDF_ERR_TOO_LARGE;
-    a.n_tiles = (uint32_t)n_tiles;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    void *q = nullptr;
-    if (hipGetSymbolAddress(&q, HIP_SYMBOL(g_train_queue)) != hipSuccess || !q) return RDF_ERR_NO_DEVICE;
-    const hipError_t eq = hipMemsetAsync(q, 0, sizeof(unsigned int) * 2, st);
-    if (eq != hipSuccess) return (int)eq;
+    if (tile_geometry(n_img, dim_x, dim_y, a.tiles_x, a.tiles_y, a.n_tiles) != RDF_OK) return RDF_ERR_TOO_LARGE;
+    const int eq = clear_tile_queue(st);
+    if (eq != RDF_OK) return eq;
     static_assert((kTHb * kTWb * 2) % 16 == 0, "the mailbox words sit aligned behind the tile");
     hipFuncAttributes fa;      // the probes address the tile as LDS address 0 + offset (TileCtx): no static LDS allowed
     if (hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_train_bits)) != hipSuccess || fa.sharedSizeBytes != 0)
@@ -1007,8 +1070,7 @@ int rdf_train_decision_bits(const uint16_t *depth, const int32_t *pos, int n_img
     const int lds = kTHb * kTWb * 2 + 16;
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_train_bits, 256, (size_t)lds) != hipSuccess || per_cu < 1) per_cu = 4;
-    long long grid = (long long)cus * per_cu;
-    if (grid > n_tiles) grid = n_tiles;
+    const long long grid = min((long long)device_cus() * per_cu, (long long)a.n_tiles);
     hipLaunchKernelGGL(k_train_bits, dim3((unsigned)grid), dim3(256), lds, st, a);
     return (int)hipGetLastError();
 }
@@ -1017,8 +1079,8 @@ int rdf_train_count_rows(const void *bits, const int32_t *rowkey, const void *so
                          int n_classes, int node_start, int node_end, int nodes_per_block, unsigned long long *counts,
                          void *stream)
 {
-    if (n_proposals < 0 || n_proposals > 1024 || n_classes < 1 || n_classes > kMaxClasses || n_nodes < 1 || nodes_per_block < 1 ||
-        node_end - node_start > nodes_per_block || node_start < 0)
+    if (n_proposals < 0 || n_proposals > 1024 || n_classes < 1 || n_classes > kMaxClasses || n_nodes < 1 ||
+        bad_node_block(node_start, node_end, nodes_per_block))
         return RDF_ERR_BAD_ARG;
     if (n_proposals == 0) return RDF_OK;
     if (!bits || !rowkey || !sort_workspace || !counts) return RDF_ERR_NULL_PTR;
@@ -1030,10 +1092,8 @@ int rdf_train_count_rows(const void *bits, const int32_t *rowkey, const void *so
     a.counts = counts;
     a.P = n_proposals; a.words = bits_words(n_proposals); a.q = a.words * 32 / 64;
     a.C = n_classes; a.NB = nodes_per_block; a.node_start = node_start; a.node_end = node_end;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const dim3 grid((unsigned)cus * 8u), block(256);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)device_cus() * 8u), block(256);
+    hipStream_t st = S(stream);
     switch (a.q) {
     case 1: hipLaunchKernelGGL(k_train_count_rows<1>, grid, block, 0, st, a); break;
     case 2: hipLaunchKernelGGL(k_train_count_rows<2>, grid, block, 0, st, a); break;
@@ -1048,16 +1108,15 @@ int rdf_train_right_counts(int n_active, const int32_t *active_nodes, int n_prop
                            int node_start, int node_end, int n_classes, const unsigned long long *parent_counts,
                            unsigned long long *counts, void *stream)
 {
-    if (n_active < 0 || n_proposals < 0 || n_classes < 1 || n_classes > kMaxClasses || nodes_per_block < 1 ||
-        node_end - node_start > nodes_per_block || node_start < 0)
+    if (n_active < 0 || n_proposals < 0 || n_classes < 1 || n_classes > kMaxClasses ||
+        bad_node_block(node_start, node_end, nodes_per_block))
         return RDF_ERR_BAD_ARG;
     if (n_active == 0 || n_proposals == 0) return RDF_OK;
     if (!active_nodes || !parent_counts || !counts) return RDF_ERR_NULL_PTR;
     const long long n = (long long)n_active * n_proposals;
     if (n >= (1ll << 31)) return RDF_ERR_TOO_LARGE;
-    hipLaunchKernelGGL(k_train_right_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), n_active, active_nodes, n_proposals, nodes_per_block,
-                       node_start, node_end, n_classes, parent_counts, counts);
+    hipLaunchKernelGGL(k_train_right_counts, dim3(blocks(n, 256)), dim3(256), 0, S(stream), n_active, active_nodes, n_proposals,
+                       nodes_per_block, node_start, node_end, n_classes, parent_counts, counts);
     return (int)hipGetLastError();
 }
 
@@ -1073,7 +1132,7 @@ int rdf_train_pick_best(int n_active, const int32_t *active_nodes, int n_proposa
     if (n_active == 0 || n_proposals == 0) return RDF_OK;
     if (!active_nodes || !parent_counts || !counts_by_feature || !proposals || !tree_out || !child_counts || !best_gain_per_node)
         return RDF_ERR_NULL_PTR;
-    hipLaunchKernelGGL(k_train_pick_best, dim3((n_active + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(k_train_pick_best, dim3((n_active + 3) / 4), dim3(256), 0, S(stream),
                        n_active, active_nodes, n_proposals, max_depth, nodes_per_block, node_start, node_end, n_classes, level,
                        parent_counts, counts_by_feature, proposals, tree_out, child_counts, best_gain_per_node);
     return (int)hipGetLastError();
@@ -1085,7 +1144,7 @@ int rdf_train_next_active(int level, int max_depth, int n_classes, const float *
     if (level < 0 || level >= max_depth || max_depth > 30 || n_classes < 1 || n_active < 0) return RDF_ERR_BAD_ARG;
     if (!n_next_active) return RDF_ERR_NULL_PTR;
     if (n_active > 0 && (!tree || !active_nodes || !next_active_nodes)) return RDF_ERR_NULL_PTR;
-    hipLaunchKernelGGL(k_train_next_active, dim3(1), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), level, n_classes,
+    hipLaunchKernelGGL(k_train_next_active, dim3(1), dim3(1024), 0, S(stream), level, n_classes,
                        tree, active_nodes, n_active, next_active_nodes, n_next_active);
     return (int)hipGetLastError();
 }
@@ -1099,8 +1158,8 @@ int rdf_train_update_pixels(const uint16_t *depth, int n_img, int dim_x, int dim
     if (n_px == 0) return RDF_OK;
     if (n_px >= ((size_t)1 << 39)) return RDF_ERR_TOO_LARGE;
     if (!depth || !nodes_by_pixel || !tree) return RDF_ERR_NULL_PTR;
-    hipLaunchKernelGGL(k_train_update_pixels, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), depth, n_px, dim_x, dim_y, level, n_classes, nodes_by_pixel, tree);
+    hipLaunchKernelGGL(k_train_update_pixels, dim3(blocks((long long)n_px, 256)), dim3(256), 0, S(stream), depth, n_px, dim_x,
+                       dim_y, level, n_classes, nodes_by_pixel, tree);
     return (int)hipGetLastError();
 }
 

@@ -264,6 +264,24 @@ def test_aggregation_64_slots_in_one_wave(T, C, rdf, gpu_runtime):
 
 
 @pytest.mark.gpu
+def test_aggregation_six_deep_keys_of_several_lanes_each(rdf, gpu_runtime):
+    """One wave (a frame of 8 x 8) with more than kAggIters = 4 distinct keys below the LDS histogram, each held by several
+    lanes: column k = 0..5 carries 8 - k labelled pixels of class 1 + k % 2 and ends in its own slot of level 6 (T3/D7/C6:
+    3 * 63 * 12 = 2268 cells fit in the 4096, 3 * 127 * 12 = 4572 do not).  Four keys go through one add each, the lanes of
+    the other two add one each."""
+    depth = np.full((1, 8, 8), 1000, np.uint16)
+    labels = np.zeros(depth.shape, np.uint16)
+    for k in range(6):
+        labels[0, :8 - k, k] = 1 + k % 2
+    forest = np.stack([rc.column_tree(7, 6, 128)] * 3)
+    r = _check_count(rdf, depth, labels, forest)
+    assert r.totals()["walked"] == 33
+    got = r.counts.get()[0]
+    cells = {(63, 0, 1): 8, (63, 1, 2): 7, (64, 0, 1): 6, (64, 1, 2): 5, (65, 0, 1): 4, (65, 1, 2): 3}
+    assert {tuple(i): int(got[tuple(i)]) for i in np.argwhere(got).tolist()} == cells
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("T,D", [(1, 1), (1, 4), (3, 1)])
 def test_small_forests(T, D, rdf, gpu_runtime):
     rng = np.random.default_rng(T * 8 + D)
