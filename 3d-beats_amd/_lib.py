@@ -6,6 +6,7 @@ library, or a machine without a HIP device, raises.
 """
 import ctypes
 import os
+import threading
 import warnings
 
 from . import _build
@@ -231,6 +232,7 @@ BINDINGS = {
     }),
 }
 _loaded = {}
+_load_lock = threading.Lock()     # two threads' first load() of a library: one opens and types it, both get that object
 
 
 class RdfError(RuntimeError):
@@ -252,6 +254,11 @@ def load(name="hip"):
     not been built, if its ABI number is not the one this binding was written for, or if it was built from other sources."""
     if name in _loaded:
         return _loaded[name]
+    with _load_lock:
+        return _loaded[name] if name in _loaded else _load(name)
+
+
+def _load(name):
     prefix = _build.LIBRARIES[name].prefix
     path = library_path(name)
     if not os.path.exists(path):

@@ -279,13 +279,15 @@ void launch_ir(long long n_total, int dim_x, int dim_y, const uint16_t *depth_l,
 
 inline int match_lds_bytes(int D) { return kTileRows * (64 + D - 1) * (int)sizeof(u64); }       // 91 872 at D = 256
 
-// before anything is launched: a tile beyond 64 KiB has to be allowed per kernel
+// before anything is launched: a tile beyond 64 KiB has to be allowed per kernel.  The attribute is an upper bound and one per
+// kernel for the whole process, so it is always set to the widest range's tile (D = 256): two sensors with two ranges on two
+// threads then cannot lower it under each other's launch.
 template <bool RIGHT>
 int allow_match_lds(int D)
 {
     if (match_lds_bytes(D) <= 64 * 1024) return RDF_OK;
     return (int)hipFuncSetAttribute(reinterpret_cast<const void *>(k_stereo_match<RIGHT>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, match_lds_bytes(D));
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, match_lds_bytes(256));
 }
 
 template <bool RIGHT>

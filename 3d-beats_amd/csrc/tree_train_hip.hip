@@ -27,6 +27,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <mutex>
+
 #include "../../include/rdf_hip.h"
 #include "rdf_device.hpp"
 #include "rdf_kernel_util.hpp"
@@ -47,8 +49,8 @@ constexpr int kMaxClasses = 64;
 constexpr int kBatch = 4;                     // proposals evaluated together: 8 probes in flight per lane
 
 // Tile queue of the histogram kernel: {next tile, workgroups finished}.  Zero at rest: the last workgroup of a launch
-// puts it back (the host clears it before every launch all the same).  One queue per device: histogram launches of one device must not overlap
-// (the trainer issues them on one stream).  Labelled pixels cluster (a hand covers ~15 % of a frame), so tiles handed
+// puts it back (the host clears it before every launch all the same).  One queue per device: the launchers keep the launches
+// that pull from it apart, whatever streams they are on (QueueGate below; include/rdf_hip.h states the rule).  Labelled pixels cluster (a hand covers ~15 % of a frame), so tiles handed
 // out by static striding left the average SIMD with ONE resident wave while the unluckiest workgroup finished
 // (SQ_WAVE_CYCLES / GRBM_GUI_ACTIVE, level 0: 3.2 ms against a 1.4 ms VALU floor).
 __device__ unsigned int g_train_queue[2];
@@ -878,6 +880,58 @@ int clear_tile_queue(hipStream_t st)
     if (hipGetSymbolAddress(&q, HIP_SYMBOL(g_train_queue)) != hipSuccess || !q) return RDF_ERR_NO_DEVICE;
     return (int)hipMemsetAsync(q, 0, sizeof(unsigned int) * 2, st);
 }
+// One launch at a time pulls from a device's queue.  The gate of a device remembers the stream of the last such launch and an
+// event recorded behind it; a launch on ANOTHER stream waits for that event before it clears the queue (the same stream is in
+// order already: a pointer compare).  Held from the wait to the record, so that two host threads enqueue one after the other.
+// A stream that is being captured is left alone (an event recorded there means nothing outside the graph).
+class QueueGate {
+public:
+    explicit QueueGate(hipStream_t st) : st_(st)
+    {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kDevices) dev = 0;
+        dev_ = &per_device()[dev];
+        dev_->mu.lock();
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        capturing_ = hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+    }
+    ~QueueGate() { dev_->mu.unlock(); }
+    QueueGate(const QueueGate &) = delete;
+    QueueGate &operator=(const QueueGate &) = delete;
+    // before clear_tile_queue: the stream waits for the last launch unless it is that launch's own
+    int enter()
+    {
+        if (capturing_ || !dev_->behind_last || dev_->last == st_) return RDF_OK;
+        return (int)hipStreamWaitEvent(st_, dev_->behind_last, 0);
+    }
+    // behind the launch (and behind a launch that failed half-way: what it enqueued is waited for all the same)
+    int leave()
+    {
+        if (capturing_) return RDF_OK;
+        if (!dev_->behind_last && hipEventCreateWithFlags(&dev_->behind_last, hipEventDisableTiming) != hipSuccess) {
+            dev_->behind_last = nullptr;
+            return RDF_ERR_NO_DEVICE;
+        }
+        dev_->last = st_;
+        return (int)hipEventRecord(dev_->behind_last, st_);
+    }
+
+private:
+    static constexpr int kDevices = 64;
+    struct PerDevice {
+        std::mutex mu;
+        hipEvent_t behind_last = nullptr;       // made at the first launch, kept for the life of the process
+        hipStream_t last = nullptr;
+    };
+    static PerDevice *per_device()
+    {
+        static PerDevice gates[kDevices];
+        return gates;
+    }
+    PerDevice *dev_;
+    hipStream_t st_;
+    bool capturing_;
+};
 
 } // namespace
 
@@ -920,16 +974,20 @@ static int train_histogram(const uint16_t *depth, const uint16_t *labels, const 
     if (tile_geometry(n_img, dim_x, dim_y, a.tiles_x, a.tiles_y, a.n_tiles) != RDF_OK) return RDF_ERR_TOO_LARGE;
     const long long grid = min((long long)device_cus() * 8, (long long)a.n_tiles);
     hipStream_t st = S(stream);
-    const int eq = clear_tile_queue(st);
-    if (eq != RDF_OK) return eq;
-    if (!workspace) {
-        hipLaunchKernelGGL(k_train_histogram<false>, dim3((unsigned)grid), dim3(256), 0, st, a);
-        return (int)hipGetLastError();
+    if (workspace && ((uintptr_t)workspace & 7u) != 0) return RDF_ERR_BAD_ARG;
+    hipError_t e;
+    {
+        QueueGate gate(st);
+        int eq = gate.enter();
+        if (eq == RDF_OK) eq = clear_tile_queue(st);
+        if (eq != RDF_OK) return eq;
+        if (!workspace) hipLaunchKernelGGL(k_train_histogram<false>, dim3((unsigned)grid), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_train_histogram<true>, dim3((unsigned)grid), dim3(256), 0, st, a);
+        e = hipGetLastError();
+        const int el = gate.leave();
+        if (e == hipSuccess && el != RDF_OK) return el;
     }
-    if (((uintptr_t)workspace & 7u) != 0) return RDF_ERR_BAD_ARG;
-    hipLaunchKernelGGL(k_train_histogram<true>, dim3((unsigned)grid), dim3(256), 0, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    if (e != hipSuccess || !workspace) return (int)e;
     const int n_bins = (node_end - node_start) * n_classes;
     const long long n = (long long)n_bins * a.Ppad;
     if (n > 0) {
@@ -1061,8 +1119,6 @@ int rdf_train_decision_bits(const uint16_t *depth, const int32_t *pos, int n_img
     a.depth = depth; a.pos = pos; a.props = props2; a.bits = reinterpret_cast<uint32_t *>(bits);
     a.W = dim_x; a.H = dim_y; a.P = n_proposals; a.words = bits_words(n_proposals);
     if (tile_geometry(n_img, dim_x, dim_y, a.tiles_x, a.tiles_y, a.n_tiles) != RDF_OK) return RDF_ERR_TOO_LARGE;
-    const int eq = clear_tile_queue(st);
-    if (eq != RDF_OK) return eq;
     static_assert((kTHb * kTWb * 2) % 16 == 0, "the mailbox words sit aligned behind the tile");
     hipFuncAttributes fa;      // the probes address the tile as LDS address 0 + offset (TileCtx): no static LDS allowed
     if (hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_train_bits)) != hipSuccess || fa.sharedSizeBytes != 0)
@@ -1071,8 +1127,14 @@ int rdf_train_decision_bits(const uint16_t *depth, const int32_t *pos, int n_img
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_train_bits, 256, (size_t)lds) != hipSuccess || per_cu < 1) per_cu = 4;
     const long long grid = min((long long)device_cus() * per_cu, (long long)a.n_tiles);
+    QueueGate gate(st);
+    int eq = gate.enter();
+    if (eq == RDF_OK) eq = clear_tile_queue(st);
+    if (eq != RDF_OK) return eq;
     hipLaunchKernelGGL(k_train_bits, dim3((unsigned)grid), dim3(256), lds, st, a);
-    return (int)hipGetLastError();
+    const hipError_t e = hipGetLastError();
+    const int el = gate.leave();
+    return e != hipSuccess ? (int)e : el;
 }
 
 int rdf_train_count_rows(const void *bits, const int32_t *rowkey, const void *sort_workspace, int n_nodes, int n_proposals,

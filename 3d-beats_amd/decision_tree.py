@@ -17,6 +17,7 @@ make_random_features and DecisionTreeTrainer; the dataset reader l
 import json
 import logging
 import os
+import threading
 import time
 
 import numpy as np
@@ -87,6 +88,16 @@ class DecisionForest:
         The reference has no such step (its load is the upload at decision_tree.py:148-158); this is
         the load-time repack described in include/rdf_hip.h.  Returns None for an empty forest."""
         s = float(np.float32(scale_factor))
+        key = (id(self.forest_cu), self.forest_cu.version)
+        hit = self._packed.get(s)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        # two threads that meet here (a forest shared by two stacks, first evaluated on two threads at once) must not pack
+        # two tables and drop one under the other's launch: one packs, the other finds the entry
+        with self.__dict__.setdefault("_pack_lock", threading.Lock()):
+            return self._pack(s)
+
+    def _pack(self, s):
         key = (id(self.forest_cu), self.forest_cu.version)
         hit = self._packed.get(s)
         if hit is not None and hit[0] == key:

@@ -11,12 +11,14 @@ fallback.  Tests install a host-memory stand-in through `set_runtime()` to exerc
 without a GPU; that stand-in lives under tests/.
 """
 import ctypes
+import threading
 
 import numpy as np
 
 from . import _lib
 
 _runtime = None
+_runtime_lock = threading.Lock()
 
 
 class HipRuntime:
@@ -112,7 +114,9 @@ def get_runtime():
     """The process-wide runtime; created on first use.  Raises without a GPU or without the library."""
     global _runtime
     if _runtime is None:
-        _runtime = HipRuntime()
+        with _runtime_lock:         # (two threads' first call: one runtime)
+            if _runtime is None:
+                _runtime = HipRuntime()
     return _runtime
 
 
