@@ -11,7 +11,8 @@ SRC = os.path.join(HERE, "csrc", "rdf_hip.hip")
 SOURCES = [SRC, os.path.join(HERE, "csrc", "mean_shift_hip.hip"), os.path.join(HERE, "csrc", "points_ops_hip.hip"),
            os.path.join(HERE, "csrc", "tree_train_hip.hip"), os.path.join(HERE, "csrc", "grouping_hip.hip")]
 HEADERS = [os.path.join(HERE, "..", "include", "rdf_hip.h"), os.path.join(HERE, "csrc", "rdf_device.hpp"),
-           os.path.join(HERE, "csrc", "rdf_host_state.hpp"), os.path.join(HERE, "csrc", "rdf_kernel_util.hpp")]
+           os.path.join(HERE, "csrc", "rdf_host_state.hpp"), os.path.join(HERE, "csrc", "rdf_launch_plan.hpp"),
+           os.path.join(HERE, "csrc", "rdf_kernel_util.hpp")]
 SO = os.path.join(HERE, "csrc", "librdf_hip.so")
 
 

@@ -44,6 +44,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <mutex>
 #include <utility>
@@ -52,197 +53,18 @@
 #include "../../include/rdf_hip.h"
 #include "rdf_device.hpp"
 #include "rdf_host_state.hpp"
+#include "rdf_launch_plan.hpp"      // records, kernel arguments, knobs, the launch plan, the list of kernels: all without HIP
 
 namespace {
 
-constexpr int kGroup = 4;          // trees walked interleaved by one lane (template GROUP: 1 and 2 for smaller forests)
-constexpr int kMaxRowsPerWave = 4; // label rows each wave owns in a tile (fewer for small launches)
-constexpr int kDefaultLdsBudget = 32700;   // node table + depth tile per 256-thread workgroup (five per CU)
-constexpr int kDefaultLdsBudget512 = 54600;   // ... per 512-thread workgroup (three per CU)
-constexpr int kDefaultHalo = 32;   // depth pixels staged around a tile's centres
-constexpr int kMinLdsLevels = 6;   // top levels of every tree that stay in LDS when the depth tile competes for it
 constexpr uint32_t kFlagLeftLeaf = 1u, kFlagRightLeaf = 2u, kFlagExact = 4u;
 using rdf_host::kSchedSlots;            // one per (device, stream) that launches directly
 using rdf_host::kGraphSlots;            // one per launch recorded into a hipGraph (stream capture)
 
-// Dynamic tile queue state.  A workgroup's first tile is its own index; the queues hand out the tiles beyond the grid size
-// (a launch with no more tiles than workgroups never touches its slot).  One slot per (device, stream) that launches directly
-// (launches on one stream run in order, so they never meet in a slot) and a slot of its own for every launch recorded
-// into a hipGraph: a graph replays on whatever stream it is launched on, so its launch must not share the slot of the
-// stream it happened to be captured on (an executable graph never runs concurrently with itself).
-// Zero at rest: the last workgroup of a launch resets its slot, so launches need no memset and replay correctly.
-// A slot holds one queue head per XCD and the count of finished workgroups, each on a 128-byte line of its own (word
-// 32 q, q = 0..7; word 256): the tiles of a launch are cut into eight contiguous ranges, a workgroup pulls from the range
-// of the XCD it runs on (s_getreg XCC_ID) until it is empty and then helps the next two XCDs -- the workgroups that
-// share an L2 work on the same frames (4.74 -> 4.54 ms on the bench batch, 11.45 -> 10.74 ms on config 5's shard).
-// Helping is for balance and is kept short (one workgroup in sixteen goes round all eight queues, so that a range
-// whose XCD runs no workgroup of the launch -- CU masks -- is drained all the same): a failing pull is an atomic on a contended line (~90 per us per line), and with all heads on one line
-// and every workgroup trying all eight at the end a single frame took 188 instead of 97 us.
-constexpr int kSchedStride = 32;                 // words between two counters
-constexpr int kSchedWords = 9 * kSchedStride;
+// The tile queues' slots (their layout and who gets which: "Dynamic tile queue state" in rdf_launch_plan.hpp)
 constexpr uint32_t kStealFrom = 2;               // neighbours a workgroup helps once its own range is empty
 constexpr uint32_t kXcdQueuesFrom = 64;          // launches with fewer workgroups keep one queue
 __device__ unsigned int g_sched[kSchedSlots + kGraphSlots][kSchedWords];
-
-// ---- node records --------------------------------------------------------------------------
-// Hot record, 16 bytes, one 128-bit load per node.  Each word carries a numerator in its high 23 bits, a guard
-// bit and one byte of unrelated payload:
-//   w0 = floor(s*u.x) << 9 | g0 << 8 | T[7:0]       T = integer threshold (see thresh_to_int), 24-bit two's complement
-//   w1 = floor(s*u.y) << 9 | g1 << 8 | T[15:8]
-//   w2 = floor(s*v.x) << 9 | g2 << 8 | T[23:16]
-//   w3 = floor(s*v.y) << 9 | g3 << 8 | flags        flags: kFlagLeftLeaf/RightLeaf = that side is a leaf,
-//                                                          kFlagExact = use the exact record
-//   g = NOT bit 7 of the payload byte, so the nine low bits are a value in [128, 383].
-// The numerator is decoded with ONE instruction, v_cvt_f32_i32 of the whole word = 512*(x + e), 1/4 <= e <= 3/4
-// (the payload and the convert's rounding only move e inside that range): for integers x and d, (x + e)/d lies at
-// least 1/(4d) away from the integers on either side of floor(x/d), which is more than the error of ONE multiply by the
-// pixel's refined reciprocal -- so the whole divide-floor-add of decision_tree_common.hpp:15-18 is
-//     t = fma(n, r/512, 1.5*2^23)   in round-toward-minus-infinity mode:   bits(t) - bits(1.5*2^23) = floor(x/d)
-//     coordinate = bits(t) + (pixel coordinate - bits(1.5*2^23))            one v_add_u32
-// (the level loop runs with the wave's fp32 rounding mode set to round-down; everything outside it in round-to-nearest).
-// Checked exhaustively on gfx950 by tools/verify_magic.hip: every x in [-2^21, 2^21) x every payload byte x every
-// depth 1..65535 against integer floor division (logs under profiles/); tools/verify_intoffset.hip and
-// tools/verify_fastdiv.hip tie integer floor division to the reference's floor(IEEE (s*u)/d) for every fp32 numerator
-// that is +-0 or has a biased exponent in [40,147] (|a| < 2^21).  Any other numerator (huge, denormal, inf, NaN) flags
-// the node kFlagExact and the kernel takes the IEEE divide on the fp32 numerators s*u, s*v, which it recomputes -- the same
-// one multiply rdf_forest_pack did -- from the node's record in the caller's reference-layout forest (rounds 1-3 kept them in
-// a dense 32-byte table of their own, 128 MB for a T4/D20 forest that practically never has such a node).  rdf_forest_pack
-// counts the flagged nodes and notes the scale in the table's info block; a packed forest that has any needs the `forest`
-// argument at evaluation (RDF_ERR_NULL_PTR otherwise).
-struct alignas(16) NodeRec16 {
-    uint32_t w[4];
-};
-// What rdf_forest_pack leaves in the last 128 bytes of a packed table.
-struct PackInfo {
-    uint32_t exact_nodes;   // nodes flagged kFlagExact
-    float scale;            // the scale_factor the table was packed for
-    uint32_t magic;         // kPackMagic once k_pack has run
-    uint32_t deep_choice;   // which table serves the deep levels, chosen for THIS table (rdf_forest_set_deep_from / rdf_forest_tune):
-                            // 0 = no choice made, 1 + level otherwise (1 = heap-order records).  It travels with the table: a process that
-                            // maps or copies a tuned table (and every later evaluation in this one) finds the choice without tuning again
-    uint32_t generation;    // (round 6) which packing this is: a non-zero number rdf_forest_pack draws per call, unlike any other this
-                            // process drew and, with 31 random bits, practically unlike another process's.  The host remembers it
-                            // with what else it knows about the table at this address and hands it to every launch; the KERNEL compares
-                            // it with the word in the table and raises the device's stale flag when they differ (a different table was
-                            // copied over a known address without rdf_forest_forget): the next call returns RDF_ERR_STALE
-    uint32_t n_trees, max_depth, n_classes;     // the shape the table was packed for
-    uint32_t pad[24];
-};
-constexpr uint32_t kPackMagic = 0x52444635u;   // "RDF5" (round 6: generation and shape words)
-// Last-level record, 64 bytes (forests of up to four classes): the hot record of a node of level D-1 and the PDFs of
-// its two leaves in ONE half cache line.  A walk that reaches level D-1 ends there (tree_eval.cu:95-128), so its last
-// node fetch and its leaf fetch are the same 128-byte line: fetched together they are one L1 fill instead of two
-// (leaf loads were 6.5 % of the batch's time, profiles/r03_*).  The table is used when every record of it is an
-// ordinary node with two leaves (flags == both leaves, no kFlagExact; untrained all-zero nodes are such nodes);
-// k_pack counts the others behind the table and the kernel takes the general path when the count is not zero.
-struct alignas(64) LastLevelRec {
-    NodeRec16 node;
-    float pdf_left[4], pdf_right[4];
-    uint32_t pad[4];
-};
-static_assert(sizeof(NodeRec16) == 16 && sizeof(PackInfo) == 128 && sizeof(LastLevelRec) == 64, "record sizes");
-
-// ---- deep blocks: the levels whose records no cache holds, three levels to a 128-byte line ---------------------------
-// A forest whose deep levels are OCCUPIED (a trained forest; synth's "balanced" topology) visits practically every node of
-// them, so below the levels that fit an XCD's 4-MB L2 every node fetch of the heap-order table is a 128-byte line from
-// the Infinity Cache or HBM for 16 useful bytes: the bench batch on a balanced T4/D20 forest moves 0.67e9 such lines =
-// 86 GB per launch at 7.7 TB/s -- the fabric's whole bandwidth -- and takes 11.2 ms against 3.9 ms on the cache-resident
-// "full" topology (profiles/r04_*).  The packed forest therefore holds the hot records a second time, grouped by SUBTREE:
-//   * block of three levels, root on level R: records {root, left, right, LL, LR, RL, RR} = 112 bytes of one 128-byte line
-//     (the eighth slot is zero);
-//   * last block, root on level D - 2 (forests of up to four classes): {root, left, right} and the four leaf PDFs of
-//     level D - 1 {L.left, L.right, R.left, R.right}, 16 bytes each: a walk's last two node fetches AND its leaf fetch;
-//     forests of five to eight classes: root on level D - 1: {node, pad, left PDF (32 B), right PDF (32 B)}.
-// Block roots sit on levels R0 = D - 2 (or D - 1), R0 - 3, R0 - 6, ... >= 0; the blocks of one root level are contiguous,
-// [tree][root's index on its level], smaller root levels first; one all-zero line and a 64-byte trailer follow.
-// The kernel (k_eval_forest<..., DEEP>) walks the levels below `deep_from` (a root level, chosen per table) from this
-// table, ONE TREE AFTER THE OTHER, and the WAVE fetches its lanes' blocks together: eight LDS-DMA loads of eight whole lines
-// each into an 8-KB slab per wave, from which every lane reads the three records its walk takes (see "deep blocks" in the
-// kernel; round 4's walk had every lane fetch its own block with seven 16-byte loads -- seven L1 look-ups per line -- and
-// was bound by the L1's line accesses: 7.9 against 6.7 ms on the bench batch, 23.4 against 18.4 ms on config 5's shard,
-// profiles/r05_deep_coop.txt) -- a third of the lines from beyond L2 per walk, and the leaf comes with the last of them.
-// Usable from root level R on iff no node of a level >= R is flagged kFlagExact and (for the last block) every node
-// of level D - 1 has two leaves: k_pack leaves both facts in the trailer {1 + deepest level with an exact node,
-// nodes of level D - 1 that are not plain two-leaf nodes}.
-__host__ __device__ inline int deep_last_levels(int cpad) { return cpad == 4 ? 2 : 1; }
-// lines of every block level whose root level is below R (R, Lmin members of the series R0 - 3 i)
-__host__ __device__ inline size_t deep_lines_before(int n_trees, int R, int Lmin)
-{
-    return (size_t)n_trees * ((((size_t)1 << R) - ((size_t)1 << Lmin)) / 7u);
-}
-__host__ __device__ inline size_t deep_total_lines(int n_trees, int max_depth, int cpad)   // without the zero line and the trailer
-{
-    const int R0 = max_depth - deep_last_levels(cpad);
-    return deep_lines_before(n_trees, R0, R0 % 3) + ((size_t)n_trees << R0);
-}
-// A lane's block is addressed as {wave-uniform 64-bit base of its tree's blocks of the root level} + {32-bit byte offset =
-// heap index x 128}: root levels up to 23, i.e. forests of up to 24 levels.
-__host__ __device__ inline bool deep_possible(int n_trees, int max_depth, int cpad)
-{
-    return n_trees >= 1 && (cpad == 4 || cpad == 8) && max_depth >= 5 && max_depth <= 24;
-}
-
-struct EvalArgs {
-    const uint16_t *depth;
-    const float *forest;
-    const NodeRec16 *packed16;   // nullptr on the unpacked path
-    const uint16_t *filter;
-    uint16_t *labels;
-    unsigned long long *stats;
-    int stats_wide;        // stats holds 8 counters (rdf_eval_forest_packed_stats), not 3
-    unsigned int *sched;   // queue slot, or nullptr for static round-robin tiles
-    uint32_t n_tiles;      // n_img * (tiles_x * tiles_y + tiles_y_n)
-    uint32_t tiles_x;      // ceil(Wl / 64); with a folded last column: floor(Wl / 64)
-    // (round 6) The label map's last columns when Wl is not a multiple of 64 and at most 32 are left over (848 = 13 x 64 + 16):
-    // instead of a tile column whose waves run with 16 of 64 lanes, NARROW tiles of 64 / fold columns x fold x tile_rows rows in
-    // which a wave covers `fold` rows of 64 / fold pixels -- every lane has a pixel.  tiles_y_n of them per image, behind the
-    // image's ordinary tiles; their staged depth tile has its own shape.
-    uint32_t fold;         // 0: no narrow tiles; 2 or 4
-    uint32_t tiles_y_n;
-    int tw_n, th_n, twp_n;
-    int halo_xn;           // their halo in x (<= halo): chosen so that the `fold` rows of a wave do not share LDS banks
-    uint32_t stage_tw8_n, stage_magic_n;
-    uint32_t tiles_y;      // ceil(Hl / (waves per block * rows_per_wave))
-    int rows_per_wave;     // 1..kMaxRowsPerWave
-    uint32_t per_img_l;    // Wl*Hl
-    uint32_t per_img_d;    // W*H
-    int W, H, Wl, Hl, r;
-    int T, D, C, E;
-    int nodes;             // 2^D - 1
-    int lds_levels;        // top levels held in LDS
-    int halo;              // depth pixels around the tile's centres held in LDS
-    int tw, th, twp;       // staged depth tile: width, height, row pitch (0: no staged tile)
-    uint32_t stage_tw8;    // > 0: stage with 16-byte loads, tw / 8 vectors per row (W, tx0 and twp are multiples of 8)
-    uint32_t stage_magic;  // floor(2^32 / stage_tw8) + 1: i / stage_tw8 == umulhi(i, magic) for i < 2^32 / stage_tw8
-    uint32_t lds_xchg_off; // (tree waves) where the trees of a pixel row meet
-    uint32_t lds_nodes_off; // byte offsets inside the dynamic LDS allocation (the depth tile is at 0)
-    uint32_t lds_mail_off;
-    uint32_t lds_list_off;
-    uint32_t lds_slab_off; // (DEEP) the waves' block slabs: 8 KB each, 1-KB aligned
-    const float *packed_pdf;   // leaf PDFs [T][2^D][2][cpad], 16-byte aligned rows (packed path), or null
-    const uint4 *last_level;   // LastLevelRec [T][2^(D-1)] followed by the trailer (see k_pack), or null
-    uint32_t last_level_min;   // deepest-level nodes in use from which the table is taken
-    const uint4 *deep;         // deep blocks (see above), or null
-    int deep_from;             // root level from which the walk takes the deep blocks (a member of the series; DEEP kernels)
-    int cpad;                  // classes rounded up to a multiple of 4
-    int filter_class;
-    int check_empty;       // look at a tile's centre depths before staging it (throughput shape)
-    int keep_if_no_leaf;   // single-tree semantics: no leaf reached -> pixel untouched
-    int fill_untouched;    // fused pre-fill: write 65535 to every label pixel that is not evaluated
-    int plain_levels;      // the level loop may start on its plain path (g_plain_levels); 0: the general loop from level 0
-    float s;
-    // (round 6) the packed table's info block, the generation the host believes the table at this address has, and where a
-    // kernel that finds another one says so (pinned host memory, one word per device): see PackInfo.generation
-    const PackInfo *info;
-    uint32_t expect_gen;
-    unsigned int *stale_flag;
-    // (round 6) two launches that share ONE tile queue (rdf_eval_forest_packed_split: a main launch on a CU-masked stream and
-    // a helper launch that starts when the CUs left to another kernel are free again): q_static = tiles handed out
-    // statically (the main launch's grid; 0: this launch's own grid), q_blocks = workgroups of both launches together (the
-    // last of them puts the slot back to zero; 0: this launch's own), q_helper: this launch's workgroups have no static tile
-    uint32_t q_static, q_blocks;
-    int q_helper;
-};
 
 // A side continues iff floor(x) == -1  <=>  -1 <= x < 0   (NaN: false); anything else makes it a leaf.
 // tree_eval.cu:101-102 / :186-187.
@@ -367,22 +189,15 @@ __device__ __forceinline__ uint32_t walk_step_plain(uint32_t h, int g, uint32_t 
     return next;
 }
 
-// Every wave owns a.rows_per_wave label rows of the tile (up to kMaxRowsPerWave in the throughput shape, one for small
-// launches such as one live frame).
-// NL > 1 ("layers in one launch", small launches of a layered stack): workgroup b evaluates forest b % NL of the kernel's
-// NL argument sets on the same frame -- NL independent forest evaluations that share ONE launch, hence one ramp and one
-// drain (a small launch costs one wave-row's dependent chain however little it evaluates), with a tile queue per role.
-template <int NL>
-struct EvalArgsN {
-    EvalArgs l[NL];
-};
-
 // ---- a reader's map of k_eval_forest (one kernel, ~900 lines; the template parameters select code, never semantics) ----
 //   template parameters   BLOCK threads per workgroup | PACKED tables or the reference's records | CMAX classes summed in
 //                         registers at a time | STATS visit / line counters | GROUP trees a lane walks interleaved | COMPACT
 //                         pixel list (filtered launches) | NL layers of a stack in one launch | TW one wave per tree (small
 //                         launches) | DEEP walk the deep levels from the deep blocks
-//   per workgroup, once   "stage the top K levels": the node table's top levels into LDS; which tables serve the forest
+//   the host side         rdf_launch_plan.hpp: the arguments (EvalArgs) and how a launch's geometry and LDS layout are worked out
+//                         (plan_shape), the instantiations that exist (kForestKernels) and the one a plan takes (select_kernel);
+//                         below the kernels: the HIP calls around that plan, and the entry points
+//   per workgroup, once  "stage the top K levels": the node table's top levels into LDS; which tables serve the forest
 //                         (last-level table, deep blocks: their trailers)
 //   per tile              "take the next tile": the workgroup's own index first; after that "the look-ahead wave" -- the first wave to
 //                         leave the pixel loop of the tile before (the election at the loop's end) -- pulls from the per-XCD queues
@@ -1683,56 +1498,8 @@ __global__ void k_debug_div(const float *num, const float *den, float *out, size
 }
 
 // ------------------------------------------------------------------------------------------
-// host side
+// host side: the HIP calls around the launch plan (rdf_launch_plan.hpp has the knobs, the plan and the list of kernels)
 // ------------------------------------------------------------------------------------------
-// Tuning / test knobs: process-wide, each read once per call (atomic: a library two threads use must not tear them; a
-// call that overlaps a change sees the old or the new value).  A knob resolves itself in get(): the value its rdf_set_*
-// left, else its environment variable, else the caller's default; what is out of range is dealt with where the value is used.
-// The RDF_* environment is read ONCE per variable (the first call that looks at it; thread-safe): a
-// launch used to pay ten getenv scans of the environment, microseconds on the critical path of a sync-per-frame live loop.
-// The rdf_set_* knobs are the way to change a choice at run time.
-struct Knob {
-    const int unset;            // setter values up to this one mean "nothing set": 0 or -1, per knob
-    const char *const env;      // the environment variable behind the knob, or nullptr
-    std::atomic<int> value;
-    std::once_flag env_once;
-    int env_set = 0, env_val = 0;
-    Knob(int unset_, const char *env_) : unset(unset_), env(env_), value(unset_) {}
-    int get(int dflt, bool *by_setter = nullptr)
-    {
-        const int v = value;
-        if (by_setter) *by_setter = v > unset;
-        if (v > unset) return v;
-        if (!env) return dflt;
-        std::call_once(env_once, [this]() {
-            const char *s = getenv(env);
-            if (s && *s) { env_set = 1; env_val = atoi(s); }
-        });
-        return env_set ? env_val : dflt;
-    }
-};
-// (setter only: no environment variable names these three)
-Knob g_compaction{-1, nullptr};                         // unset: filtered launches compact their pixels; 0: never
-Knob g_group{0, nullptr};                               // unset: trees per lane chosen by forest size; 1..4: forced (rdf_set_group)
-Knob g_force_exact{0, nullptr};                         // unset: off (rdf_forest_pack hands the value itself to k_pack)
-Knob g_sched_mode{-1, nullptr};                         // unset: RDF_SCHED, a string that sched_mode() reads itself (default dynamic); 0 static, 1 dynamic, 2 one tile per workgroup
-// (one setter over two environment names: RDF_LDS_BUDGET for ordinary launches, RDF_COOP_LDS_BUDGET for those that walk deep blocks)
-Knob g_lds_budget{0, nullptr}, g_env_lds_budget{-1, "RDF_LDS_BUDGET"}, g_env_coop_lds_budget{-1, "RDF_COOP_LDS_BUDGET"};   // unset: by workgroup size
-// (environment only: no setter)
-Knob g_env_check_empty_small{-1, "RDF_CHECK_EMPTY_SMALL"};     // unset: small launches at labels_reduce 1 skip the empty-tile check
-Knob g_env_last_level_min_pct{-1, "RDF_LAST_LEVEL_MIN_PCT"};   // unset: 50
-Knob g_block_threads{0, "RDF_BLOCK"};                   // unset: 512 threads for launches that fill the chip, else 256
-Knob g_rows_per_wave{0, "RDF_ROWS_PER_WAVE"};           // unset: by launch size
-Knob g_halo{-1, "RDF_HALO"};                            // unset: by workgroup size, trees and labels_reduce
-Knob g_lds_levels{-1, "RDF_LDS_LEVELS"};                // unset: what the tile leaves
-Knob g_tree_waves{-1, "RDF_TREE_WAVES"};                // unset: on
-Knob g_stage_vec{-1, "RDF_STAGE_VEC"};                  // unset: on
-Knob g_layers_one_launch{-1, "RDF_LAYERS_ONE_LAUNCH"};  // unset/1: small packed layered runs evaluate their layers in one launch; 0: never
-Knob g_fold{-1, "RDF_FOLD"};                            // unset/1: narrow tiles for a label map's last <= 32 columns (EvalArgs.fold); 0: never
-Knob g_plain_levels{-1, "RDF_PLAIN_LEVELS"};            // unset/1: the level loop starts on its plain path where it can (EvalArgs.plain_levels); 0: never
-Knob g_deep_from{-1, "RDF_DEEP_FROM"};                  // unset: the table's own choice (choose_geometry); 0: never; > 0: from this level on (rounded up to a block root)
-Knob g_last_level_table{-1, "RDF_LAST_LEVEL_TABLE"};    // unset: level D-1 from the last-level table when it is usable and the forest uses half of that level; 1: whenever usable; 0: never
-
 // C-side cost of a call (rdf_debug_host_overhead): nanoseconds plan_launch and dispatch spend before the launch goes to the HIP
 // runtime, and inside the runtime's launch call
 std::atomic<unsigned long long> g_host_ns_plan{0}, g_host_ns_launch{0}, g_host_calls{0}, g_host_ns_layered{0}, g_host_layered_calls{0};
@@ -1743,31 +1510,9 @@ inline unsigned long long now_ns()
     return (unsigned long long)ts.tv_sec * 1000000000ull + (unsigned long long)ts.tv_nsec;
 }
 
-// Launches that walk deep blocks (their waves fetch the blocks through LDS slabs): what is left for the depth tile, the node
-// table, the mailbox and the pixel list next to 8 KB of slab per wave -- two 512-thread or four 256-thread workgroups per CU.
-int coop_lds_budget(int block)
-{
-    const int knob = g_lds_budget.get(0);
-    const int v = knob > 0 ? knob : g_env_coop_lds_budget.get(0);
-    if (v > 0) return v;
-    return block == 512 ? 81920 - 65536 - 1024 : 40960 - 32768 - 1024;
-}
-
-int lds_budget(int block)
-{
-    // per workgroup: five 256-thread or three 512-thread workgroups share a CU's 160 KB
-    const int knob = g_lds_budget.get(0);
-    int b = knob > 0 ? knob : g_env_lds_budget.get(block == 512 ? kDefaultLdsBudget512 : kDefaultLdsBudget);
-    if (b > 160 * 1024) b = 160 * 1024;
-    if (b < 0) b = 0;
-    return b;
-}
-
 // ---- what the host remembers between calls (rdf_host_state.hpp): one DeviceState per device, one registry of packed tables.
 // An entry point asks for the current device's state ONCE (current_device: the call's only hipGetDevice) and hands the reference
 // down; the HIP calls whose answers the state keeps are made here, outside its locks. ----
-using rdf_host::DeviceState;
-using rdf_host::PackedState;
 using rdf_host::StaleFlag;
 rdf_host::DeviceStates g_devices;
 rdf_host::PackedTables g_tables;        // keyed by the table's address alone, whichever device is current
@@ -1787,15 +1532,6 @@ int current_device(DeviceState **out)
     }
     *out = &ds;
     return 0;
-}
-
-int sched_mode()
-{
-    static const int from_env = []() {
-        const char *v = getenv("RDF_SCHED");
-        return (v && strcmp(v, "static") == 0) ? 0 : (v && strcmp(v, "tile") == 0) ? 2 : 1;
-    }();
-    return g_sched_mode.get(from_env);
 }
 
 // ---- scheduler slots: one per (device, stream) that has launched; beyond kSchedSlots distinct
@@ -1876,12 +1612,34 @@ struct SplitSpec {
     int *launched;      // (out) workgroups of the helper launch; 0: the launch was not split
 };
 
-template <int BLOCK, bool PACKED, int CMAX, bool STATS, int GROUP, bool COMPACT, bool DEEP = false>
-int launch_one(const EvalArgs &a, int lds_bytes, DeviceState &ds, int cus, hipStream_t st, const SplitSpec *split)
+// The kernel behind every key of kForestKernels, in the list's order: the one place that instantiates k_eval_forest.
+template <int NL>
+using ForestKernel = void (*)(EvalArgsN<NL>);
+template <size_t I>
+const void *forest_kernel_at()
 {
-    auto kern = k_eval_forest<BLOCK, PACKED, CMAX, STATS, GROUP, COMPACT, 1, false, DEEP>;
+    constexpr KernelKey k = kForestKernels[I];
+    return reinterpret_cast<const void *>(&k_eval_forest<k.block, k.packed, k.cmax, k.stats, k.group, k.compact, k.nl, k.tw, k.deep>);
+}
+template <size_t... I>
+std::array<const void *, sizeof...(I)> forest_kernels(std::index_sequence<I...>)
+{
+    return {{forest_kernel_at<I>()...}};
+}
+const std::array<const void *, kNumForestKernels> g_forest_kernels = forest_kernels(std::make_index_sequence<kNumForestKernels>{});
+
+// ... and the kernel of one key, for a launch of NL argument sets; nullptr: the list has no such kernel
+template <int NL>
+ForestKernel<NL> forest_kernel(const KernelKey &key)
+{
+    const int i = key.nl == NL ? kernel_index(key) : -1;
+    return i < 0 ? nullptr : reinterpret_cast<ForestKernel<NL>>(const_cast<void *>(g_forest_kernels[i]));
+}
+
+int launch_one(ForestKernel<1> kern, int block, const EvalArgs &a, int lds_bytes, DeviceState &ds, int cus, hipStream_t st, const SplitSpec *split)
+{
     int per_cu = 0;
-    const int rc = workgroups_per_cu(ds, reinterpret_cast<const void *>(kern), BLOCK, lds_bytes, &per_cu);
+    const int rc = workgroups_per_cu(ds, reinterpret_cast<const void *>(kern), block, lds_bytes, &per_cu);
     if (rc != RDF_OK) return rc;
     // persistent workgroups: as many as are resident at once, never more than there are tiles.  Mode 2 launches one
     // workgroup per tile instead (8 % slower alone: the node table is staged per tile) -- workgroups then retire all
@@ -1900,28 +1658,25 @@ int launch_one(const EvalArgs &a, int lds_bytes, DeviceState &ds, int cus, hipSt
         if (hgrid >= 1) {
             ka.l[0].q_static = (uint32_t)grid;
             ka.l[0].q_blocks = (uint32_t)(grid + hgrid);
-            hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BLOCK), lds_bytes, st, ka);
+            hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(block), lds_bytes, st, ka);
             hipError_t e = hipGetLastError();
             if (e != hipSuccess) return (int)e;
             ka.l[0].q_helper = 1;
-            hipLaunchKernelGGL(kern, dim3((unsigned)hgrid), dim3(BLOCK), lds_bytes, split->helper_stream, ka);
+            hipLaunchKernelGGL(kern, dim3((unsigned)hgrid), dim3(block), lds_bytes, split->helper_stream, ka);
             *split->launched = (int)hgrid;
             return (int)hipGetLastError();
         }
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BLOCK), lds_bytes, st, ka);
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(block), lds_bytes, st, ka);
     return (int)hipGetLastError();
 }
 
-// NL forests (the layers of a small layered run) in one launch: 256 threads, runtime rows, four trees per lane, no
-// pixel list -- the one geometry every small packed launch can take.
-template <int CMAX, int NL, bool TW = false>
-int launch_multi(const EvalArgsN<NL> &ka, int lds_bytes, DeviceState &ds, int cus, hipStream_t st)
+// NL forests (the layers of a small layered run) in one launch, or one forest as tree waves: every role a share of the grid.
+template <int NL>
+int launch_multi(ForestKernel<NL> kern, int block, const EvalArgsN<NL> &ka, int lds_bytes, DeviceState &ds, int cus, hipStream_t st)
 {
-    constexpr int kBlock = TW ? 512 : 256;      // tree waves: 8 waves = 8 / T pixel rows x T trees
-    auto kern = k_eval_forest<kBlock, true, CMAX, false, TW ? 1 : kGroup, false, NL, TW>;
     int per_cu = 0;
-    const int rc = workgroups_per_cu(ds, reinterpret_cast<const void *>(kern), kBlock, lds_bytes, &per_cu);
+    const int rc = workgroups_per_cu(ds, reinterpret_cast<const void *>(kern), block, lds_bytes, &per_cu);
     if (rc != RDF_OK) return rc;
     // every role gets the same number of persistent workgroups (all roles have the same tiles: same frame, same reduce)
     long long per_role = (long long)cus * per_cu / NL;
@@ -1929,88 +1684,9 @@ int launch_multi(const EvalArgsN<NL> &ka, int lds_bytes, DeviceState &ds, int cu
     for (int l = 0; l < NL; ++l) most_tiles = ka.l[l].n_tiles > most_tiles ? ka.l[l].n_tiles : most_tiles;
     if (per_role > (long long)most_tiles) per_role = most_tiles;
     if (per_role < 1) per_role = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(per_role * NL)), dim3(kBlock), lds_bytes, st, ka);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(per_role * NL)), dim3(block), lds_bytes, st, ka);
     return (int)hipGetLastError();
 }
-
-// Which instantiations exist (65 kernels; every one costs half a second of compile time and ~20 KB of code object, so the list is
-// what launches really take -- rows per wave, halo, LDS levels, scheduler are run-time arguments):
-//   packed table, no pixel list:         256 / 512 threads x 4 / 8 classes in registers x 1 / 2 / 3 / 4 trees in a lane, 16 classes x 1 / 4 trees
-//   packed table, filtered (pixel list): 256 / 512 threads x 4 / 8 / 16 classes x 4 trees in a lane
-//   reference-layout forest:             256 / 512 threads x 4 / 16 classes x 1 or 4 trees in a lane (a filtered launch
-//                                        takes the early-outs per lane instead of listing pixels)
-//   visit counters (rdf_eval_forest_stats): reference layout, 256 threads, classes four at a time
-//   visit and line counters of a packed launch (rdf_eval_forest_packed_stats): 256 / 512 threads, four classes, heap-order / deep
-//   deep blocks (launch_deep):           256 / 512 threads x 4 / 8 classes x 2 / 3 / 4 trees in a lane + the pixel-list variant
-//   layers of a stack / tree waves in one launch: launch_multi, 4 / 8 classes
-// A lane walks GROUP trees interleaved: forests of one, two, three or six trees (and `rdf_eval_tree`) get kernels without the
-// idle slots of the 4-wide one (measured: T = 1 costs 54 % of T = 4 with idle slots).  rdf_set_group overrides the choice by
-// forest size (any width is correct for any forest: slots beyond the last tree idle).
-int group_for(const EvalArgs &a, bool packed)
-{
-    const int knob = g_group.get(0);
-    const int g = knob > 0 ? knob : (a.T == 1 ? 1 : a.T == 2 ? 2 : (a.T == 3 || a.T == 6) ? 3 : 4);
-    return packed ? g : (g == 1 ? 1 : 4);
-}
-
-template <int BLOCK, bool PACKED, int CMAX>
-int launch_group(bool compact, const EvalArgs &a, int lds_bytes, DeviceState &ds, int cus, hipStream_t st, const SplitSpec *split)
-{
-    const int g = group_for(a, PACKED);
-    if constexpr (PACKED) {
-        if (compact) return launch_one<BLOCK, true, CMAX, false, 4, true>(a, lds_bytes, ds, cus, st, split);
-        if constexpr (CMAX <= 8) {      // (forests of more than eight classes: one or four trees in a lane only -- round 6 took the two- and
-                                        // three-wide sixteen-class kernels out to pay for the narrow tiles' code: slots beyond the last tree idle)
-            if (g == 2) return launch_one<BLOCK, true, CMAX, false, 2, false>(a, lds_bytes, ds, cus, st, split);
-            if (g == 3) return launch_one<BLOCK, true, CMAX, false, 3, false>(a, lds_bytes, ds, cus, st, split);
-        }
-        if (g == 1) return launch_one<BLOCK, true, CMAX, false, 1, false>(a, lds_bytes, ds, cus, st, split);
-        return launch_one<BLOCK, true, CMAX, false, 4, false>(a, lds_bytes, ds, cus, st, split);
-    } else {
-        return g == 1 ? launch_one<BLOCK, false, CMAX, false, 1, false>(a, lds_bytes, ds, cus, st, split)
-                      : launch_one<BLOCK, false, CMAX, false, 4, false>(a, lds_bytes, ds, cus, st, split);
-    }
-}
-
-template <int BLOCK>
-int launch_block(bool packed, bool compact, const EvalArgs &a, int lds_bytes, DeviceState &ds, int cus, hipStream_t st, const SplitSpec *split)
-{
-    if (packed) {
-        if (a.C <= 4) return launch_group<BLOCK, true, 4>(compact, a, lds_bytes, ds, cus, st, split);
-        if (a.C <= 8) return launch_group<BLOCK, true, 8>(compact, a, lds_bytes, ds, cus, st, split);
-        return launch_group<BLOCK, true, 16>(compact, a, lds_bytes, ds, cus, st, split);
-    }
-    if (a.C <= 4) return launch_group<BLOCK, false, 4>(false, a, lds_bytes, ds, cus, st, split);
-    return launch_group<BLOCK, false, 16>(false, a, lds_bytes, ds, cus, st, split);
-}
-
-// Launches that walk their deep levels from the deep blocks (packed forests of up to eight classes): the same choices of
-// workgroup size, classes in registers, trees per lane and pixel list as launch_block.
-template <int BLOCK, int CMAX>
-int launch_deep_c(bool compact, const EvalArgs &a, int lds_bytes, DeviceState &ds, int cus, hipStream_t st, const SplitSpec *split)
-{
-    if (compact) return launch_one<BLOCK, true, CMAX, false, 4, true, true>(a, lds_bytes, ds, cus, st, split);
-    switch (group_for(a, true)) {
-    case 1:         // (a single tree walks the two-wide kernel with one slot idle: forests that big have more trees)
-    case 2: return launch_one<BLOCK, true, CMAX, false, 2, false, true>(a, lds_bytes, ds, cus, st, split);
-    case 3: return launch_one<BLOCK, true, CMAX, false, 3, false, true>(a, lds_bytes, ds, cus, st, split);
-    default: return launch_one<BLOCK, true, CMAX, false, 4, false, true>(a, lds_bytes, ds, cus, st, split);
-    }
-}
-template <int BLOCK>
-int launch_deep(bool compact, const EvalArgs &a, int lds_bytes, DeviceState &ds, int cus, hipStream_t st, const SplitSpec *split)
-{
-    return a.cpad == 4 ? launch_deep_c<BLOCK, 4>(compact, a, lds_bytes, ds, cus, st, split) : launch_deep_c<BLOCK, 8>(compact, a, lds_bytes, ds, cus, st, split);
-}
-
-// Where the deep blocks take over when nothing was chosen (no knob, no rdf_forest_set_deep_from / rdf_forest_tune for the table):
-// NEVER -- the heap-order records, round 3's walk.  Round 4 switched forests of 32 MB of hot records and more to the blocks by
-// size alone; that default was slower on two of the three kinds of forest measured (synth's "full" topology 5.9 against 3.9 ms,
-// the trainer's own forest 0.83 against 0.70 ms: profiles/r04_trained_forest_probe.txt) and faster only where the deep levels
-// are occupied (balanced topology: 7.8 against 11.2 ms).  Nothing in the records tells the kinds apart, so the blocks are taken
-// only where a measurement on the caller's frames chose them: rdf_forest_tune, or rdf_forest_set_deep_from with a level found
-// that way (a good first guess for an occupied forest: the deepest root level that still holds <= 512 KB of heap-order records).
-constexpr int kUntunedDeepFrom = 0;
 
 // ---- the stale flag: one word of pinned host memory per device that kernels can write (PackInfo.generation) ----
 // allocated when a device's first packed table is looked at (never during a stream capture: packed_info refuses those)
@@ -2055,37 +1731,6 @@ uint32_t next_generation()      // non-zero, unlike any other this process drew;
     }
     uint32_t g = g_generation.fetch_add(2u, std::memory_order_relaxed) + 2u;   // (stays odd: never zero)
     return g;
-}
-
-static int classes_padded(int n_classes) { return (n_classes + 3) & ~3; }
-
-// the last-level table (LastLevelRec) behind the three per-slot tables, and the 64 bytes that hold its count of unusable
-// records: forests of one to four classes and two or more levels
-static size_t last_level_bytes(int n_trees, int max_depth, int n_classes)
-{
-    if (classes_padded(n_classes) != 4 || max_depth < 2 || n_trees < 1) return 0;
-    return ((size_t)n_trees << (max_depth - 1)) * sizeof(LastLevelRec) + 64;
-}
-
-// the deep blocks behind the last-level table (128-byte aligned), one all-zero line and a 128-byte trailer
-static size_t slot_tables_bytes(int n_trees, int max_depth, int n_classes)      // hot records + PDF rows
-{
-    return ((size_t)n_trees << max_depth) * (sizeof(NodeRec16) + 2 * (size_t)classes_padded(n_classes) * sizeof(float));
-}
-static size_t deep_offset(int n_trees, int max_depth, int n_classes)
-{
-    const size_t before = slot_tables_bytes(n_trees, max_depth, n_classes) + last_level_bytes(n_trees, max_depth, n_classes);
-    return (before + 127u) & ~(size_t)127u;
-}
-static size_t deep_bytes(int n_trees, int max_depth, int n_classes)
-{
-    if (!deep_possible(n_trees, max_depth, classes_padded(n_classes))) return 0;
-    return (deep_total_lines(n_trees, max_depth, classes_padded(n_classes)) + 2u) * 128u;
-}
-// the info block (PackInfo) is the table's last 128 bytes
-static size_t info_offset(int n_trees, int max_depth, int n_classes)
-{
-    return deep_offset(n_trees, max_depth, n_classes) + deep_bytes(n_trees, max_depth, n_classes);
 }
 
 // The table's info block as the host knows it; read back from the device once (a synchronous 128-byte copy behind whatever the
@@ -2138,276 +1783,8 @@ int set_deep_choice(const void *packed, int level, bool write_through)
     return RDF_OK;
 }
 
-int check_common(const void *depth, int n_img, int dim_x, int dim_y, const void *forest, int n_trees,
-                 int max_depth, int n_classes, const void *labels, int r)
-{
-    if (n_img < 0 || dim_x < 0 || dim_y < 0 || n_trees < 0 || max_depth < 0 || max_depth > 30 ||
-        n_classes < 0 || r < 1)
-        return RDF_ERR_BAD_ARG;
-    if ((long long)n_img * dim_x * dim_y >= (1ll << 31)) return RDF_ERR_TOO_LARGE;
-    // (a far probe's byte offset is one 24-bit multiply-add, TileCtx: y * 2W + 2x with y < 2^24 and 2W < 2^24)
-    if (dim_x >= (1 << 23) || dim_y >= (1 << 24)) return RDF_ERR_TOO_LARGE;
-    const long long total = (long long)n_img * (dim_x / r) * (dim_y / r);
-    if (total == 0) return 1; // nothing to do
-    if (!depth || !labels) return RDF_ERR_NULL_PTR;
-    if (!forest && n_trees > 0 && max_depth > 0) return RDF_ERR_NULL_PTR;
-    return 0;
-}
-
-// One forest evaluation as an entry point asks for it (eval_common; layered_run plans with it).
-struct Request {
-    const uint16_t *depth; int n_img, dim_x, dim_y;
-    const void *packed; const float *forest; int n_trees, max_depth, n_classes;
-    const uint16_t *filter; int filter_class;
-    uint16_t *labels_out; int r; float s; int keep_if_no_leaf;      // (r: labels_reduce; s: the scale factor of an unpacked forest)
-    unsigned long long *stats; void *stream;
-    int fill_untouched = 0;
-    bool allow_tw = true;       // (layered_run plans a second time without tree waves when not every layer can take them)
-};
-
-// The shape of a launch: workgroup size, rows per wave, tiles, and from which level on the deep blocks are wanted.
-struct Geometry {
-    uint32_t fold, tiles_x, tiles_y, tiles_y_n, tile_rows;
-    long long n_tiles;
-    bool big, tw;
-    int block, rpw, deep_from_wanted;
-};
-
-// What plan_launch works out and dispatch launches: the kernel arguments (without a queue slot), the dynamic LDS and the
-// geometry.  layered_run takes the plans of several layers and puts them into one launch itself.
-struct Plan {
-    EvalArgs a;
-    Geometry g;
-    int lds_bytes = 0;
-    DeviceState *ds = nullptr;          // the device current when the plan was made
-    bool empty = false, deep = false, compact_launch = false, packed = false, stats = false;
-    unsigned long long t_entry = 0;     // when plan_launch was entered (rdf_debug_host_overhead)
-};
-
-Geometry choose_geometry(const Request &q, int Wl, int Hl, int device_cus, const PackedState &ps, bool compaction)
-{
-    Geometry g = {};
-    g.tiles_x = ((uint32_t)Wl + 63u) / 64u;
-    // (round 6) a label map whose width leaves at most 32 columns beyond a multiple of 64 (848 = 13 x 64 + 16: every frame of the
-    // metric) gets NARROW tiles for those columns -- a wave covers 2 rows x 32 or 4 rows x 16 pixels there -- instead of a tile
-    // column whose waves run three quarters empty: 5.4 % fewer wave-rows on an 848-wide frame (EvalArgs.fold)
-    const int w_rem = Wl % 64;
-    if (g_fold.get(1) && Wl > 64 && w_rem != 0 && w_rem <= 32) {
-        g.fold = w_rem <= 16 ? 4u : 2u;
-        g.tiles_x = (uint32_t)Wl / 64u;
-    }
-    // Throughput shape: the launch fills the chip with four-row waves.  Small launches (a single live frame) take fewer
-    // rows per wave so that every CU still gets several waves.
-    const long long waves_wanted = 24ll * device_cus;
-    const bool big = (long long)q.n_img * g.tiles_x * ((Hl + kMaxRowsPerWave - 1) / kMaxRowsPerWave) >= waves_wanted;
-    // Workgroup size.  Big unfiltered launches: 512 threads, three workgroups per CU = 24 waves with a 48-pixel halo
-    // (54 KB of LDS each) instead of five 256-thread workgroups = 20 waves with 32 pixels: 4.77 vs 5.14 ms on the bench
-    // batch, 11.45 vs 12.60 ms on config 5's shard (profiles/r02_sweep_512.txt).  Small launches keep 256 threads.
-    int block = g_block_threads.get(0);
-    // (filtered launches at labels_reduce 1 gain nothing from 512 threads: 1.36 ms either way, 1.63 with this default's
-    // halo; at labels_reduce 2 they do: 0.46 vs 0.55 ms)
-    const bool filtered_r1 = q.packed && q.filter_class != -1 && compaction && q.r == 1;
-    if (block != 256 && block != 512) block = (big && !filtered_r1) ? 512 : 256;   // (other requests: the default)
-    if (q.stats && !q.packed) block = 256;      // (the packed visit-counter kernels take the geometry of the launch they describe)
-    // deep blocks (k_eval_forest<..., DEEP>): from which root level on.  The knob or RDF_DEEP_FROM names a level (rounded up
-    // to a block root by lay_out_lds, and never inside the levels LDS holds); nothing chosen: kUntunedDeepFrom.  (Tree-wave
-    // launches never walk them: see below.)
-    int deep_from_wanted = 0;
-    if (q.packed && deep_bytes(q.n_trees, q.max_depth, q.n_classes) != 0) {
-        deep_from_wanted = g_deep_from.get(-1);                                      // process-wide knob first,
-        if (deep_from_wanted < 0) deep_from_wanted = ps.deep_from;                   // then what was chosen for this packed forest,
-        if (deep_from_wanted < 0) deep_from_wanted = kUntunedDeepFrom;               // else the heap-order records
-        const char *dp = reinterpret_cast<const char *>(q.packed) + deep_offset(q.n_trees, q.max_depth, q.n_classes);
-        if ((reinterpret_cast<uintptr_t>(dp) & 127u) != 0) deep_from_wanted = 0;
-        // what the kernel would find in the blocks' trailer, known to the host since the table was first seen: blocks that cannot
-        // serve the forest (a level D-1 node that is not a plain two-leaf node; exact nodes down to the last block) are not planned
-        // for at all -- the launch takes the ordinary geometry instead of the deep one with heap-order records in it
-        if (deep_from_wanted > 0) {
-            const int R0 = q.max_depth - deep_last_levels(classes_padded(q.n_classes));
-            if (ps.deep_bad_last != 0u || (int)ps.deep_min_root > R0) deep_from_wanted = 0;
-            else if (deep_from_wanted < (int)ps.deep_min_root) deep_from_wanted = (int)ps.deep_min_root;      // (rounded up to a root later)
-        }
-    }
-    int rpw = g_rows_per_wave.get(0);
-    if (rpw < 1 || rpw > kMaxRowsPerWave) {
-        rpw = kMaxRowsPerWave;
-        if (big && block == 512) {
-            // 8 waves x 2 rows: the 64 x 16 tile of four waves x 4 rows -- when that gives every workgroup slot (three per
-            // CU) ten tiles or more; a smaller batch takes 8-row tiles, so that its last round is not half empty
-            // (848x480 frames: 4 in a launch 0.237 -> 0.212 ms, 8: 0.378 -> 0.362, 16: 0.696 -> 0.677; 24: 0.937 vs 0.952)
-            const long long tiles2 = (long long)q.n_img * g.tiles_x * ((Hl + 15) / 16);
-            rpw = tiles2 >= 30ll * device_cus ? 2 : 1;
-            // (deep blocks, eight trees and more: 8-row tiles leave the 15 KB beside the slabs to a 24-pixel halo -- config 5's
-            // shard on a balanced forest 18.5 -> 18.0 ms, profiles/r05_deep_coop.txt section 7)
-            if (deep_from_wanted > 0 && q.n_trees >= 8) rpw = 1;
-        }
-        while (rpw > 1 && (long long)q.n_img * g.tiles_x * ((Hl + rpw - 1) / rpw) < waves_wanted) rpw >>= 1;
-    }
-    // Tree waves (k_eval_forest<..., TW>): a small unfiltered packed launch of a forest of 2-4 trees gives every tree
-    // of a pixel row a wave of its own -- 512 threads = 8 waves = 8 / T rows of 64 pixels x T trees (two rows for three or
-    // four trees: half the tile of four waves x four trees in a lane, on twice the CUs).  One live 848x480 frame at
-    // labels_reduce 2 (T4/D20): 31 -> 19 us; a dense one 37 -> 31 us (with 1 024 threads = four rows x four trees: 20 and
-    // 35 us; with 256 = one row: 32 and 44 us, more tiles than workgroup slots).  Only for label maps of up to 128 K pixels:
-    // a tile now needs four times the wave slots, and a dense 848x480 frame at full resolution got slower (82 -> 95 us with
-    // the 1 024-thread shape; live: 48 -> 42).  The layers of a stack evaluated in one launch (rdf_layered_run) take the
-    // same shape when every layer can.
-    const bool tw = q.allow_tw && g_tree_waves.get(1) != 0 && !big && !q.stats && q.packed && q.filter_class == -1 && block == 256 &&
-                    q.n_trees >= 2 && q.n_trees <= 4 && q.n_classes <= 8 && q.max_depth >= 1 && sched_mode() != 2 &&
-                    (long long)q.n_img * Wl * Hl <= 131072;
-    if (tw) { rpw = 1; block = 512; deep_from_wanted = 0; }
-    g.tile_rows = tw ? (uint32_t)(8 / q.n_trees) : (uint32_t)(block / 64) * (uint32_t)rpw;
-    g.tiles_y = ((uint32_t)Hl + g.tile_rows - 1u) / g.tile_rows;
-    g.tiles_y_n = g.fold ? ((uint32_t)Hl + g.tile_rows * g.fold - 1u) / (g.tile_rows * g.fold) : 0u;
-    g.n_tiles = (long long)q.n_img * ((long long)g.tiles_x * g.tiles_y + g.tiles_y_n);
-    g.big = big; g.tw = tw; g.block = block; g.rpw = rpw; g.deep_from_wanted = deep_from_wanted;
-    return g;
-}
-
-// The staged depth tile at halo h: width, height and row pitch in pixels and its bytes, for the ordinary tiles and (fold != 0)
-// the narrow ones, whose halo in x may come out smaller (hx_n).
-struct TileShape {
-    long long tw, th, twp, bytes, tw_n, th_n, twp_n, hx_n;
-};
-
-// A wave of a narrow tile reads `fold` rows of the staged tile at once: with a row pitch of a whole number of LDS bank
-// sweeps (256 bytes: 16 columns + 2 x 56 of halo) the rows fall into the SAME banks -- a four-way conflict on every probe
-// (measured: the narrow tiles gave 2 % where their 5 % fewer wave-rows promised more).  The pitch modulo 256 bytes must
-// leave room for one row segment on either side: padding when it fits the budget, else a few columns less halo in x.
-// Sets the narrow tile's width and pitch for a halo of hx in x and `pad` columns of padding; true when the pitch is such a one.
-bool narrow_pitch(TileShape &s, long long hx, long long pad, int r, uint32_t fold, bool vec)
-{
-    const long long seg = (64ll / fold) * 2 * r;          // bytes one row of a wave spans
-    s.tw_n = (64ll / fold - 1) * r + 1 + 2ll * hx;
-    if (vec) s.tw_n = (s.tw_n + 7) & ~7ll;
-    s.twp_n = (vec ? s.tw_n : (s.tw_n + 1) & ~1ll) + pad;
-    const long long m = (s.twp_n * 2) % 256;
-    return seg > 128 || (m >= seg && m <= 256 - seg);
-}
-
-TileShape tile_shape(int h, int r, uint32_t tile_rows, uint32_t fold, bool vec)
-{
-    TileShape s = {};
-    s.tw = 63ll * r + 1 + 2ll * h;
-    s.th = ((long long)tile_rows - 1) * r + 1 + 2ll * h;
-    if (vec) s.tw = (s.tw + 7) & ~7ll;                      // a few more columns than the probes' reach: harmless
-    s.twp = vec ? s.tw : (s.tw + 1) & ~1ll;
-    if (vec && (s.twp * 2) % 512 == 0) s.twp += 8;          // not a whole number of LDS bank sweeps per row
-    s.bytes = (s.th * s.twp * 2 + 15) & ~15ll;
-    s.hx_n = h;
-    // (narrow tiles: 64 / fold columns x fold x tile_rows rows of centres, the same halo; the allocation holds either shape)
-    if (fold) {
-        s.th_n = ((long long)tile_rows * fold - 1) * r + 1 + 2ll * h;
-        bool ok_banks = narrow_pitch(s, h, 0, r, fold, vec);
-        for (long long pad = 8; !ok_banks && pad <= 64; pad += 8)
-            ok_banks = narrow_pitch(s, h, pad, r, fold, vec) && ((s.th_n * s.twp_n * 2 + 15) & ~15ll) <= s.bytes;   // (padding that costs no halo)
-        for (long long hx = h - (vec ? 8 : 2); !ok_banks && hx >= 0 && hx >= h - 24; hx -= (vec ? 8 : 2)) {
-            ok_banks = narrow_pitch(s, hx, 0, r, fold, vec);
-            if (ok_banks) s.hx_n = hx;
-        }
-        if (!ok_banks) (void)narrow_pitch(s, h, 0, r, fold, vec);
-        s.bytes = std::max(s.bytes, (s.th_n * s.twp_n * 2 + 15) & ~15ll);
-    }
-    return s;
-}
-
-// ---- LDS plan: [depth tile: th*twp*2 B, at address 0][node table: T*2^K*16 B][queue mailbox 32 B][pixel list][slabs] ----
-// Fills the LDS side of the kernel arguments (tile, levels, last-level table, deep blocks, offsets) and returns the dynamic LDS bytes.
-int lay_out_lds(const Request &q, const Geometry &g, bool compact_launch, EvalArgs &a)
-{
-    const int block = g.block, r = q.r, n_trees = q.n_trees, max_depth = q.max_depth;
-    // A launch that walks deep blocks fetches them by the WAVE, through a slab of 8 KB per wave in LDS (k_eval_forest<..., DEEP>): the
-    // slabs take 64 KB of a 512-thread workgroup (32 KB of a 256-thread one), so such a launch keeps a smaller depth tile and
-    // fewer levels in LDS and runs two (four) workgroups per CU instead of three (five).
-    const bool coop = g.deep_from_wanted > 0;
-    const long long slab_bytes = coop ? (long long)(block / 64) * 8192 : 0;
-    // (whatever the budget knob says: a workgroup's tile, node table and slabs together fit a CU's 160 KB)
-    const long long budget = coop ? std::min<long long>(coop_lds_budget(block), 163840 - slab_bytes - 2048) : lds_budget(g.tw ? 256 : block);
-    // Halo and the levels that must stay in LDS, by measurement (profiles/r02_sweep_*.txt).  256-thread workgroups (32.7 KB):
-    // four trees 7 levels + 32 px (5.17 ms; 8 + 24: 5.26, 6 + 40: 5.61), eight trees 5 levels + 40 px (config 5's shape:
-    // 12.68 ms; 6 + 32: 12.90).  512-thread workgroups (54.6 KB): 56 px with 7 levels (4.74 ms; 8 + 48: 4.76) or, for eight
-    // trees, 5 levels (11.45 ms; 6 + 48: 11.66).  With labels_reduce > 1 the halo shrinks until the tile fits.
-    const bool many_trees = n_trees >= 8;
-    // (labels_reduce 2, 64 frames, 512 threads: 6 levels + 32 px 0.81 ms, 7 + 40 0.89 ms -- a tile spans r times the pixels)
-    const int halo_default = coop ? (block == 512 ? (many_trees ? 24 : 16) : 8)
-                                  : block == 512 ? (r > 1 ? 32 : 56) : (many_trees ? kDefaultHalo + 8 : kDefaultHalo);
-    const int halo = g_halo.get(halo_default);
-    // The staged tile may take half the budget.  With labels_reduce > 1 a tile spans r times the pixels per label, so
-    // the halo shrinks (by twos) until the tile fits -- a narrow tile still beats none: 64 frames at r = 2 take 1.08 ms
-    // with an 8-pixel halo against 1.49 ms with every probe going to global memory; only when not even the bare
-    // centres fit is the tile dropped.
-    // (Throughput shape only: for a single small frame staging a narrow tile cost more than it saved, 91 vs 87 us.)
-    const int h_min = g.big ? 0 : halo;
-    // pixel list: one uint16 per tile pixel, then one uint32 per tile row
-    // (tree waves use the list region for the words the trees of a row exchange: tile_rows x T x 64)
-    const long long list_bytes = g.tw ? (long long)g.tile_rows * n_trees * 256 :
-                                 compact_launch ? (((long long)block * g.rpw * 2 + (long long)g.tile_rows * 4) + 15) & ~15ll : 0;
-    // levels of the forest the caller pinned into LDS (rdf_set_lds_levels): the tile then gets all that is left of the
-    // budget instead of half of it
-    int k_forced = g_lds_levels.get(-1);
-    if (k_forced > max_depth) k_forced = max_depth;
-    while (k_forced > 0 && (long long)n_trees * (1ll << k_forced) * 16 + 32 + list_bytes > budget) --k_forced;
-    // otherwise the tile may take what kMinLdsLevels levels of the forest leave: level for level, a level moved from LDS
-    // to L1-resident global records costs less than the far probes a wider halo saves (measured: T4, 8 levels + 24 px
-    // 5.26 ms, 7 levels + 32 px 5.17 ms, 6 levels + 40 px 5.6 ms on the bench batch)
-    const int k_min = coop ? (many_trees ? kMinLdsLevels - 2 : kMinLdsLevels - 1)       // (4 and 5 levels)
-                           : many_trees ? kMinLdsLevels - 1 : (block == 512 && r == 1 ? kMinLdsLevels + 1 : kMinLdsLevels);
-    const int k_floor = k_forced >= 0 ? k_forced : (max_depth < k_min ? max_depth : k_min);
-    const long long tile_budget = budget - 32 - list_bytes - (k_floor > 0 ? (long long)n_trees * (1ll << k_floor) * 16 : 0);
-    // 16-byte staging needs every row start 16-byte aligned in the image and in LDS
-    const bool vec_ok = g_stage_vec.get(1) && q.dim_x % 8 == 0 && ((64 * r) % 8 == 0) && (reinterpret_cast<uintptr_t>(q.depth) & 15u) == 0;
-    long long tile_bytes = 0;
-    for (int h = halo; h >= h_min && h >= 0; h -= 2) {
-        const bool vec = vec_ok && h % 8 == 0;
-        const TileShape s = tile_shape(h, r, g.tile_rows, a.fold, vec);
-        if (s.bytes > tile_budget) continue;
-        tile_bytes = s.bytes;
-        a.halo = h; a.tw = (int)s.tw; a.th = (int)s.th; a.twp = (int)s.twp;
-        a.tw_n = (int)s.tw_n; a.th_n = (int)s.th_n; a.twp_n = (int)s.twp_n; a.halo_xn = (int)s.hx_n;
-        if (vec) {
-            a.stage_tw8 = (uint32_t)(s.tw >> 3);
-            a.stage_magic = (uint32_t)((1ull << 32) / a.stage_tw8) + 1u;
-            if (a.fold) {
-                a.stage_tw8_n = (uint32_t)(s.tw_n >> 3);
-                a.stage_magic_n = (uint32_t)((1ull << 32) / a.stage_tw8_n) + 1u;
-            }
-        }
-        break;
-    }
-    int K = 0;
-    while (K < max_depth && (k_forced < 0 || K < k_forced) &&
-           (long long)n_trees * (1ll << (K + 1)) * 16 + tile_bytes + 32 + list_bytes <= budget) ++K;
-    a.lds_levels = K;
-    // level D-1 from the last-level table (LastLevelRec) when the forest was packed with one and that level is not in LDS
-    bool llt_by_setter = false;
-    const int want_llt = g_last_level_table.get(1, &llt_by_setter);
-    if (q.packed && want_llt != 0 && !g.tw && max_depth - 1 >= K && last_level_bytes(n_trees, max_depth, q.n_classes) != 0) {
-        a.last_level = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(a.packed_pdf) +
-                                                       ((size_t)n_trees << max_depth) * 2 * (size_t)a.cpad * sizeof(float));
-        // from which share of level D-1 in use (see k_pack) on: by default half; knob 1 = whenever the table is usable
-        const int pct = llt_by_setter && want_llt == 1 ? 0 : g_env_last_level_min_pct.get(50);
-        a.last_level_min = (uint32_t)((((unsigned long long)n_trees << (max_depth - 1)) * (unsigned long long)(pct < 0 ? 0 : pct > 100 ? 100 : pct)) / 100u);
-    }
-    if (coop) {
-        const int R0 = max_depth - deep_last_levels(a.cpad);
-        int from = g.deep_from_wanted;
-        if (from < K) from = K;
-        if (from > R0) from = R0;
-        from = R0 - 3 * ((R0 - from) / 3);          // a root level: R0 - 3 i, rounded up
-        a.deep = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(q.packed) + deep_offset(n_trees, max_depth, q.n_classes));
-        a.deep_from = from;
-    }
-    const long long node_bytes = K > 0 ? (long long)n_trees * (1ll << K) * 16 : 0;
-    a.lds_nodes_off = (uint32_t)tile_bytes;
-    a.lds_mail_off = (uint32_t)(tile_bytes + node_bytes);
-    a.lds_list_off = (uint32_t)(tile_bytes + node_bytes + 32);
-    a.lds_xchg_off = a.lds_list_off;
-    // (the slabs start on a 1-KB boundary: an LDS-DMA piece is 1 KB)
-    const long long slab_at = (tile_bytes + node_bytes + 32 + list_bytes + 1023) & ~1023ll;
-    a.lds_slab_off = (uint32_t)slab_at;
-    return coop ? (int)(slab_at + slab_bytes) : (int)(node_bytes + tile_bytes + 32 + list_bytes);
-}
-
-// Everything about a launch that can be known without making it (no HIP call beyond the first look at a packed table).
+// Everything about a launch that can be known without making it: the argument checks, what HIP has to be asked (the current
+// device; for a packed request the stale flag and the first look at the table), then the plan itself (plan_shape).
 // `dsp`: the current device's state, looked up here -- after the argument checks, as ever -- if the caller has none yet (nullptr).
 int plan_launch(DeviceState *&dsp, const Request &q, Plan *plan)
 {
@@ -2420,57 +1797,19 @@ int plan_launch(DeviceState *&dsp, const Request &q, Plan *plan)
     if (q.filter_class != -1 && !q.filter) return RDF_ERR_NULL_PTR;
     if (!dsp && (rc = current_device(&dsp)) != 0) return rc;
     DeviceState &ds = *dsp;
-    EvalArgs &a = plan->a;
     PackedState ps;
-    memset(&a, 0, sizeof(a));
-    a.depth = q.depth; a.forest = q.forest; a.filter = q.filter; a.labels = q.labels_out;
-    a.stats = q.stats;
-    a.W = q.dim_x; a.H = q.dim_y; a.Wl = q.dim_x / q.r; a.Hl = q.dim_y / q.r; a.r = q.r;
-    a.per_img_l = (uint32_t)a.Wl * (uint32_t)a.Hl;
-    a.per_img_d = (uint32_t)q.dim_x * (uint32_t)q.dim_y;
-    a.T = q.n_trees; a.D = q.max_depth; a.C = q.n_classes; a.E = 7 + 2 * q.n_classes;
-    a.nodes = (int)((1ll << q.max_depth) - 1);
-    a.filter_class = q.filter_class;
-    a.keep_if_no_leaf = q.keep_if_no_leaf;
-    a.fill_untouched = q.fill_untouched;
-    a.s = q.s;
     if (q.packed) {
-        const size_t slots = (size_t)q.n_trees << q.max_depth;   // 1-based heap slots, 2^D per tree
-        a.packed16 = reinterpret_cast<const NodeRec16 *>(q.packed);
-        a.packed_pdf = reinterpret_cast<const float *>(a.packed16 + slots);
-        a.cpad = classes_padded(q.n_classes);
-        // nodes that need the exact numerators read them from the caller's forest, with the scale the table was packed for
         // a kernel of an earlier call found a table that was not the one the host remembered at its address (a copy over a
         // known address without rdf_forest_forget): what the host knew is gone, this call says so, the next one reads afresh
         if (stale_flag_raised(ds)) return RDF_ERR_STALE;
         rc = packed_info(ds, q.packed, q.n_trees, q.max_depth, q.n_classes, q.stream, &ps);
         if (rc != RDF_OK) return rc;
-        if (ps.exact_nodes > 0 && !q.forest) return RDF_ERR_NULL_PTR;
-        a.s = ps.scale;
-        a.info = reinterpret_cast<const PackInfo *>(ps.info_dev);
-        a.expect_gen = ps.generation;
-        a.stale_flag = ds.stale_flag_if_made().dev;
     }
-    const bool compaction = g_compaction.get(1) != 0;
-    const Geometry &g = plan->g = choose_geometry(q, a.Wl, a.Hl, ds.cus.load(std::memory_order_relaxed), ps, compaction);
-    if (g.n_tiles >= (1ll << 31)) return RDF_ERR_TOO_LARGE;
-    a.fold = g.fold; a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y; a.tiles_y_n = g.tiles_y_n;
-    a.n_tiles = (uint32_t)g.n_tiles; a.rows_per_wave = g.rpw;
-    a.plain_levels = g_plain_levels.get(1) != 0;
-    // the empty-tile check (see the kernel): always on launches that fill the chip; on small launches only at labels_reduce > 1,
-    // where a staged tile covers r x r times the image per label pixel and a live frame is mostly background (config 3's
-    // two-layer frame 30.5 -> 29.2 us; at labels_reduce 1 the extra round trip costs more than the skipped staging saves:
-    // one live 848x480 frame 41.6 -> 43.5 us, a dense one 76 -> 77 us, tools/latency.py with RDF_CHECK_EMPTY_SMALL=1)
-    a.check_empty = (g.big || q.r > 1) ? 1 : g_env_check_empty_small.get(0);
-    // filtered launches of the default geometry carry the pixel list in LDS (k_eval_forest<..., COMPACT>)
-    plan->compact_launch = q.packed && !q.stats && q.filter_class != -1 && compaction;
-    plan->lds_bytes = lay_out_lds(q, g, plan->compact_launch, a);
-    plan->ds = &ds; plan->deep = g.deep_from_wanted > 0;
-    plan->packed = q.packed != nullptr; plan->stats = q.stats != nullptr;
-    return RDF_OK;
+    plan->ds = &ds;
+    return plan_shape(q, ps, ds.cus.load(std::memory_order_relaxed), ds.stale_flag_if_made().dev, plan);
 }
 
-// Takes the queue slot and names the instantiation that makes the launch `p` describes.
+// Takes the queue slot and the kernel select_kernel names for the launch `p` describes, and makes the launch.
 int dispatch(const Plan &p, void *stream, const SplitSpec *split)
 {
     EvalArgs a = p.a;
@@ -2480,28 +1819,18 @@ int dispatch(const Plan &p, void *stream, const SplitSpec *split)
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int cus = usable_cus(ds, st);   // a CU-masked stream holds fewer persistent workgroups
     const unsigned long long t_launch = now_ns();
+    const KernelKey key = select_kernel(p);
+    if (key.block == 0) return RDF_ERR_BAD_ARG;
+    const ForestKernel<1> kern = forest_kernel<1>(key);
+    if (!kern) return RDF_ERR_BUILD;        // (never: every key select_kernel returns is in the list, tests/launch_plan_main.cpp)
+    if (key.stats && key.packed) a.stats_wide = 1;
     int rc;
-    if (p.g.tw) {
+    if (key.tw) {
         EvalArgsN<1> ka;
         ka.l[0] = a;
-        rc = a.C <= 4 ? launch_multi<4, 1, true>(ka, p.lds_bytes, ds, cus, st) : launch_multi<8, 1, true>(ka, p.lds_bytes, ds, cus, st);
-    } else if (p.stats && p.packed) {
-        // the launch rdf_eval_forest_packed would make, with the visit and line counters on (four classes, no pixel list)
-        if (a.C > 4 || p.compact_launch) return RDF_ERR_BAD_ARG;
-        a.stats_wide = 1;
-        if (p.deep)
-            rc = p.g.block == 512 ? launch_one<512, true, 4, true, 4, false, true>(a, p.lds_bytes, ds, cus, st, split)
-                                : launch_one<256, true, 4, true, 4, false, true>(a, p.lds_bytes, ds, cus, st, split);
-        else
-            rc = p.g.block == 512 ? launch_one<512, true, 4, true, 4, false, false>(a, p.lds_bytes, ds, cus, st, split)
-                                : launch_one<256, true, 4, true, 4, false, false>(a, p.lds_bytes, ds, cus, st, split);
-    } else if (p.stats) {   // (reference layout, 256 threads: choose_geometry chose both)
-        rc = launch_one<256, false, 4, true, 4, false>(a, p.lds_bytes, ds, cus, st, split);
-    } else if (p.deep) {
-        rc = p.g.block == 512 ? launch_deep<512>(p.compact_launch, a, p.lds_bytes, ds, cus, st, split) : launch_deep<256>(p.compact_launch, a, p.lds_bytes, ds, cus, st, split);
+        rc = launch_multi<1>(kern, key.block, ka, p.lds_bytes, ds, cus, st);
     } else {
-        rc = p.g.block == 512 ? launch_block<512>(p.packed, p.compact_launch, a, p.lds_bytes, ds, cus, st, split)
-                            : launch_block<256>(p.packed, p.compact_launch, a, p.lds_bytes, ds, cus, st, split);
+        rc = launch_one(kern, key.block, a, p.lds_bytes, ds, cus, st, split);
     }
     const unsigned long long t_done = now_ns();
     g_host_ns_plan.fetch_add(t_launch - p.t_entry, std::memory_order_relaxed);
@@ -2525,8 +1854,9 @@ int launch_layers(const Plan *plans, bool tw_all, int cmax, int lds, DeviceState
 {
     EvalArgsN<NL> ka;
     for (int i = 0; i < NL; ++i) ka.l[i] = plans[i].a;
-    if (tw_all) return cmax == 4 ? launch_multi<4, NL, true>(ka, lds, ds, cus, st) : launch_multi<8, NL, true>(ka, lds, ds, cus, st);
-    return cmax == 4 ? launch_multi<4, NL>(ka, lds, ds, cus, st) : launch_multi<8, NL>(ka, lds, ds, cus, st);
+    const KernelKey key = select_layers_kernel(NL, cmax, tw_all);
+    const ForestKernel<NL> kern = forest_kernel<NL>(key);
+    return kern ? launch_multi<NL>(kern, key.block, ka, lds, ds, cus, st) : RDF_ERR_BUILD;
 }
 
 } // namespace

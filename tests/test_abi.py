@@ -120,8 +120,8 @@ def test_code_object_targets_gfx950(name, rdf):
 
 
 def test_code_object_stays_small(rdf, tmp_path):
-    """Every instantiation of the forest kernel costs compile time and code size; the dispatch in rdf_hip.hip lists the
-    ones launches really take.  Fewer than 75 of them (16 walk the deep blocks, 4 count visits and lines), and a library under 1.9 MB."""
+    """Every instantiation of the forest kernel costs compile time and code size; kForestKernels in rdf_launch_plan.hpp lists
+    the ones launches really take.  Fewer than 75 of them (16 walk the deep blocks, 4 count visits and lines), and a library under 1.9 MB."""
     import shutil
     import subprocess
     so = import_module("3d-beats_amd._build").build()

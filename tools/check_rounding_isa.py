@@ -24,7 +24,8 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "3d-beats_amd", "csrc", "rdf_hip.hip")
-HDRS = [os.path.join(ROOT, "3d-beats_amd", "csrc", "rdf_device.hpp"), os.path.join(ROOT, "include", "rdf_hip.h")]
+HDRS = [os.path.join(ROOT, "3d-beats_amd", "csrc", "rdf_device.hpp"), os.path.join(ROOT, "3d-beats_amd", "csrc", "rdf_launch_plan.hpp"),
+        os.path.join(ROOT, "include", "rdf_hip.h")]
 NEAREST_ONLY = ("v_add_f32", "v_sub_f32", "v_subrev_f32", "v_mul_f32", "v_pk_add_f32", "v_pk_mul_f32", "v_fmac_f32", "v_rcp_f32",
                 "v_div_scale_f32", "v_div_fmas_f32", "v_div_fixup_f32", "v_mac_f32", "v_madak_f32", "v_madmk_f32", "v_fmaak_f32", "v_fmamk_f32")
 DOWN_ONLY = ("v_pk_fma_f32",)

@@ -41,17 +41,22 @@ def edit():
     # -- bigger workgroups
     t = sub1(t, "__launch_bounds__(BLOCK, TW ? 8 : DEEP ? 4 : BLOCK == 512 ? 6 : BLOCK == 256 ? 5 : 4)",
              "__launch_bounds__(BLOCK, TW ? 8 : DEEP ? 4 : BLOCK == 512 ? 6 : BLOCK == 256 ? 5 : BLOCK == 768 ? 6 : BLOCK == 896 ? 7 : BLOCK == 1024 ? RDF_EXP_WAVES_1024 : 4)")
-    t = sub1(t, "namespace {\n\nconstexpr int kGroup = 4;", "#ifndef RDF_EXP_WAVES_1024\n#define RDF_EXP_WAVES_1024 4\n#endif\nnamespace {\n\nconstexpr int kGroup = 4;")
-    t = sub1(t, "if (block != 256 && block != 512) block = (big && !filtered_r1) ? 512 : 256;",
+    # (the host side of it -- the geometry, the list of kernels and the selection -- is in the launch plan's header)
+    hp = os.path.join(SRC, "rdf_launch_plan.hpp")
+    h = open(hp).read()
+    h = sub1(h, "namespace {\n\nconstexpr int kGroup = 4;", "#ifndef RDF_EXP_WAVES_1024\n#define RDF_EXP_WAVES_1024 4\n#endif\nnamespace {\n\nconstexpr int kGroup = 4;")
+    h = sub1(h, "if (block != 256 && block != 512) block = (big && !filtered_r1) ? 512 : 256;",
              "if (block != 256 && block != 512 && block != 768 && block != 896 && block != 1024) block = (big && !filtered_r1) ? 512 : 256;\n"
              "    if (block > 512 && (!q.packed || q.filter_class != -1 || q.n_classes > 4 || q.stats)) block = 512;")
-    t = sub1(t, "        rc = p.g.block == 512 ? launch_block<512>(p.packed, p.compact_launch, a, p.lds_bytes, ds, cus, st, split)\n",
-             "        rc = p.g.block == 768 ? launch_one<768, true, 4, false, 4, false>(a, p.lds_bytes, ds, cus, st, split)\n"
-             "           : p.g.block == 896 ? launch_one<896, true, 4, false, 4, false>(a, p.lds_bytes, ds, cus, st, split)\n"
-             "           : p.g.block == 1024 ? launch_one<1024, true, 4, false, 4, false>(a, p.lds_bytes, ds, cus, st, split)\n"
-             "           : p.g.block == 512 ? launch_block<512>(p.packed, p.compact_launch, a, p.lds_bytes, ds, cus, st, split)\n")
+    h = sub1(h, "constexpr KernelKey kForestKernels[] = {\n",
+             "constexpr KernelKey kForestKernels[] = {\n"
+             "    {768, true, 4, false, 4, false, 1, false, false}, {896, true, 4, false, 4, false, 1, false, false}, {1024, true, 4, false, 4, false, 1, false, false},\n")
+    h = sub1(h, "    const int block = p.g.block == 512 ? 512 : 256;\n",
+             "    const int block = p.g.block == 512 ? 512 : 256;\n"
+             "    if (p.g.block > 512 && !p.deep) return {p.g.block, true, 4, false, 4, false, 1, false, false};\n")
     # (rows per wave for the big blocks: the knob; default 2)
-    t = sub1(t, "        if (big && block == 512) {", "        if (big && block >= 512) {")
+    h = sub1(h, "        if (big && block == 512) {", "        if (big && block >= 512) {")
+    open(hp, "w").write(h)
     # -- ablations
     t = sub1(t, "                                float4 pa = *reinterpret_cast<const float4 *>(pp);\n"
                 "                                float4 pb = *reinterpret_cast<const float4 *>(pp + 1);\n",

@@ -40,7 +40,7 @@ def isa_text(path=None):
     if path:
         return open(path).read().splitlines()
     out = os.path.join(tempfile.gettempdir(), "rdf_hip_gfx950.s")
-    newest = max(os.path.getmtime(p) for p in [SRC] + [os.path.join(os.path.dirname(SRC), h) for h in ("rdf_device.hpp", "rdf_host_state.hpp")])
+    newest = max(os.path.getmtime(p) for p in [SRC] + [os.path.join(os.path.dirname(SRC), h) for h in ("rdf_device.hpp", "rdf_host_state.hpp", "rdf_launch_plan.hpp")])
     if not os.path.exists(out) or os.path.getmtime(out) < newest:
         subprocess.check_call(["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-fno-fast-math", "-ffp-contract=off",
                                "-S", "--cuda-device-only", "-o", out, SRC], stderr=subprocess.DEVNULL)
