@@ -187,10 +187,36 @@ def score_saved_model(model_path, dataset_dir, num_images, labels_reduce=1):
     return scorer.add(out, truth, labels_reduce, per_image=True).result()
 
 
-def score_layered_model(config_filename, dataset_dir, num_images, labels_reduce=2, scale_factor=1.):
+def calibrate_saved_model(model_path, dataset_dir, num_images, labels_reduce=1, bins=64):
+    """score_saved_model's flow through ONE ungated posterior pass (DecisionTreeEvaluator.get_posteriors_forest, min_conf 0):
+    returns (score.Score, score.Calibration) of the forest on `num_images` random images, read as score_saved_model reads
+    them -- with the same numpy seed the Score is score_saved_model's.  The Calibration says how often a pixel of a given
+    confidence is right, and picks a rejection threshold from that (Calibration.min_conf_for).  No map is read back."""
+    from .decision_tree import DecisionForest, DecisionTreeEvaluator
+    from .device import DeviceArray
+    from .score import ConfidenceScorer, LabelScorer
+    from .util import MAX_UINT16
+    forest = DecisionForest.load(model_path)
+    ev = DecisionTreeEvaluator()
+    ds = DecisionTreeDatasetConfig(dataset_dir, num_images=num_images, imgs_name='test')
+    n, h, w = ds.images_shape()
+    depth = DeviceArray((n, h, w), np.uint16)
+    ds.get_depth_block_cu(0, depth)
+    truth = DeviceArray((n, h, w), np.uint16)
+    ds.get_labels_block_cu(0, truth)
+    out = DeviceArray((n, h // labels_reduce, w // labels_reduce), np.uint16).fill(MAX_UINT16)
+    conf = DeviceArray(out.shape, np.uint16).fill(0)
+    ev.get_posteriors_forest(forest, depth, out, conf, labels_reduce=labels_reduce)
+    scorer = LabelScorer(max(int(forest.num_classes), ds.num_classes()))
+    score = scorer.add(out, truth, labels_reduce, per_image=True).result()
+    return score, ConfidenceScorer(bins).add(out, conf, truth, labels_reduce).result()
+
+
+def score_layered_model(config_filename, dataset_dir, num_images, labels_reduce=2, scale_factor=1., min_conf=None):
     """Score a layered model -- what the app runs -- on `num_images` random images of a dataset: LayeredDecisionForest.run per
     frame into one [N, H // r, W // r] array of composite labels, scored in one pass against the truth sampled at
-    (x * r, y * r).  The host comparison cannot do this: the shapes differ.  The dataset's ids must be the composite's."""
+    (x * r, y * r).  The host comparison cannot do this: the shapes differ.  The dataset's ids must be the composite's.
+    min_conf: the stack's per-layer confidence thresholds (LayeredDecisionForest.min_conf); None: plain labels."""
     from .decision_tree import LayeredDecisionForest
     from .device import DeviceArray
     from .engine.buffer import GpuBuffer
@@ -198,6 +224,7 @@ def score_layered_model(config_filename, dataset_dir, num_images, labels_reduce=
     ds = DecisionTreeDatasetConfig(dataset_dir, num_images=num_images, imgs_name='test')
     n, h, w = ds.images_shape()
     layered = LayeredDecisionForest.load(config_filename, (h, w), labels_reduce)
+    layered.min_conf = min_conf
     hl, wl = layered.labels_dims
     depth = DeviceArray((n, h, w), np.uint16)
     ds.get_depth_block_cu(0, depth)

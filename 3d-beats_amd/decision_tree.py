@@ -248,6 +248,8 @@ class LayeredDecisionForest:
         self.eval = DecisionTreeEvaluator()
         self.fused = fused          # run() through rdf_layered_run (one call) or step by step like the reference
         self._fused_args = None
+        self._min_conf = None       # per-layer confidence thresholds (the `min_conf` property); None: plain argmax labels
+        self.conf_images = None     # with min_conf set: one GpuBuffer of labels_dims a layer, the layer's confidences
 
         self.depth_dims = tuple(depth_dims)  # y,x !!
         self.labels_reduce = labels_reduce
@@ -297,6 +299,28 @@ class LayeredDecisionForest:
         self.label_colors = GpuBuffer(label_colors.shape, dtype=np.uint8)
         self.label_colors.cu().set(label_colors)
 
+    @property
+    def min_conf(self):
+        """None (the default: every launch is the one made without this attribute, nothing is allocated), or one integer
+        0..65535 per layer.  When set, run() and run_hand() take the step-by-step path with each layer evaluated by
+        DecisionTreeEvaluator.get_posteriors_forest: a pixel whose confidence (rule Q4 of include/rdf_labels.h) is below the
+        layer's threshold stays 65535 in that layer's label image, so it fails a later layer's filter, stays 65535 in the
+        composite and is ignored by mean shift; the layer's confidences land in `conf_images[i]` (allocated here, once).
+        Not in the reference."""
+        return self._min_conf
+
+    @min_conf.setter
+    def min_conf(self, value):
+        if value is None:
+            self._min_conf = None
+            return
+        value = tuple(int(v) for v in value)
+        assert len(value) == self.num_models, f"min_conf: one threshold per layer ({self.num_models}), not {len(value)}"
+        assert all(0 <= v <= 65535 for v in value), f"min_conf: 0..65535, not {value}"
+        if self.conf_images is None:
+            self.conf_images = [GpuBuffer(self.labels_dims, dtype=np.uint16) for _ in range(self.num_models)]
+        self._min_conf = value
+
     def sibling(self):
         """A second stack over the SAME forests (device tables and packed tables are shared), conditions and colours, with
         its own per-layer label buffers, pointer table and evaluator.  run() writes `label_images` and the evaluator's
@@ -312,23 +336,34 @@ class LayeredDecisionForest:
         cfg = {'layers': layers, 'conditions': self._cfg_host['conditions'], 'label_colors': self._cfg_host['label_colors']}
         other = LayeredDecisionForest(cfg, self.depth_dims, self.labels_reduce, fused=self.fused)
         other.eval.use_packed = self.eval.use_packed
+        other.min_conf = self._min_conf
         return other
 
     def run(self, depth_image, labels_image, scale_factor=1.):
         """Per-frame entry of the live apps (run_live_layered.py:126, 3d_bz.py:389-437): every label buffer ends
         up 65535 where nothing was classified, layer i holds forest i's labels, labels_image the composite."""
-        if self.fused:
+        if self.fused and self._min_conf is None:
             return self._run_fused(depth_image, labels_image, scale_factor)
 
         labels_image.cu().fill(MAX_UINT16)
         for buf in self.label_images:
             buf.cu().fill(MAX_UINT16)
+        if self._min_conf is not None:
+            for buf in self.conf_images:
+                buf.cu().fill(0)
 
         # one image per call: add the leading image axis
         depth_3d = depth_image.cu().reshape((1,) + self.depth_dims)
         label_shape = (1,) + self.labels_dims
-        for (forest, filter_model, filter_model_class), out_buf in zip(self.m, self.label_images):
+        for i, ((forest, filter_model, filter_model_class), out_buf) in enumerate(zip(self.m, self.label_images)):
             filt = self.label_images[filter_model].cu().reshape(label_shape) if filter_model is not None else None
+            if self._min_conf is not None:      # the gated path: the posterior call in place of the argmax one
+                self.eval.get_posteriors_forest(forest, depth_3d, out_buf.cu().reshape(label_shape),
+                                                self.conf_images[i].cu().reshape(label_shape), None,
+                                                labels_reduce=self.labels_reduce, filter_images=filt,
+                                                filter_images_class=filter_model_class, scale_factor=scale_factor,
+                                                min_conf=self._min_conf[i])
+                continue
             self.eval.get_labels_forest(forest, depth_3d, out_buf.cu().reshape(label_shape),
                                         labels_reduce=self.labels_reduce, filter_images=filt,
                                         filter_images_class=filter_model_class, scale_factor=scale_factor)
@@ -342,7 +377,7 @@ class LayeredDecisionForest:
         (RGBA bytes, labels_dims + (4,)) receives label_colors[label - 1] wherever a label in 1..num_layered_classes is
         written, as make_rgba_from_labels would.  The per-layer label images stay unflipped.  Stacks that cannot take the
         fused call (a layer filtering on a later layer) run the reference sequence followed by the separate kernels."""
-        if self.fused:
+        if self.fused and self._min_conf is None:
             return self._run_fused(depth_image, labels_image, scale_factor, bool(flip_x), color_image)
         if getattr(self, "_hand_scratch", None) is None:   # once: nothing is allocated per call (or inside a graph capture)
             from .cuda.points_ops import PointsOps
@@ -366,9 +401,10 @@ class LayeredDecisionForest:
         `batch_label_images` (one [capacity, lh, lw] array a layer, the first n frames of each), NOT in `label_images`,
         which stay the single-frame path's.  Those buffers and their device pointer table are allocated once, for the
         largest n seen, before anything is enqueued: call it once with the largest batch before capturing a stream.
-        Stacks that cannot take the fused call raise ValueError."""
+        Stacks that cannot take the fused call raise ValueError.  With `min_conf` set the frames go through run_hand() one by
+        one (the gated path is not batched): the same composites, colours and `batch_label_images`."""
         import ctypes
-        if not self.fused:
+        if not self.fused and self._min_conf is None:
             raise ValueError("run_hand_batch needs a stack that takes the fused call (no layer filtering on a later layer)")
         depth_images = depth_images.cu() if hasattr(depth_images, "cu") else depth_images
         labels_images = labels_images.cu() if hasattr(labels_images, "cu") else labels_images
@@ -385,6 +421,13 @@ class LayeredDecisionForest:
             self._batch_ptrs_cu[:nl].set(np.array([b.ptr for b in self.batch_label_images], dtype=np.int64))
             self._batch_layer_labels = (ctypes.c_void_p * nl)(*[b.ptr for b in self.batch_label_images])
             self._batch_capacity = n
+        if self._min_conf is not None:      # gated: run_hand frame by frame, the same result (batching it is not built)
+            for k in range(n):
+                self.run_hand(_Cu(depth_images[k]), _Cu(labels_images[k]), scale_factor, flip_x,
+                              _Cu(color_images[k]) if color_images is not None else None)
+                for b, single in zip(self.batch_label_images, self.label_images):
+                    b[k].copy_from(single.cu())
+            return
         fa = self._fused_tables()
         packed = None
         if self.eval.use_packed:
@@ -547,6 +590,43 @@ class DecisionTreeEvaluator:
         _touch(labels_out)
 
     evaluate = get_labels_forest  # the name BASELINE.json's north_star uses; not in the reference
+
+    # -- forest posteriors: rdf_labels_forest_posterior of librdf_labels.so ----------------------
+    def get_posteriors_forest(self, forest, depth_images_in, labels_out=None, conf_out=None, sums_out=None, labels_reduce=1,
+                              filter_images=None, filter_images_class=None, scale_factor=1., min_conf=0):
+        """What get_labels_forest sums and discards (rules Q of include/rdf_labels.h), on the current stream: per evaluated
+        pixel the label into labels_out, the winning class's share of the vote as a 16-bit confidence into conf_out (both
+        uint16 [N, H // r, W // r]) and the class sums into sums_out (float32 [N, C, H // r, W // r]); any of the three may be
+        None, not all.  A pixel whose confidence is below min_conf (0..65535) keeps labels_out's bytes: with 0 the label map
+        is get_labels_forest's, byte for byte.  Skipped pixels are written nowhere: callers pre-fill.  Walks the
+        reference-layout forest (up to 16 classes); not in the reference.  Returns nothing."""
+        num_images, dim_y, dim_x = depth_images_in.shape
+        lshape = (num_images, dim_y // labels_reduce, dim_x // labels_reduce)
+        assert labels_out is not None or conf_out is not None or sums_out is not None, "at least one output"
+        for out in (labels_out, conf_out):
+            assert out is None or tuple(out.shape) == lshape
+        C = int(forest.num_classes)
+        if sums_out is not None:
+            assert tuple(sums_out.shape) == (lshape[0], C) + lshape[1:] and np.dtype(sums_out.dtype) == np.float32
+        if filter_images is not None:
+            assert filter_images_class is not None
+            assert tuple(filter_images.shape) == lshape
+        lb, st = _lib.load("labels"), self._rt.stream()
+        filter_class = int(filter_images_class) if filter_images is not None else -1
+        lpix = lshape[1] * lshape[2]
+        for i0, n in _image_chunks(num_images, dim_y * dim_x):
+            rc = lb.rdf_labels_forest_posterior(
+                _at(depth_images_in, i0, dim_y * dim_x * 2), n, dim_x, dim_y, device_ptr(forest.forest_cu),
+                int(forest.num_trees), int(forest.max_depth), C,
+                _at(filter_images, i0, lpix * 2) if filter_images is not None else None, filter_class, int(labels_reduce),
+                float(scale_factor), int(min_conf),
+                _at(labels_out, i0, lpix * 2) if labels_out is not None else None,
+                _at(conf_out, i0, lpix * 2) if conf_out is not None else None,
+                _at(sums_out, i0, C * lpix * 4) if sums_out is not None else None, st)
+            _lib.check(lb, rc, "rdf_labels_forest_posterior")
+        for out in (labels_out, conf_out, sums_out):
+            if out is not None:
+                _touch(out)
 
     # forests from this size on (hot records) may or may not be served better by the deep blocks: see DecisionForest.tune
     AUTO_TUNE_HOT_BYTES = 32 << 20
@@ -851,3 +931,13 @@ def _at(arr, first_image, bytes_per_image):
 def _touch(arr):
     if isinstance(arr, DeviceArray):
         arr.mark_dirty()
+
+
+class _Cu:
+    """A DeviceArray where run() and run_hand() take a GpuBuffer: `.cu()` is all they ask of it."""
+
+    def __init__(self, arr):
+        self._arr = arr
+
+    def cu(self):
+        return self._arr

@@ -188,7 +188,9 @@ class HandPipeline:
         address, and its cache key) with what they were at capture, and raises RuntimeError BEFORE anything is enqueued
         when one differs -- after
         `LeafRefitter.apply`, a `forest_cu.set(...)` or a re-pack: capture again.  (A bare `replay.graph.replay()` is
-        not covered.)"""
+        not covered.)  A stack with `min_conf` set (the gated, step-by-step path) is not captured: NotImplementedError."""
+        if getattr(self.layered_rdf, "min_conf", None) is not None:
+            raise NotImplementedError("HandPipeline.capture: the stack has min_conf set; capture of the gated path is not built")
         import torch
         scale = self.EVAL_TO_TRAIN_DIM_RATIO
         side = torch.cuda.Stream()

@@ -153,3 +153,110 @@ class LabelScorer:
         """Read the counts back (synchronises) as a Score."""
         per_image = self.per_image_cu.get() if self.per_image_cu is not None else None
         return Score.from_counts(self.counts_cu.get(), self.num_classes, per_image)
+
+
+class Calibration:
+    """Plain host object: what a forest's confidence (rule Q4 of include/rdf_labels.h) is worth.  Bin b of `bins` holds the
+    classified labelled pixels whose 16-bit confidence k has (k * bins) >> 16 == b.  count_by_bin, correct_by_bin (lists),
+    labelled and unclassified are exact Python integers; every ratio below is one float64 division."""
+
+    def __init__(self, count_by_bin, correct_by_bin, labelled, unclassified):
+        self.count_by_bin = [int(v) for v in count_by_bin]
+        self.correct_by_bin = [int(v) for v in correct_by_bin]
+        self.bins = len(self.count_by_bin)
+        assert self.bins >= 1 and len(self.correct_by_bin) == self.bins
+        self.labelled, self.unclassified = int(labelled), int(unclassified)
+
+    @staticmethod
+    def from_counts(counts, bins):
+        """counts: the uint64 block rdf_labels_confidence_counts fills: per bin {wrong, correct}, then unclassified, labelled."""
+        bins = int(bins)
+        counts = [int(v) for v in np.asarray(counts, np.uint64).reshape(-1)]
+        assert len(counts) == 2 * bins + 2, (bins, len(counts))
+        wrong, correct = counts[0:2 * bins:2], counts[1:2 * bins:2]
+        return Calibration([w + c for w, c in zip(wrong, correct)], correct, counts[2 * bins + 1], counts[2 * bins])
+
+    @property
+    def classified(self):
+        return sum(self.count_by_bin)
+
+    @property
+    def accuracy_by_bin(self):
+        """float64 [bins]: correct / count, NaN for an empty bin."""
+        return np.array([c / n if n else np.nan for c, n in zip(self.correct_by_bin, self.count_by_bin)], np.float64)
+
+    @property
+    def ece(self):
+        """Expected calibration error: sum over the non-empty bins of n_b / N * |acc_b - (b + 1/2) / bins|, N the classified
+        labelled pixels; NaN when there are none.  Over the common denominator 2 * bins * N the sum is one of integers,
+        sum |2 * bins * c_b - n_b * (2 b + 1)|, so it is exact up to the one division."""
+        N = self.classified
+        if N == 0:
+            return float("nan")
+        num = sum(abs(2 * self.bins * c - n * (2 * b + 1)) for b, (c, n) in enumerate(zip(self.correct_by_bin, self.count_by_bin)))
+        return num / (2 * self.bins * N)
+
+    def coverage_curve(self):
+        """(min_conf int64 [bins], coverage float64 [bins], accuracy float64 [bins]): min_conf[b] = ceil(b * 65536 / bins) is
+        the smallest confidence of bin b; gating at it keeps the pixels of the bins >= b, `coverage` is their share of
+        `labelled` and `accuracy` the share of them that is correct (NaN where nothing is kept or labelled)."""
+        B = self.bins
+        min_conf = np.array([-((-b * 65536) // B) for b in range(B)], np.int64)
+        kept, right = [0] * B, [0] * B
+        n = c = 0
+        for b in range(B - 1, -1, -1):
+            n, c = n + self.count_by_bin[b], c + self.correct_by_bin[b]
+            kept[b], right[b] = n, c
+        coverage = np.array([k / self.labelled if self.labelled else np.nan for k in kept], np.float64)
+        accuracy = np.array([r / k if k else np.nan for r, k in zip(right, kept)], np.float64)
+        return min_conf, coverage, accuracy
+
+    def min_conf_for(self, accuracy):
+        """The smallest threshold of coverage_curve() whose kept pixels reach `accuracy`, or None when none does."""
+        min_conf, _, acc = self.coverage_curve()
+        for m, a in zip(min_conf, acc):
+            if a >= accuracy:           # (False for NaN)
+                return int(m)
+        return None
+
+    def __repr__(self):
+        return (f"Calibration(bins={self.bins}, labelled={self.labelled}, unclassified={self.unclassified}, ece={self.ece:.4f})")
+
+
+class ConfidenceScorer:
+    def __init__(self, bins=64):
+        """bins: 1..1024 equal ranges of the 16-bit confidence."""
+        self.bins = int(bins)
+        assert 1 <= self.bins <= 1024, bins
+        self._rt = get_runtime()
+        self._lb = _lib.load("labels")
+        self.counts_cu = DeviceArray((2 * self.bins + 2,), np.uint64)
+        self.reset()
+
+    def reset(self):
+        """Zero the counts (stream-ordered)."""
+        self.counts_cu.fill(np.uint64(0))
+        return self
+
+    def add(self, pred, conf, truth, labels_reduce=1):
+        """Enqueue the counts of pred and conf uint16 [N, H // r, W // r] (what get_posteriors_forest wrote) against truth
+        uint16 [N, H, W] on the current stream, adding onto what is there; nothing is read back."""
+        r = int(labels_reduce)
+        assert r >= 1
+        pred, (n, hl, wl) = _maps(pred, "pred")
+        conf, cshape = _maps(conf, "conf")
+        truth, (nt, h, w) = _maps(truth, "truth")
+        assert cshape == (n, hl, wl), f"conf {cshape} against pred {(n, hl, wl)}"
+        assert nt == n and (hl, wl) == (h // r, w // r), f"pred {(n, hl, wl)} against truth {(nt, h, w)} at labels_reduce {r}"
+        from .decision_tree import _image_chunks
+        p0, c0, t0, st = device_ptr(pred), device_ptr(conf), device_ptr(truth), self._rt.stream()
+        for i0, cnt in _image_chunks(n, h * w):
+            rc = self._lb.rdf_labels_confidence_counts(cnt, w, h, r, self.bins, p0 + i0 * hl * wl * 2, c0 + i0 * hl * wl * 2,
+                                                       t0 + i0 * h * w * 2, self.counts_cu.ptr, st)
+            _lib.check(self._lb, rc, "rdf_labels_confidence_counts")
+        self.counts_cu.mark_dirty()
+        return self
+
+    def result(self):
+        """Read the counts back (synchronises) as a Calibration."""
+        return Calibration.from_counts(self.counts_cu.get(), self.bins)

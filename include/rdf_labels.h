@@ -16,6 +16,8 @@
  * pattern, a census transform and a block matcher, integer like the colour kernels.
  * And the leaf refit (rdf_labels_refit_count, rdf_labels_refit_apply): a trained forest's leaf distributions re-estimated
  * from labelled frames, in integer counts.
+ * And what the forest knows beyond its argmax (rdf_labels_forest_posterior, rdf_labels_confidence_counts): per-pixel class
+ * sums, a confidence, a reject option and a reliability histogram.
  *
  * It is a library of its own, next to librdf_hip.so and librdf_frontend.so, with its own ABI number and build id.
  * Conventions are those of rdf_hip.h: every pointer is caller-owned DEVICE memory; nothing is allocated, freed or
@@ -50,7 +52,7 @@ extern "C" {
 /*
  * 1: first version.  The number changes when something declared here is removed or re-typed; a pure addition (as
  * rdf_points_center, rdf_rerender, rdf_hand_scene_render and the pose fit -- rdf_pose_cost, rdf_pose_propose, rdf_pose_select,
- * rdf_pose_fit_workspace_bytes and rdf_pose_fit --, the stereo sensor's three and the leaf refit's three were) keeps it, since every caller of the older entry points still links and runs.
+ * rdf_pose_fit_workspace_bytes and rdf_pose_fit --, the stereo sensor's three, the leaf refit's three and the forest posterior's two were) keeps it, since every caller of the older entry points still links and runs.
  * Two builds with the same number are told apart by rdf_labels_build_id().
  */
 #define RDF_LABELS_ABI_VERSION 1
@@ -536,6 +538,61 @@ int rdf_labels_refit_count(const uint16_t *depth, const uint16_t *labels, int n_
 size_t rdf_labels_refit_workspace_bytes(int n_trees, int max_depth, int n_classes);
 int rdf_labels_refit_apply(float *forest, int n_trees, int max_depth, int n_classes, const uint64_t *counts, uint64_t min_count,
                            int fallback, void *workspace, uint64_t *report, void *stream);
+
+/*
+ * Forest posteriors: what rdf_eval_forest sums per pixel and discards.  rdf_labels_forest_posterior evaluates a forest as
+ * rdf_eval_forest does and writes, per evaluated pixel, the label, a 16-bit confidence (the winning class's share of the
+ * summed leaf distributions) and, on request, the sums themselves; a pixel whose confidence is below min_conf is left out of
+ * the label map (a reject option).  rdf_labels_confidence_counts bins (prediction, confidence, truth) into a reliability
+ * histogram.  The reference has no counterpart; the rules below are this library's own, tests/posterior_numpy.py restates
+ * them, and the kernels match that bit for bit: the sums are made in a stated order and the counts are integers.
+ *
+ *   forest  float32 [T][N][E], the reference layout of the leaf refit above.  1 <= T, 1 <= D <= 30, 1 <= C <=
+ *           RDF_POSTERIOR_MAX_CLASSES.
+ *   depth   uint16 [n_img][dim_y][dim_x].  With r = labels_reduce >= 1, Hl = dim_y / r, Wl = dim_x / r:
+ *   filter, labels_out, conf_out  uint16 [n_img][Hl][Wl];  sums_out float32 [n_img][C][Hl][Wl], planar.
+ *           Each of the three outputs may be NULL, not all of them.
+ *
+ * Q1. Pixels, as rdf_eval_forest chooses them.  Label pixel (x, y) of image i reads depth pixel (x * r, y * r).  If filter_class
+ *     != -1 and filter[i][y][x] != filter_class the pixel is skipped; if its depth d is 0 or 65535 it is skipped.  A skipped
+ *     pixel is written in none of the three outputs: callers pre-fill, as with rdf_eval_forest.
+ * Q2. Walk and sums.  For t = 0 .. T-1 the pixel walks tree t exactly as rule R2 describes: one multiply and one IEEE divide
+ *     per offset, floor with saturation and NaN -> 0, a wrapping add, a per-axis out-of-range probe reads 65535.0, f < thresh
+ *     goes left and anything else right, and the leaf-slot test floor(rec[5 + s]) != -1 is made at every level.  At a leaf
+ *     slot acc[c] = acc[c] + rec[7 + s * C + c] for every c: one fp32 add each, rounded to nearest, no contraction; acc starts
+ *     at +0.0f and the trees are taken in index order.  A walk that is told to go on at level D - 1 adds nothing.
+ * Q3. Label.  best = 0.f, label = 0; for c ascending, acc[c] > best replaces both.  The inference argmax: ties go to the
+ *     lowest class, an all <= 0 or NaN vote gives 0, NaN never wins.
+ * Q4. Confidence.  S = (..((0.f + acc[0]) + acc[1]) + ..) in fp32, in class order.  If !(S > 0.f), conf = 0; else q = best / S
+ *     (one IEEE divide), v = floor(q * 65535.0f) with rule R2's floor (saturating, NaN -> 0), conf = min(max(v, 0), 65535).
+ *     A one-hot vote gives 65535, a two-way tie of equal halves 32767.
+ * Q5. Outputs, for every evaluated pixel: conf_out = conf; sums_out[i][c][y][x] = acc[c] for all c < C; labels_out = label iff
+ *     conf >= min_conf, else labels_out keeps the caller's bytes.  With min_conf == 0 the label map is byte for byte what
+ *     rdf_eval_forest writes for the same arguments.
+ * Q6. Arguments.  T < 1, D outside 1..30, C < 1, r < 1, a negative dimension, filter_class outside -1..65535, min_conf outside
+ *     0..65535 or a misaligned pointer (2 bytes for the maps, 4 for forest and sums_out) is RDF_ERR_BAD_ARG; C >
+ *     RDF_POSTERIOR_MAX_CLASSES or n_img * dim_y * dim_x >= 2^31 (callers split the batch by images) RDF_ERR_TOO_LARGE; zero
+ *     label pixels is a successful no-op; else a NULL depth or forest, all three outputs NULL, or a NULL filter with
+ *     filter_class != -1 is RDF_ERR_NULL_PTR.  A rejected call launches nothing and writes nothing.  An accepted call makes
+ *     one launch, is stream-ordered and reads nothing back: one lane per label pixel, a wave leaves at once when none of
+ *     its 64 pixels is evaluated, the sums stay in registers, no LDS, no atomics.
+ * Q7. Confidence counts (rdf_labels_confidence_counts).  pred, conf uint16 [n_img][Hl][Wl]; truth uint16 [n_img][dim_y][dim_x],
+ *     sampled at (x * r, y * r) as rdf_score_labels samples it.  counts uint64 [2 * bins + 2], 8-byte aligned: the call ADDS,
+ *     the caller zeroes.  Per label pixel, with the raw values p, k (the confidence) and t:  t == 0: ignored.  Else
+ *     counts[2 * bins + 1] += 1 (labelled pixels); if p == 65535, counts[2 * bins + 0] += 1 (labelled, not classified); else,
+ *     with b = (k * bins) >> 16, counts[2 * b + (p == t)] += 1.  bins outside 1..1024 is RDF_ERR_BAD_ARG; the other error rules
+ *     are rdf_score_labels': r < 1, a negative dimension or a misaligned pointer RDF_ERR_BAD_ARG, zero label pixels a successful
+ *     no-op, else a NULL pointer RDF_ERR_NULL_PTR and n_img * dim_y * dim_x >= 2^31 RDF_ERR_TOO_LARGE.  One launch; 32-bit LDS
+ *     histograms, each workgroup adds its non-zero cells once with 64-bit integer atomics: the result does not depend on the
+ *     order of arrival.
+ */
+#define RDF_POSTERIOR_MAX_CLASSES 16
+int rdf_labels_forest_posterior(const uint16_t *depth, int n_img, int dim_x, int dim_y, const float *forest, int n_trees,
+                                int max_depth, int n_classes, const uint16_t *filter, int filter_class, int labels_reduce,
+                                float scale_factor, int min_conf, uint16_t *labels_out, uint16_t *conf_out, float *sums_out,
+                                void *stream);
+int rdf_labels_confidence_counts(int n_img, int dim_x, int dim_y, int labels_reduce, int bins, const uint16_t *pred,
+                                 const uint16_t *conf, const uint16_t *truth, uint64_t *counts, void *stream);
 
 int rdf_labels_abi_version(void);
 const char *rdf_labels_build_id(void);
