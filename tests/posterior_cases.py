@@ -1,6 +1,7 @@
 """The cases of tests/test_posterior.py, built from seeds: the case worked by hand, the parity cases (the smallest shapes at
-which the posterior kernel can go wrong: widths on both sides of a wave, one to five rows, every class-capacity bound), a
-hand-made forest of awkward PDFs, and the two-layer stack of the layered tests."""
+which the posterior kernel can go wrong: widths on both sides of a wave, one to five rows, every class-capacity bound, a
+depth-12 forest whose leaves begin at level 9), a hand-made forest of awkward PDFs, the two-layer stack of the layered tests with
+the thresholds at which its gates reject, and the maps of the confidence counts' striding launches."""
 import importlib
 
 import numpy as np
@@ -66,6 +67,50 @@ def trained_like(T, D, C, first):
     return forest
 
 
+def deep_forest(T, D, C, first):
+    """trained_like's offsets and thresholds on trees whose leaves begin at level 9: every walk goes nine levels down at least,
+    through the levels at which the node index (1 << j) - 1 + g and the record offset n * E grow."""
+    s = _synth()
+    forest = np.stack([s.trained_like_tree(first + k, D, C, 0.3, min(9, D - 1)) for k in range(T)])
+    forest[:, :, 0:4:2] *= 20.
+    forest[:, :, 1:4:2] /= 50.
+    forest[:, :, 4] /= 20.
+    return forest
+
+
+def walk_ends(depth, forest, labels_reduce=1, scale=1.):
+    """[(image, y, x, tree, node, side)] of every walk of the evaluated label pixels (no filter); node and side are None for
+    a walk that falls off level D - 1."""
+    import refit_numpy as rn
+    T, D, _ = rn.dims(forest)
+    r = int(labels_reduce)
+    out = []
+    for i in range(depth.shape[0]):
+        for y in range(0, (depth.shape[1] // r) * r, r):
+            for x in range(0, (depth.shape[2] // r) * r, r):
+                if depth[i, y, x] in (0, NO_PIXEL):
+                    continue
+                for t in range(T):
+                    at = rn.walk(depth[i], forest[t], D, x, y, scale)
+                    out.append((i, y, x, t) + (at if at is not None else (None, None)))
+    return out
+
+
+def level_of(node):
+    return int(node + 1).bit_length() - 1
+
+
+def plant_fall_off(depth, forest, labels_reduce=1, scale=1.):
+    """The first walk (in walk_ends' order) that ends in a leaf slot of level D - 1 is told to go on there: it falls off the
+    tree at depth.  Changes `forest` in place; returns (image, y, x, tree, node, side) of the plant."""
+    D = level_of(forest.shape[1])
+    for i, y, x, t, n, s in walk_ends(depth, forest, labels_reduce, scale):
+        if n is not None and level_of(n) == D - 1:
+            forest[t, n, 5 + s] = -1.
+            return i, y, x, t, n, s
+    raise AssertionError("no walk ends on the last level")
+
+
 def sharp_forest(T, D, C, first, hot_share=0.4):
     """trained_like with the leaf PDFs a well-trained tree has: cubed and normalised again, and four leaf slots in ten one-hot
     (the trainer's rule above 0.999 purity), so that confidences reach from below a half up to 65535."""
@@ -115,6 +160,8 @@ PARITY = {
     "single_r2": (1, 4, 130, 2, 1.0, 1, 1, 16, None, 0, "trained", "single"),
     "row_d1":    (3, 1, 64, 1, 0.5, 5, 1, 8, None, NO_PIXEL, "trained", "live"),
     "sharp":     (1, 5, 65, 1, 1.0, 2, 6, 5, None, NO_PIXEL, "sharp", "live"),
+    # (sorted last: the seeds of the cases above are their places in the sorted list)
+    "walk_d12":  (1, 5, 130, 1, 1.0, 2, 12, 5, None, NO_PIXEL, "deep", "live500"),
 }
 
 
@@ -122,10 +169,12 @@ def parity_case(name):
     """(depth, forest, kwargs of posterior_numpy.posterior / get_posteriors_forest, pre-fill)."""
     n, h, w, r, scale, T, D, C, fclass, prefill, fkind, dkind = PARITY[name]
     seed = sorted(PARITY).index(name)
-    depth = live_rows(100 + 10 * seed, n, h, w) if dkind == "live" else single_pixel(n, h, w, (h - 1 - (h - 1) % r, (w - 1) - (w - 1) % r))
+    depth = live_rows(500, n, h, w) if dkind == "live500" else live_rows(100 + 10 * seed, n, h, w) if dkind == "live" else single_pixel(n, h, w, (h - 1 - (h - 1) % r, (w - 1) - (w - 1) % r))
     forest = {"awkward": awkward_forest, "sharp": lambda: sharp_forest(T, D, C, 30 + 5 * seed),
-              "trained": lambda: trained_like(T, D, C, 30 + 5 * seed)}[fkind]()
+              "trained": lambda: trained_like(T, D, C, 30 + 5 * seed), "deep": lambda: deep_forest(T, D, C, 30 + 5 * seed)}[fkind]()
     assert forest.shape == (T, (1 << D) - 1, 7 + 2 * C)
+    if fkind == "deep":
+        plant_fall_off(depth, forest, r, scale)
     filt = None if fclass is None else filter_image(seed, (n, h // r, w // r), fclass)
     return depth, forest, dict(labels_reduce=r, scale=scale, filter_images=filt, filter_class=fclass), prefill
 
@@ -144,3 +193,68 @@ def layered_case():
     colors = [[10 * i, 255 - 10 * i, i, 255] for i in range(1, 8)]
     frames = np.stack([_synth().live_frame(300 + i, 48, LAYERED["W"])[12:12 + LAYERED["H"]] for i in range(2)])
     return f0, f1, conditions, colors, frames
+
+
+# thresholds at which both gates of layered_case() reject and layer 0's gate changes what layer 1 evaluates (the conditions are
+# asserted by test_posterior.test_the_gated_stack_case_meets_its_conditions)
+LAYERED_GATE = (50000, 30000)
+LAYERED_FILTER_CLASS = 3
+
+
+def stack_answer(pn, oracle, case, frame, thresholds=None, scale=0.75, prefill_colors=0):
+    """What a LayeredDecisionForest over layered_case()'s forests leaves for one frame, from the restatement `pn` gated per
+    layer (thresholds None: no gate) and the oracle's composite: a dict of `labels` and `conf` (one [Hl, Wl] map a layer,
+    confidence 0 where nothing was evaluated), `evaluated` (bool, a layer), `composite`, `hand` (the composite mirrored in x) and
+    `colors` / `hand_colors` (RGBA of the composite / the mirrored one over `prefill_colors` bytes)."""
+    f0, f1, conditions, colors, _ = case
+    R = LAYERED["R"]
+    t0, t1 = (0, 0) if thresholds is None else thresholds
+    d3 = np.ascontiguousarray(frame)[None]
+    l0, c0, _ = pn.posterior(d3, f0, R, scale, min_conf=t0)
+    l1, c1, _ = pn.posterior(d3, f1, R, scale, filter_images=l0, filter_class=LAYERED_FILTER_CLASS, min_conf=t1)
+    ev0, ev1 = pn.evaluated_mask(d3, R), pn.evaluated_mask(d3, R, l0, LAYERED_FILTER_CLASS)
+    comp = np.full(l0.shape[1:], NO_PIXEL, np.uint16)
+    assert oracle.composite([l0[0], l1[0]], conditions, comp) == 0
+    hand = np.ascontiguousarray(comp[:, ::-1])
+
+    def rgba(labels):
+        out = np.full(labels.shape + (4,), prefill_colors, np.uint8)
+        known = (labels >= 1) & (labels <= len(colors))
+        out[known] = np.array(colors, np.uint8)[labels[known].astype(np.int64) - 1]
+        return out
+    return dict(labels=[l0[0], l1[0]], conf=[np.where(ev0[0], c0[0], 0).astype(np.uint16), np.where(ev1[0], c1[0], 0).astype(np.uint16)],
+                evaluated=[ev0[0], ev1[0]], composite=comp, hand=hand, colors=rgba(comp), hand_colors=rgba(hand))
+
+
+# ------------------------------------------------------------ the confidence counts' striding launches --------------------------
+COUNTS_GRID_PIXELS = 512 * 256      # kCountBlocks workgroups of kThreads lanes: what one trip of k_confidence_counts covers
+COUNTS_STRIDE = {
+    "one_image":  dict(truth_shape=(1, 257, 511), r=1),        # 131327 label pixels: workgroup 0 alone makes a second trip
+    "two_images": dict(truth_shape=(2, 258, 1022), r=2),       # [2, 129, 511] maps, 131838: a wave of the second trip spans the images
+}
+
+
+def counts_stride_maps(name, C=8):
+    """(pred, conf, truth, r) with more label pixels than one trip of the counts kernel covers: pred 20 % 65535, truth 70 % zero (and
+    never zero at the planted pixels), confidence 0 and 65535 planted at the first pixel, the last pixel and pixel 131072, and
+    the two aligned waves from label pixel 131072 + 64 on without any truth."""
+    n, h, w = COUNTS_STRIDE[name]["truth_shape"]
+    r = COUNTS_STRIDE[name]["r"]
+    hl, wl = h // r, w // r
+    n_lpx = n * hl * wl
+    rng = np.random.default_rng(n_lpx)
+    pred = rng.integers(0, C, n_lpx).astype(np.uint16)
+    pred[rng.random(n_lpx) < 0.2] = NO_PIXEL
+    conf = rng.integers(0, 65536, n_lpx).astype(np.uint16)
+    at = rng.integers(1, C, n_lpx).astype(np.uint16)              # the truth under each label pixel
+    at[rng.random(n_lpx) < 0.7] = 0
+    right = (rng.random(n_lpx) < 0.5) & (at > 0) & (pred != NO_PIXEL)
+    pred[right] = at[right]
+    planted = np.array([0, 1, COUNTS_GRID_PIXELS - 1, COUNTS_GRID_PIXELS, COUNTS_GRID_PIXELS + 1, n_lpx - 2, n_lpx - 1])
+    conf[planted] = [0, 65535, 65535, 65535, 0, 0, 65535]
+    at[planted] = [1, 2, 3, 1, 2, 3, 1]
+    pred[planted] = [1, 2, 1, 1, 3, 3, 2]
+    at[COUNTS_GRID_PIXELS + 64:COUNTS_GRID_PIXELS + 192] = 0
+    truth = rng.integers(1, C, (n, h, w)).astype(np.uint16)       # off the sampled coordinates: never zero, never to be read
+    truth[:, :hl * r:r, :wl * r:r] = at.reshape(n, hl, wl)
+    return pred.reshape(n, hl, wl), conf.reshape(n, hl, wl), truth, r

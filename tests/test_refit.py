@@ -526,3 +526,40 @@ def test_dataset_functions(rdf, gpu_runtime, tmp_path):
     report = ds_mod.refit_saved_model(str(tmp_path / "plain.npy"), str(rdir), 0, str(tmp_path / "anc.npy"), min_count=50, fallback="ancestor")
     want, want_report = rn.apply(plain, want_counts, 50, rn.ANCESTOR)
     assert np.array_equal(_bits(np.load(tmp_path / "anc.npy")), _bits(want)) and list(report.values()) == [int(v) for v in want_report]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["lds_histogram", "hash_table"])
+def test_counts_over_more_than_one_trip(kind, rdf, gpu_runtime):
+    """k_refit_count launches at most kMaxBlocks = 1024 workgroups of kThreads = 256 lanes: from 1024 * 256 = 262144 pixels on a
+    workgroup makes further trips, with its LDS histogram (T2/D4/C4: every level is in it) and its table of deep cells (a
+    column tree of depth 10, whose leaf slots lie on level 9, below the nine levels the histogram holds for T1/C4) carried
+    from trip to trip.  One frame of 513 x 512 is 512 pixels more: workgroups 0 and 1 make a second trip, over the last row."""
+    H, W, C = 513, 512, 4
+    n_px = H * W
+    assert n_px == 262656 > 1024 * 256 == 262144                            # kMaxBlocks * kThreads of forest_refit_hip.hip
+    rng = np.random.default_rng(77)
+    labelled = rng.random(n_px) < 0.02
+    labelled[[0, 262143, 262144, 262145, n_px - 1]] = True                  # the first pixel, both sides of the second trip's start, the last
+    labels = np.where(labelled, rng.integers(1, C, n_px), 0).astype(np.uint16).reshape(1, H, W)
+    if kind == "lds_histogram":
+        forest = rc.trained_like(2, 4, C, first=120)
+        forest[:, :, 0:4] *= 100.                                           # offsets of a few pixels at these depths
+        depth = rng.integers(400, 1201, n_px)                               # a reading under every label; around them background and holes
+        depth[~labelled & (rng.random(n_px) < 0.3)] = 65535
+        depth[~labelled & (rng.random(n_px) < 0.05)] = 0
+        depth = depth.astype(np.uint16).reshape(1, H, W)
+        assert 2 * 15 * 2 * C <= 4096
+    else:
+        forest = rc.column_tree(10, C, 1024)[None]                          # columns 0..511: the lower half of level 9's slots
+        depth = np.full((1, H, W), 1000, np.uint16)
+        assert 1 * 511 * 2 * C <= 4096 < 1 * 1023 * 2 * C                   # L = 9: level 9 is not in the histogram
+    assert 0.015 < labelled.mean() < 0.025 and labelled[262144:].sum() >= 5
+    r = _check_count(rdf, depth, labels, forest)
+    got = r.counts.get()
+    assert r.totals()["walked"] == int(labelled.sum()) and r.totals()["fell_off"] == 0
+    if kind == "lds_histogram":
+        assert (got.sum(axis=3) > 0).sum() >= 8                             # the walks end in many slots
+    if kind == "hash_table":                                                # every column's slot of level 9, nothing above it
+        per_slot = got[0].sum(axis=2)
+        assert not per_slot[:511].any() and (per_slot[511:511 + 256] > 0).all() and not per_slot[511 + 256:].any()

@@ -409,3 +409,68 @@ def test_score_layered_model_matches_the_oracle_composite(rdf, gpu_runtime, orac
     assert s.num_classes == C and np.array_equal(s.confusion, want[:-2].reshape(C + 1, C + 1))
     assert (s.equal, s.labelled) == (int(want[-2]), int(want[-1])) and np.array_equal(s.per_image, snp.score_per_image(comp, t, r))
     assert s.confusion[1:5, 1:5].sum() > 0 and s.num_pixels == n * (h // r) * (w // r)
+
+
+@pytest.mark.gpu
+def test_score_layered_model_with_gates_that_reject(rdf, gpu_runtime, oracle, tmp_path):
+    """score_layered_model(min_conf=...) over the layered stack of tests/posterior_cases.py at the thresholds at which both of
+    its gates reject (test_posterior.test_the_gated_stack_case_meets_its_conditions): the expected composite is the
+    restatement gated per layer, then the oracle's composite; without min_conf the ungated one, and another score."""
+    import posterior_cases as pc
+    import posterior_numpy as pn
+    ds_mod = _mod("dataset")
+    case = pc.layered_case()
+    f0, f1, conditions, colors, frames = case
+    H, W, r, scale = pc.LAYERED["H"], pc.LAYERED["W"], 2, 0.75
+    assert r == pc.LAYERED["R"]
+    depth = np.concatenate([frames, rdf.synth.live_frame(302, 48, W)[None, 12:12 + H]])
+    n = depth.shape[0]
+    rng = np.random.default_rng(21)
+    truth = rng.integers(1, 8, depth.shape).astype(np.uint16)
+    truth[depth == 65535] = 0
+    ds_mod.write_dataset(str(tmp_path / "data"), depth, truth, {k: [30 * k, 9, 200 - k, 255] for k in range(1, 8)})
+    np.save(tmp_path / "layer0.npy", f0)
+    np.save(tmp_path / "layer1.npy", f1)
+    cfg = {"layers": [{"model": "layer0.npy"}, {"model": "layer1.npy", "filter_model": 0, "filter_model_class": pc.LAYERED_FILTER_CLASS}],
+           "conditions": conditions, "label_colors": colors}
+    with open(tmp_path / "layered.json", "w") as fh:
+        fh.write(json.dumps(cfg))
+    np.random.seed(3)
+    order = list(range(n))
+    np.random.shuffle(order)                          # the images DecisionTreeDatasetConfig draws
+    assert sorted(order) == [0, 1, 2] and order != [0, 1, 2]
+    d, t = depth[order], truth[order]
+    C = 8
+    scores, wants = {}, {}
+    for min_conf in (pc.LAYERED_GATE, None):
+        np.random.seed(3)
+        s = ds_mod.score_layered_model(str(tmp_path / "layered.json"), str(tmp_path / "data"), n, r, scale, min_conf=min_conf)
+        comp = np.stack([pc.stack_answer(pn, oracle, case, d[i], min_conf, scale)["composite"] for i in range(n)])
+        want = snp.score_counts(comp, t, C, r)
+        assert s.num_classes == C and np.array_equal(s.confusion, want[:-2].reshape(C + 1, C + 1)), min_conf
+        assert (s.equal, s.labelled) == (int(want[-2]), int(want[-1])) and np.array_equal(s.per_image, snp.score_per_image(comp, t, r))
+        assert s.confusion[1:8, 1:8].sum() > 0 and s.num_pixels == n * (H // r) * (W // r)
+        scores[min_conf], wants[min_conf] = s, comp
+    gated, plain = scores[pc.LAYERED_GATE], scores[None]
+    assert not np.array_equal(gated.confusion, plain.confusion) and gated.confusion[1:8, C].sum() > plain.confusion[1:8, C].sum()
+    assert all(not np.array_equal(wants[None][i], wants[pc.LAYERED_GATE][i]) for i in range(n))      # in every image
+
+
+@pytest.mark.gpu
+def test_label_scorer_one_image_per_call(rdf, gpu_runtime, monkeypatch):
+    """LabelScorer.add splits a batch as the evaluator does and offsets both maps and the per-image sums (8 bytes an image) by
+    hand: decision_tree._PIX_LIMIT patched down to a frame and a half makes it one image per call."""
+    N, H, W, r, C = 3, 37, 53, 2, 7
+    pred, truth = _maps(N, H, W, r, C, 31)
+    per_image = snp.score_per_image(pred, truth, r)
+    assert len({tuple(row) for row in per_image.tolist()}) == N                           # three different images
+    whole = rdf.LabelScorer(C).add(rdf.to_device(pred), rdf.to_device(truth), r, per_image=True)
+    dt = _mod("decision_tree")
+    monkeypatch.setattr(dt, "_PIX_LIMIT", H * W * 3 // 2)
+    assert dt._image_chunks(N, H * W) == [(0, 1), (1, 1), (2, 1)]
+    s = _check(rdf, pred, truth, C, r, per_image=True)                                    # against score_numpy
+    assert np.array_equal(s.per_image, whole.result().per_image) and np.array_equal(s.confusion, whole.result().confusion)
+    chunked = rdf.LabelScorer(C).add(rdf.to_device(pred), rdf.to_device(truth), r, per_image=True)
+    assert chunked.counts_cu.get().tobytes() == whole.counts_cu.get().tobytes()
+    assert chunked.per_image_cu.get().tobytes() == whole.per_image_cu.get().tobytes()
+    _check(rdf, pred, truth, C, r, per_image=False)
