@@ -38,12 +38,14 @@ LIBRARIES = {lib.key: lib for lib in (
     # sensor that turns a left and a right render of those frames into what a camera would report, and the refit of a trained
     # forest's leaf distributions on such frames (its walk takes the reference-layout feature step -- the offset coordinate and
     # the bounds-checked read -- from rdf_device.hpp, the forest and training kernels' header), and the forest's posterior:
-    # the same walk ending in per-pixel class sums, a confidence and a gated label where inference ends in an argmax
+    # the same walk ending in per-pixel class sums, a confidence and a gated label where inference ends in an argmax, and the
+    # consumer of that confidence: composite weights of a layered stack and the weighted mean shift (soft modes)
     Library("labels", os.path.join(HERE, "csrc", "librdf_labels.so"),
             [os.path.join(HERE, "csrc", "labels_hip.hip"), os.path.join(HERE, "csrc", "rerender_hip.hip"),
              os.path.join(HERE, "csrc", "score_hip.hip"), os.path.join(HERE, "csrc", "hand_scene_hip.hip"),
              os.path.join(HERE, "csrc", "pose_fit_hip.hip"), os.path.join(HERE, "csrc", "stereo_sensor_hip.hip"),
-             os.path.join(HERE, "csrc", "forest_refit_hip.hip"), os.path.join(HERE, "csrc", "forest_posterior_hip.hip")],
+             os.path.join(HERE, "csrc", "forest_refit_hip.hip"), os.path.join(HERE, "csrc", "forest_posterior_hip.hip"),
+             os.path.join(HERE, "csrc", "soft_modes_hip.hip")],
             [os.path.join(HERE, "..", "include", "rdf_labels.h"), os.path.join(HERE, "csrc", "rdf_kernel_util.hpp"),
              os.path.join(HERE, "csrc", "rdf_raster.hpp"), os.path.join(HERE, "csrc", "rdf_device.hpp")], "rdf_labels_"),
 )}

@@ -230,6 +230,12 @@ BINDINGS = {
                                                  _c_int, _c_int, _c_float, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
         "rdf_labels_confidence_counts": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p,
                                                   _c_void_p, _c_void_p]),
+        "rdf_labels_composite_weights": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_int,
+                                                  _c_void_p, _c_void_p]),
+        "rdf_labels_weighted_modes": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_void_p,
+                                               _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float,
+                                               _c_float, _c_void_p, _c_void_p, _c_int, _c_void_p]),
+        "rdf_labels_weighted_modes_list_cap": (ctypes.c_uint32, []),
         "rdf_labels_abi_version": (_c_int, []),
         "rdf_labels_build_id": (ctypes.c_char_p, []),
         "rdf_labels_error_string": (ctypes.c_char_p, [_c_int]),

@@ -402,7 +402,8 @@ class LayeredDecisionForest:
         which stay the single-frame path's.  Those buffers and their device pointer table are allocated once, for the
         largest n seen, before anything is enqueued: call it once with the largest batch before capturing a stream.
         Stacks that cannot take the fused call raise ValueError.  With `min_conf` set the frames go through run_hand() one by
-        one (the gated path is not batched): the same composites, colours and `batch_label_images`."""
+        one (the gated path is not batched): the same composites, colours and `batch_label_images`, and each frame's
+        `conf_images` are copied into `batch_conf_images` the same way (what composite_weights_batch reads)."""
         import ctypes
         if not self.fused and self._min_conf is None:
             raise ValueError("run_hand_batch needs a stack that takes the fused call (no layer filtering on a later layer)")
@@ -422,10 +423,20 @@ class LayeredDecisionForest:
             self._batch_layer_labels = (ctypes.c_void_p * nl)(*[b.ptr for b in self.batch_label_images])
             self._batch_capacity = n
         if self._min_conf is not None:      # gated: run_hand frame by frame, the same result (batching it is not built)
+            cap = int(self.batch_label_images[0].shape[0])
+            if getattr(self, "batch_conf_images", None) is None or int(self.batch_conf_images[0].shape[0]) != cap:
+                # the layers' confidences of the batch, next to their labels (composite_weights_batch reads both); the device
+                # tables of both sets of addresses are made here, once per capacity
+                self.batch_conf_images = [DeviceArray((cap,) + tuple(self.labels_dims), np.uint16) for _ in range(nl)]
+                self._batch_weight_ptrs_cu = DeviceArray((2, max(nl, 1)), np.int64)
+                self._batch_weight_ptrs_cu.set(np.array([[b.ptr for b in self.batch_label_images],
+                                                         [b.ptr for b in self.batch_conf_images]], dtype=np.int64))
             for k in range(n):
                 self.run_hand(_Cu(depth_images[k]), _Cu(labels_images[k]), scale_factor, flip_x,
                               _Cu(color_images[k]) if color_images is not None else None)
                 for b, single in zip(self.batch_label_images, self.label_images):
+                    b[k].copy_from(single.cu())
+                for b, single in zip(self.batch_conf_images, self.conf_images):
                     b[k].copy_from(single.cu())
             return
         fa = self._fused_tables()
@@ -447,6 +458,43 @@ class LayeredDecisionForest:
         _touch(labels_images)
         if color_images is not None:
             _touch(color_images)
+
+    def composite_weights(self, weights_out, flip_x=False):
+        """The weight map of the composite that the last run() / run_hand() left (rules S1-S3 of include/rdf_labels.h,
+        rdf_labels_composite_weights): wherever the composite holds a label, the product of the confidences of the layers
+        that decided it, 65535 = 1.  Reads `label_images` and `conf_images`, writes weights_out (uint16, labels_dims), mirrored
+        in x with flip_x as run_hand mirrors the composite; pixels without a label keep weights_out's bytes.  Needs `min_conf`
+        (ValueError without): (0,) * layers weights without rejecting anything.  One launch on the current stream."""
+        if self._min_conf is None:
+            raise ValueError("composite_weights needs min_conf: the stack keeps no confidences without it "
+                             "((0,) * layers weights without rejecting)")
+        if getattr(self, "_weight_ptrs_cu", None) is None:       # once: the device tables of the layers' labels and confidences
+            self._weight_ptrs_cu = DeviceArray((2, self.num_models), np.int64)
+            self._weight_ptrs_cu.set(np.array([[device_ptr(b) for b in self.label_images],
+                                               [device_ptr(b) for b in self.conf_images]], dtype=np.int64))
+        self._composite_weights(self._weight_ptrs_cu, 1, weights_out, flip_x)
+
+    def composite_weights_batch(self, n, weights_out, flip_x=False):
+        """composite_weights() for the first n frames of the last run_hand_batch(): reads `batch_label_images` and
+        `batch_conf_images`, writes weights_out uint16 [n, lh, lw].  One launch for the n frames."""
+        if self._min_conf is None:
+            raise ValueError("composite_weights_batch needs min_conf: the stack keeps no confidences without it")
+        if getattr(self, "batch_conf_images", None) is None or int(self.batch_conf_images[0].shape[0]) < int(n):
+            raise ValueError(f"composite_weights_batch({n}): run_hand_batch has not run a batch of that many frames")
+        self._composite_weights(self._batch_weight_ptrs_cu, int(n), weights_out, flip_x)
+
+    def _composite_weights(self, tables, n, weights_out, flip_x):
+        weights_out = weights_out.cu() if hasattr(weights_out, "cu") else weights_out
+        assert int(np.prod(weights_out.shape)) == n * self.labels_dims[0] * self.labels_dims[1], weights_out.shape
+        assert np.dtype(weights_out.dtype) == np.uint16
+        lb = _lib.load("labels")
+        nl = self.num_models
+        rc = lb.rdf_labels_composite_weights(tables.ptr, tables.ptr + 8 * int(tables.shape[1]), nl, n, int(self.labels_dims[1]),
+                                             int(self.labels_dims[0]), device_ptr(self.labels_conditions_cu),
+                                             int(self.labels_conditions_cu.shape[0]), 1 if flip_x else 0, weights_out.ptr,
+                                             self.eval._rt.stream())
+        _lib.check(lb, rc, "rdf_labels_composite_weights")
+        _touch(weights_out)
 
     def _fused_tables(self):
         """The host arrays of the fused calls that never change: made once."""

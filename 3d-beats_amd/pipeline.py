@@ -63,12 +63,20 @@ def _release_deferred():
 class HandPipeline:
     def __init__(self, layered_rdf, depth_dims, labels_reduce, eval_to_train_dim_ratio, mean_shift_rounds,
                  mean_shift_variances, fingertip_idxes, intrinsics, plane, depth_mm_level=0, fused_io=True,
-                 hand_state=None, tip_first=0):
+                 hand_state=None, tip_first=0, soft_modes=False):
         """depth_dims = (DIM_Y, DIM_X); intrinsics = (fx, fy, ppx, ppy) of the depth stream; plane = the calibrated
         plane's 4x4 matrix (calibrated_plane.plane) or a float32 device array of 16 elements that is read every frame
         (FrameFrontEnd.calibrated_plane.plane_cu: a recalibration then reaches the heights); fingertip_idxes = 1-based
         composite label ids (3d_bz.py:112); hand_state = a HandState whose fingertips tip_first .. tip_first + n - 1 every
-        frame advances, on the device, from the heights where the chain wrote them (3d_bz.py:496-522 without the read)."""
+        frame advances, on the device, from the heights where the chain wrote them (3d_bz.py:496-522 without the read).
+        soft_modes=True (needs fused_io and a stack with `min_conf` set, ValueError otherwise): the modes are found by
+        WeightedModes with every pixel weighted by the stack's composite confidence (rules S of include/rdf_labels.h) in place
+        of the mean shift; results land where they always do.  False: nothing is allocated or launched for it."""
+        # (what soft_modes cannot serve is refused before anything is allocated or the stack is marked as this pipeline's)
+        if soft_modes and not fused_io:
+            raise ValueError("soft_modes needs fused_io=True")
+        if soft_modes and getattr(layered_rdf, "min_conf", None) is None:
+            raise ValueError("soft_modes needs a stack with min_conf set: (0,) * layers weights without rejecting")
         self._rt = get_runtime()
         self._lib = self._rt.lib
         # run() writes the stack's per-layer label buffers: a stack that already serves another pipeline is replaced by a
@@ -93,6 +101,7 @@ class HandPipeline:
         self.intrinsics = tuple(float(v) for v in intrinsics)
         self.points_ops = PointsOps()
         self.mean_shift = MeanShift()
+        self.soft_modes = bool(soft_modes)
         d, l = (self.DIM_Y, self.DIM_X), (self.LABELS_DIM_Y, self.LABELS_DIM_X)
         self.depth_image_group = GpuBuffer(d, np.uint16)
         self.depth_image_2 = GpuBuffer(d, np.uint16)
@@ -119,6 +128,10 @@ class HandPipeline:
         alloc = getattr(self._rt, "alloc_host_mapped", None)
         if self.fused_io and alloc is not None and len(self.fingertip_idxes) <= 1024:
             self._host = alloc(self._result.nbytes)
+        if self.soft_modes:
+            from .soft_modes import WeightedModes
+            self.weighted_modes = WeightedModes()
+            self.weights_image = GpuBuffer(l, np.uint16)
 
     def run(self, depth_image, depth_image_mm_groups, g_id, flip_x, height_depth=None):
         """depth_image: GpuBuffer uint16 [DIM_Y, DIM_X] (the frame, 0 = no reading);
@@ -140,7 +153,8 @@ class HandPipeline:
         to heights_out_ptr + 8 * f * heights_stride (device memory), its modes to `means_batch[f]` (device, [n, L, 2]) and
         its composite to `labels_batch[f]`; each frame bit for bit what enqueue() computes for it.  No RGBA image is written
         and no hand_state is stepped: the caller steps it, once for both hands.  The batch buffers are sized on first use,
-        for the largest n seen."""
+        for the largest n seen.  With soft_modes the third call is two: the stack's composite_weights_batch into
+        `weights_batch[f]`, then rdf_labels_weighted_modes for the n frames."""
         if not self.fused_io:
             raise ValueError("enqueue_batch needs fused_io=True")
         depth_images, group_images, height_depth = (a.cu() if hasattr(a, "cu") else a
@@ -153,6 +167,8 @@ class HandPipeline:
             self._depth_batch = DeviceArray((n, self.DIM_Y, self.DIM_X), np.uint16)
             self._labels_batch = DeviceArray((n, self.LABELS_DIM_Y, self.LABELS_DIM_X), np.uint16)
             self._means_batch = DeviceArray((n, self._L, 2), np.float64)
+            if self.soft_modes:
+                self._weights_batch = DeviceArray((n, self.LABELS_DIM_Y, self.LABELS_DIM_X), np.uint16)
             self._batch_capacity = n
         dims = np.array([self.DIM_X, self.DIM_Y], dtype=np.int32)
         depth_2, labels = self._depth_batch[:n], self._labels_batch[:n]
@@ -160,6 +176,15 @@ class HandPipeline:
         self.points_ops.prepare_hand_depth_batch(n, dims, self.depth_mm_level, g_id, group_images, depth_images, depth_2,
                                                  flip_x)
         self.layered_rdf.run_hand_batch(depth_2, labels, self.EVAL_TO_TRAIN_DIM_RATIO, flip_x)
+        if self.soft_modes:
+            self.weights_batch = self._weights_batch[:n]
+            self.layered_rdf.composite_weights_batch(n, self.weights_batch, flip_x)
+            self.weighted_modes.run_device_with_heights(
+                self.mean_shift_rounds, labels, self.weights_batch, self._L, self.mean_shift_variances, self._ids,
+                len(self.fingertip_idxes), height_depth, self.LABELS_REDUCE, self.intrinsics, self._plane, self.means_batch.ptr,
+                heights_out_ptr, heights_stride)
+            self.means_batch.mark_dirty()
+            return
         self.mean_shift.run_device_with_heights_batch(
             self.mean_shift_rounds, labels, self._L, self.mean_shift_variances, self._ids, len(self.fingertip_idxes),
             height_depth, self.LABELS_REDUCE, self.intrinsics, self._plane, self.means_batch.ptr, heights_out_ptr,
@@ -302,6 +327,18 @@ class HandPipeline:
             po.make_rgba_from_labels(np.uint32(self.LABELS_DIM_X), np.uint32(self.LABELS_DIM_Y), np.uint32(self._L),
                                      self.labels_image.cu(), self.layered_rdf.label_colors.cu(), self.labels_image_rgba.cu())
 
+        if self.soft_modes:
+            # (pixels without a label keep whatever the weight map held: the modes never read a weight there)
+            self.layered_rdf.composite_weights(self.weights_image, flip_x)
+            base = self._host[1] if self._host is not None else self._result.ptr
+            lshape = (1, self.LABELS_DIM_Y, self.LABELS_DIM_X)
+            self.weighted_modes.run_device_with_heights(
+                self.mean_shift_rounds, self.labels_image.cu().reshape(lshape), self.weights_image.cu().reshape(lshape), self._L,
+                self.mean_shift_variances, self._ids, len(self.fingertip_idxes), height_depth.cu(), self.LABELS_REDUCE,
+                self.intrinsics, self._plane, base, base + self._L * 2 * 8)
+            if self._host is None:
+                self._result.mark_dirty()
+            return
         if self._host is not None:
             base = self._host[1]
             self.mean_shift.run_device_with_heights(

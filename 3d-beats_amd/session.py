@@ -38,12 +38,14 @@ class BeatsSession:
                  mean_shift_variances=(50., 8., 8., 8., 8., 8., 8.), fingertip_idxes=(2, 3, 4, 5, 6), z_thresh_offset=25.,
                  min_velocity=10., max_velocity=120., velocity_sensitive=True, scale_factor=None,
                  fingertip_thresholds=(200., 160., 160., 160., 160.), first_notes=(36, 41), max_frames=8,
-                 num_random_guesses=25000, seed=None, fused_io=True, capacity=4096, post_filter=None):
+                 num_random_guesses=25000, seed=None, fused_io=True, capacity=4096, post_filter=None, soft_modes=False):
         """layered_rdf: a LayeredDecisionForest built for depth_dims = (DIM_Y, DIM_X) and labels_reduce; intrinsics = (focal,
         ppx, ppy) of the depth camera.  The other defaults are the app's (3d_bz.py:49-124); scale_factor = DIM_X / 848 when
         None.  max_frames = the batch of run_sequence's front end and grouping.  post_filter: a DepthPostFilter of the same
         depth_dims that calibrate, tick and run_sequence pass their frames through first; its temporal state runs on from
-        call to call (post_filter.reset() starts it afresh).  Without one nothing is allocated or launched for it."""
+        call to call (post_filter.reset() starts it afresh).  Without one nothing is allocated or launched for it.
+        soft_modes: both hands' pipelines find their modes weighted by the stack's confidence (HandPipeline's soft_modes: needs
+        fused_io and a layered_rdf with min_conf set); False, the default, changes nothing."""
         self._rt = get_runtime()
         self.DIM_Y, self.DIM_X = int(depth_dims[0]), int(depth_dims[1])
         self.max_frames = int(max_frames)
@@ -63,9 +65,9 @@ class BeatsSession:
         args = ((self.DIM_Y, self.DIM_X), labels_reduce, scale, mean_shift_rounds, list(mean_shift_variances),
                 list(fingertip_idxes), (focal, focal, ppx, ppy), self.front_end.calibrated_plane.plane_cu)
         self.right = HandPipeline(layered_rdf, *args, depth_mm_level=depth_mm_level, fused_io=fused_io,
-                                  hand_state=self.hand_state, tip_first=0)
+                                  hand_state=self.hand_state, tip_first=0, soft_modes=soft_modes)
         self.left = HandPipeline(layered_rdf, *args, depth_mm_level=depth_mm_level, fused_io=fused_io,
-                                 hand_state=self.hand_state, tip_first=n)
+                                 hand_state=self.hand_state, tip_first=n, soft_modes=soft_modes)
         self.n_tips = 2 * n
         hm, wm = self.grouping.depth_mm_dims
         self._raw = DeviceArray((self.max_frames, self.DIM_Y, self.DIM_X), np.uint16)

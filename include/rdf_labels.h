@@ -594,6 +594,72 @@ int rdf_labels_forest_posterior(const uint16_t *depth, int n_img, int dim_x, int
 int rdf_labels_confidence_counts(int n_img, int dim_x, int dim_y, int labels_reduce, int bins, const uint16_t *pred,
                                  const uint16_t *conf, const uint16_t *truth, uint64_t *counts, void *stream);
 
+/*
+ * Soft modes: mean-shift mode finding in which every pixel pulls with a weight -- the forest's confidence in it -- where
+ * rdf_mean_shift (librdf_hip.so) lets every pixel of a class pull equally.  rdf_labels_composite_weights makes the weight
+ * map of a layered stack from the per-layer labels and confidences that the gated stack leaves (rules Q); for a plain
+ * forest the confidence map of rdf_labels_forest_posterior is the weight map.  rdf_labels_weighted_modes finds the modes
+ * and, on request, the fingertip heights of any number of frames in one launch.  The reference keeps no posterior and has
+ * no counterpart; the rules below are this library's own and tests/soft_modes_numpy.py restates them.
+ *
+ * Composite weights.  layer_labels, layer_conf: DEVICE tables of n_layers device pointers, each to a uint16
+ * [n_img][dim_y][dim_x] map.  cond int32 [n_cond][2], the conditions table of rdf_composite.  weights_out uint16
+ * [n_img][dim_y][dim_x].
+ * S1. Path: exactly rdf_composite's walk.  off = 0; for layer j = 0 .. n_layers - 1: l = layer_labels[j][i][y][x]; if l is 0 or
+ *     65535, stop: nothing is written.  e = off + l - 1; if e is outside 0 .. n_cond - 1, stop: nothing is written.  (t, v) =
+ *     cond[e]; t == 0: the pixel is final; else off = v and the walk goes on.  Falling off the last layer writes nothing.  A
+ *     weight is written exactly where rdf_composite writes a label, and nowhere else: callers pre-fill.
+ * S2. Weight: w = 65535; at every layer visited, the final one included, with k = layer_conf[j][i][y][x]:
+ *     w = (w * k + 32767) / 65535 in unsigned 32-bit integers (65535^2 + 32767 < 2^32).  One layer gives w = k; 65535 is
+ *     neutral, 0 absorbs.
+ * S3. Store: weights_out[i][y][flip_x ? dim_x - 1 - x : x] = w, the mirror rdf_layered_run_hand applies to the composite.
+ *
+ * Weighted modes.  labels, weights uint16 [n_img][dim_y][dim_x]; weights may be NULL: every weight is 1.  means_out float64
+ * [n_img][num_classes][2] = (x, y); variances float32 [num_classes].
+ * S4. Pixels.  The pixels p of class c = 1 .. num_classes in image i are those with labels[p] == c; each has the integer
+ *     weight w_p.  Labels 0, 65535 and anything above num_classes are ignored.  A pixel with w_p = 0 contributes nothing; the
+ *     others are the class's COUNTED pixels.
+ * S5. Round 0: m = (sum w x / sum w, sum w y / sum w).  For maps below 2^21 pixels the three sums are integers below 2^53, exact
+ *     in fp64 in any order, followed by one IEEE divide each: a bit-exact target.  sum w == 0 gives NaN (0 / 0), as a class
+ *     without pixels does in rdf_mean_shift.
+ * S6. Round r >= 1: v2 = (double)(float)(var * var), as rdf_mean_shift; g_p = exp(-((x - mx)^2 + (y - my)^2) / (2 v2)), which
+ *     the kernel takes as the product of a column and a row factor, exp(-(x - mx)^2 / (2 v2)) * exp(-(y - my)^2 / (2 v2)), from
+ *     two tables per round when dim_x + dim_y <= 3072 and v2 > 0; m += (sum (w g) dx / sum w g, sum (w g) dy / sum w g) with dx
+ *     = x - mx, dy = y - my.  The sums are taken in an order fixed by the code (below), with no floating-point atomics: the
+ *     result is the same bits from run to run and from any pointer alignment.  num_rounds == 0 returns zeros.  v2 == 0 (a
+ *     variance whose float square is 0) takes no tables: exp(-d / 0) is 0 off the mean and NaN on it, so such a class is NaN
+ *     from round 1 on, as in rdf_mean_shift.
+ * S7. Heights, when n_ids > 0: heights_out[f * heights_stride + k], k < n_ids, from frame f's final mean of class class_ids[k]
+ *     by the rule of rdf_fingertip_heights (truncate, times labels_reduce, off-frame or NaN gives NaN, fp32 deprojection, fp64
+ *     plane row; depth uint16 [n_img][depth_dim_y][depth_dim_x]): bit for bit what that call returns for the same means.  An
+ *     id outside 1 .. num_classes gives NaN.  n_ids == 0: no heights, and the height arguments are not looked at.
+ * S8. Arguments.  n_layers < 1, a negative dimension or count, num_classes outside 1..64, dim_x or dim_y above 65535, num_rounds
+ *     < 0, n_ids outside 0..1024, with n_ids > 0 labels_reduce < 1 or heights_stride < n_ids, or a misaligned pointer (2 bytes
+ *     for the maps, 4 for cond, variances, class_ids and plane, 8 for the pointer tables, means_out and heights_out) is
+ *     RDF_ERR_BAD_ARG; n_img * dim_y * dim_x >= 2^31 (of the labels or of the depth frames) or n_img > 65535 frames in one
+ *     weighted_modes call RDF_ERR_TOO_LARGE; zero pixels is a successful no-op; else a NULL pointer (weights excepted, and the
+ *     height arguments when n_ids == 0) is RDF_ERR_NULL_PTR.  A rejected call launches nothing.
+ * Each call is one launch, stream-ordered, with nothing read back; means_out and heights_out may be mapped pinned host memory.
+ * composite_weights: one lane per pixel, a wave leaves at once when none of its 64 pixels starts a path.  weighted_modes:
+ * one workgroup of 1024 threads per (class, frame), grid (num_classes, n_img).  The workgroup lists the class's counted pixels
+ * once in LDS -- x | y << 16 plus the 16-bit weight, 6 bytes an entry; pixels of weight 0 are skipped at listing time and take
+ * no slot -- and runs all rounds on the list.  The list order is fixed: the map is cut into batches of 106 496 pixels, step k
+ * = 0 .. 12 of wave w = 0 .. 15 covers the 512 pixels from (k * 16 + w) * 512 of the batch on, eight consecutive ones a lane; a
+ * lane's pixels of all its steps take consecutive slots, and the lanes of a wave, the waves and the batches follow in index
+ * order (positions from scans, never from arrival).  Thread t sums entries t, t + 1024, ...; a wave's 64 partial sums are added
+ * by a shift-add scan inside each row of 16 lanes and the four rows in order, the 16 waves in order.  A class with more than
+ * rdf_labels_weighted_modes_list_cap() counted pixels (20 480: the list and the tables fill 148 288 B of a compute unit's 160
+ * KB) is not listed: thread t visits pixels t, t + 1024, ... of the maps in every round.
+ */
+int rdf_labels_composite_weights(const uint16_t *const *layer_labels, const uint16_t *const *layer_conf, int n_layers, int n_img,
+                                 int dim_x, int dim_y, const int32_t *cond, int n_cond, int flip_x, uint16_t *weights_out,
+                                 void *stream);
+int rdf_labels_weighted_modes(const uint16_t *labels, const uint16_t *weights, int n_img, int dim_x, int dim_y, int num_classes,
+                              const float *variances, int num_rounds, double *means_out, const int *class_ids, int n_ids,
+                              const uint16_t *depth, int depth_dim_x, int depth_dim_y, int labels_reduce, float fx, float fy,
+                              float ppx, float ppy, const float *plane, double *heights_out, int heights_stride, void *stream);
+uint32_t rdf_labels_weighted_modes_list_cap(void);
+
 int rdf_labels_abi_version(void);
 const char *rdf_labels_build_id(void);
 const char *rdf_labels_error_string(int code);
