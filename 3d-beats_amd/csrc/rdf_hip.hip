@@ -1636,6 +1636,15 @@ ForestKernel<NL> forest_kernel(const KernelKey &key)
     return i < 0 ? nullptr : reinterpret_cast<ForestKernel<NL>>(const_cast<void *>(g_forest_kernels[i]));
 }
 
+// Which kernel the launches took (rdf_debug_kernel_launches): one counter per entry of kForestKernels, bumped on the host when a
+// call that returned RDF_OK issued its launch -- once per call, however many HIP launches it made.
+std::atomic<unsigned long long> g_kernel_launches[kNumForestKernels];
+inline void count_kernel_launch(const KernelKey &key)
+{
+    const int i = kernel_index(key);
+    if (i >= 0) g_kernel_launches[i].fetch_add(1, std::memory_order_relaxed);
+}
+
 int launch_one(ForestKernel<1> kern, int block, const EvalArgs &a, int lds_bytes, DeviceState &ds, int cus, hipStream_t st, const SplitSpec *split)
 {
     int per_cu = 0;
@@ -1836,6 +1845,7 @@ int dispatch(const Plan &p, void *stream, const SplitSpec *split)
     g_host_ns_plan.fetch_add(t_launch - p.t_entry, std::memory_order_relaxed);
     g_host_ns_launch.fetch_add(t_done - t_launch, std::memory_order_relaxed);
     g_host_calls.fetch_add(1, std::memory_order_relaxed);
+    if (rc == RDF_OK) count_kernel_launch(key);
     return rc;
 }
 
@@ -1856,7 +1866,10 @@ int launch_layers(const Plan *plans, bool tw_all, int cmax, int lds, DeviceState
     for (int i = 0; i < NL; ++i) ka.l[i] = plans[i].a;
     const KernelKey key = select_layers_kernel(NL, cmax, tw_all);
     const ForestKernel<NL> kern = forest_kernel<NL>(key);
-    return kern ? launch_multi<NL>(kern, key.block, ka, lds, ds, cus, st) : RDF_ERR_BUILD;
+    if (!kern) return RDF_ERR_BUILD;
+    const int rc = launch_multi<NL>(kern, key.block, ka, lds, ds, cus, st);
+    if (rc == RDF_OK) count_kernel_launch(key);
+    return rc;
 }
 
 } // namespace
@@ -2382,6 +2395,29 @@ int rdf_debug_host_overhead(unsigned long long out[5], int reset)
         out[3] = g_host_ns_layered.load(); out[4] = g_host_layered_calls.load();
     }
     if (reset) { g_host_ns_plan = 0; g_host_ns_launch = 0; g_host_calls = 0; g_host_ns_layered = 0; g_host_layered_calls = 0; }
+    return RDF_OK;
+}
+
+// test hook: which k_eval_forest the forest launches since the last reset took, one counter per entry of kForestKernels in the
+// list's order (counted on the host when a launch is issued: see rdf_hip.h).  Returns the length of the list.
+int rdf_debug_kernel_launches(unsigned long long *out, int n, int reset)
+{
+    for (int i = 0; i < kNumForestKernels; ++i) {
+        const unsigned long long v = reset ? g_kernel_launches[i].exchange(0, std::memory_order_relaxed)
+                                           : g_kernel_launches[i].load(std::memory_order_relaxed);
+        if (out && i < n) out[i] = v;
+    }
+    return kNumForestKernels;
+}
+
+// ... and the template arguments of entry `index`, in KernelKey's order
+int rdf_debug_kernel_key(int index, int key_out[9])
+{
+    if (index < 0 || index >= kNumForestKernels) return RDF_ERR_BAD_ARG;
+    if (!key_out) return RDF_ERR_NULL_PTR;
+    const KernelKey &k = kForestKernels[index];
+    const int f[9] = {k.block, k.packed, k.cmax, k.stats, k.group, k.compact, k.nl, k.tw, k.deep};
+    for (int i = 0; i < 9; ++i) key_out[i] = f[i];
     return RDF_OK;
 }
 

@@ -560,6 +560,18 @@ int rdf_debug_div_f32(const float *num, const float *den, float *out, size_t n, 
  * forest launch is handed to the HIP runtime, out[1] nanoseconds inside the runtime's launch call, out[2] forest launches;
  * out[3] nanoseconds inside rdf_layered_run[_hand] from entry to return (runtime included), out[4] such calls.  `out` nullable. */
 int rdf_debug_host_overhead(unsigned long long out[5], int reset);
+/* Test hook: which forest kernel the launches took.  The library holds a fixed list of forest kernels (the instantiations of
+ * one template) and one counter per entry.  A forest evaluation that returned RDF_OK adds one to the counter of the kernel it
+ * launched -- once per call, however many launches the call made (rdf_eval_forest_packed_split counts once; the layers of
+ * rdf_layered_run evaluated in one launch count once, evaluated one by one they count once per layer).  Counting happens on
+ * the host when the launch is issued: a launch recorded during stream capture counts when it is captured, replays of the
+ * captured graph do not count.
+ * rdf_debug_kernel_launches returns the length of the list and copies the first min(n, length) counters to `out` (nullable:
+ * to ask for the length, or to reset only); `reset` != 0 puts every counter back to zero.
+ * rdf_debug_kernel_key fills key_out with the nine template arguments of entry `index`, in the order {block, packed, cmax,
+ * stats, group, compact, nl, tw, deep} (bools as 0 / 1); RDF_ERR_BAD_ARG for an index outside the list. */
+int rdf_debug_kernel_launches(unsigned long long *out, int n, int reset);
+int rdf_debug_kernel_key(int index, int key_out[9]);
 
 /* Tuning knobs for measurements and tests.  Not part of the reference surface, and NOT part of the re-entrancy promise the
  * evaluation calls make: every knob is ONE process-wide atomic int, read once per call, so a change is seen by every
