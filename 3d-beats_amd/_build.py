@@ -12,7 +12,7 @@ SOURCES = [SRC, os.path.join(HERE, "csrc", "mean_shift_hip.hip"), os.path.join(H
            os.path.join(HERE, "csrc", "tree_train_hip.hip"), os.path.join(HERE, "csrc", "grouping_hip.hip")]
 HEADERS = [os.path.join(HERE, "..", "include", "rdf_hip.h"), os.path.join(HERE, "csrc", "rdf_device.hpp"),
            os.path.join(HERE, "csrc", "rdf_host_state.hpp"), os.path.join(HERE, "csrc", "rdf_launch_plan.hpp"),
-           os.path.join(HERE, "csrc", "rdf_kernel_util.hpp")]
+           os.path.join(HERE, "csrc", "rdf_kernel_util.hpp"), os.path.join(HERE, "csrc", "rdf_modes.hpp")]
 SO = os.path.join(HERE, "csrc", "librdf_hip.so")
 
 
@@ -39,7 +39,8 @@ LIBRARIES = {lib.key: lib for lib in (
     # forest's leaf distributions on such frames (its walk takes the reference-layout feature step -- the offset coordinate and
     # the bounds-checked read -- from rdf_device.hpp, the forest and training kernels' header), and the forest's posterior:
     # the same walk ending in per-pixel class sums, a confidence and a gated label where inference ends in an argmax, and the
-    # consumer of that confidence: composite weights of a layered stack and the weighted mean shift (soft modes)
+    # consumer of that confidence: composite weights of a layered stack and the weighted mean shift (soft modes), whose kernel
+    # body is the mean shift's own: rdf_modes.hpp is a header of this library and of "hip", and a change to it rebuilds both
     Library("labels", os.path.join(HERE, "csrc", "librdf_labels.so"),
             [os.path.join(HERE, "csrc", "labels_hip.hip"), os.path.join(HERE, "csrc", "rerender_hip.hip"),
              os.path.join(HERE, "csrc", "score_hip.hip"), os.path.join(HERE, "csrc", "hand_scene_hip.hip"),
@@ -47,7 +48,8 @@ LIBRARIES = {lib.key: lib for lib in (
              os.path.join(HERE, "csrc", "forest_refit_hip.hip"), os.path.join(HERE, "csrc", "forest_posterior_hip.hip"),
              os.path.join(HERE, "csrc", "soft_modes_hip.hip")],
             [os.path.join(HERE, "..", "include", "rdf_labels.h"), os.path.join(HERE, "csrc", "rdf_kernel_util.hpp"),
-             os.path.join(HERE, "csrc", "rdf_raster.hpp"), os.path.join(HERE, "csrc", "rdf_device.hpp")], "rdf_labels_"),
+             os.path.join(HERE, "csrc", "rdf_raster.hpp"), os.path.join(HERE, "csrc", "rdf_device.hpp"),
+             os.path.join(HERE, "csrc", "rdf_modes.hpp")], "rdf_labels_"),
 )}
 
 # No -ffast-math, no -fgpu-flush-denormals-to-zero: the fp32 divide must stay IEEE-correct

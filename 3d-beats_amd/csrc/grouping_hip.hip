@@ -27,9 +27,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <mutex>
-
 #include "../../include/rdf_hip.h"
+#include "rdf_kernel_util.hpp"
 
 namespace {
 
@@ -397,23 +396,6 @@ __global__ __launch_bounds__(kResThreads) void k_gl_coords(int Wm, int Hm, Ws w,
     emit_coords(P, Wm, (int)(b0 >> 32), s_of, coords + (size_t)f * P * 3, s_wtot);
 }
 
-int allow_resident_lds()
-{
-    static std::mutex mu;
-    static unsigned long long allowed = 0ull;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return RDF_ERR_NO_DEVICE;
-    std::lock_guard<std::mutex> lock(mu);
-    if (dev >= 64 || !((allowed >> dev) & 1ull)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_groups_resident),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)resident_lds_bytes(kResMaxPixels));
-        if (e != hipSuccess) return (int)e;
-        if (dev < 64) allowed |= 1ull << dev;
-    }
-    return RDF_OK;
-}
-
 } // namespace
 
 extern "C" {
@@ -440,7 +422,9 @@ int rdf_hand_groups(const uint16_t *depth, int n, int dim_x, int dim_y, int mipm
     if (path == 1 && !fits) return RDF_ERR_BAD_ARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (path == 1 || (path == 0 && fits)) {
-        const int rc = allow_resident_lds();
+        static LdsAllowance allowed;
+        const int rc = allowed.allow(reinterpret_cast<const void *>(k_groups_resident), (int)resident_lds_bytes(kResMaxPixels),
+                                     RDF_ERR_NO_DEVICE);
         if (rc != RDF_OK) return rc;
         hipLaunchKernelGGL(k_groups_resident, dim3((unsigned)n), dim3(kResThreads), resident_lds_bytes((int)P), s, depth,
                            dim_x, dim_y, mipmap_level, Wm, Hm, pct_thresh, groups_out, g_info_out, components_out, coords_out);

@@ -1,12 +1,15 @@
 // rdf_kernel_util.hpp -- the small helpers that sources of the three libraries have in common: the 32-bit mix behind every
 // hash rule of include/rdf_labels.h, the wave-wide sums and the 64-bit shuffle, the lanes of a wave that share a key, the
-// unpacking of eight 16-bit pixels, and the host one-liners of the entry points.  A helper that only one file uses stays in
-// that file; so do constants that mean different things in different files (kThreads, kMaxGrid*).
+// unpacking of eight 16-bit pixels, and the host one-liners of the entry points and their allowance of large dynamic LDS.
+// A helper that only one file uses stays in that file; so do constants that mean different things in different files
+// (kThreads, kMaxGrid*).
 #ifndef RDF_KERNEL_UTIL_HPP
 #define RDF_KERNEL_UTIL_HPP
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <mutex>
 
 namespace {
 
@@ -69,6 +72,25 @@ inline hipStream_t S(void *s) { return reinterpret_cast<hipStream_t>(s); }
 inline unsigned blocks(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 inline bool misaligned(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }    // a: a power of two
 inline bool finite_f(float v) { return __builtin_fabsf(v) <= 3.0e38f; }                                          // false for NaN
+
+// A launch with more than 64 KB of dynamic LDS has to be allowed once per device and kernel: one static instance per kernel.
+struct LdsAllowance {
+    std::mutex mu;
+    u64 allowed = 0;      // bit d: done on device d (a device from 64 on is allowed again at every call)
+    // 0, `no_device_code` without a current device, or the hipError_t of a failed attribute call
+    int allow(const void *kernel, int bytes, int no_device_code)
+    {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) return no_device_code;
+        std::lock_guard<std::mutex> lock(mu);
+        if (dev >= 64 || !((allowed >> dev) & 1ull)) {
+            const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+            if (e != hipSuccess) return (int)e;
+            if (dev < 64) allowed |= 1ull << dev;
+        }
+        return 0;
+    }
+};
 
 }  // namespace
 

@@ -1,8 +1,9 @@
 """Inputs of the mean-shift tests: small pure functions that the CPU tests (preconditions, the restatement's own error) and
 the GPU tests (the kernel against the restatement) both call, so that both see the same arrays.
 
-Every builder names the branch of csrc/mean_shift_hip.hip it is there for.  The three limits below are the kernel's
-(kMsListCap, kMsTabCap, kMsMaxClasses); a test that passes with other values there checks another branch than it says."""
+Every builder names the branch of the kernel body (csrc/rdf_modes.hpp, the Unweighted policy) it is there for.  The three
+limits below are the kernel's (Unweighted::kListCap, kTabCap, kModesMaxClasses); a test that passes with other values there
+checks another branch than it says."""
 import functools
 import math
 from typing import NamedTuple
@@ -116,7 +117,7 @@ CAP_HOLES = (3, 100, 5000, 20001, 32760, 32765)     # six: every later lane's fi
 
 @functools.lru_cache(maxsize=None)
 def list_cap_image(n1):
-    """Class 1 = the first n1 pixels in raster order but for a few holes, so that slot kMsListCap falls inside a lane's
+    """Class 1 = the first n1 pixels in raster order but for a few holes, so that slot LIST_CAP falls inside a lane's
     eight pixels; class 2 a small blob after it; class 3 absent."""
     h, w = CAP_SHAPE
     lab = np.full((h, w), NO_LABEL, np.uint16)

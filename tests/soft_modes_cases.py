@@ -2,7 +2,7 @@
 restatement's own error) and the GPU tests (the kernels against the restatement) both call, so that both see the same arrays.
 Every reference is computed once, shared and left unchanged (read-only arrays).
 
-TAB_CAP is the kernel's kTabCap (csrc/soft_modes_hip.hip); the list cap is read from the library
+TAB_CAP is the kernel's kTabCap (csrc/rdf_modes.hpp); the list cap is read from the library
 (rdf_labels_weighted_modes_list_cap) and handed in by the GPU tests, CAP_FOR_CPU is what the CPU tests build the same cases from."""
 import functools
 
@@ -88,6 +88,19 @@ def random_weights(seed, shape):
     return wts
 
 
+WRAP_CASES = ((9, 8, 27, 8), (7, 9, 3, 13), (5, 15, 35, 0))      # h, w, the seeds of the labels and of the weights
+
+
+def wrap_case(h, w, label_seed, weight_seed):
+    """Two classes on a map whose rows are just wide enough for the lister's unrolled write-out (dim_x >= 8): at width 8 a
+    lane's eight pixels are exactly a row, at 9 and 15 they wrap once, at a different pixel in every lane.  Some pixels of the
+    classes have weight 0 (they take no slot: the slots after them move up) and every class keeps a counted pixel."""
+    lab, wts = blob_labels(label_seed, h, w, 2), random_weights(weight_seed, (h, w))
+    on = (lab == 1) | (lab == 2)
+    assert w >= 8 and (wts[on] == 0).any() and all(((lab == k) & (wts != 0)).any() for k in (1, 2))
+    return lab, wts
+
+
 def _raster_class(lab, label, start, count, holes):
     flat = lab.reshape(-1)
     idx = np.setdiff1d(np.arange(start, start + count + len(holes)), np.asarray(holes, np.int64))[:count]
@@ -144,7 +157,7 @@ def table_boundary(w):
     return lab, wts
 
 
-BATCH = 16 * 13 * 512       # pixels the sixteen waves list per batch (kWaves * kSteps * 512): larger maps take the lister's outer loop
+BATCH = 16 * 13 * 512       # pixels the sixteen waves list per batch (kModesWaves * kSteps * 512): larger maps take the lister's outer loop
 BATCH_SHAPES = ((5, 21301), (4, 53253))
 assert 5 * 21301 == BATCH + 9 and 2 * BATCH < 4 * 53253 < 3 * BATCH
 
@@ -217,6 +230,8 @@ def _builders(cap):
     b["blobs_240x424"] = lambda: (blob_labels(4, 240, 424, 7), random_weights(52, (240, 424)), 7,
                                   [50., 8., 8., 8., 8., 8., 8.], (1, 2, 6, 7))
     b["narrow_45x7"] = lambda: (blob_labels(8, 45, 7, 2), random_weights(53, (45, 7)), 2, [4.0, 6.0], (1, 2, 6, 7))
+    for wrap in WRAP_CASES:
+        b["wrap_%dx%d" % wrap[:2]] = lambda wrap=wrap: wrap_case(*wrap) + (2, [2.0, 3.0], (1, 2, 6, 7))
     for n_class, n_zero in ((cap - 1, 0), (cap, 0), (cap + 1, 0), (cap + 1, 2), (cap + 2, 2)):
         b[f"cap_{n_class - cap:+d}_zeros_{n_zero}"] = lambda n=n_class, z=n_zero: cap_image(cap, n, z) + (3, [30.0, 5.0, 4.0], (1, 4))
     b["both_over_cap"] = lambda: both_over_cap_image(cap) + (3, [40.0, 45.0, 4.0], (1, 4))

@@ -111,6 +111,30 @@ def test_library_binding_header_and_sources_agree(name, rdf):
     assert build.sources_present(name) and not build.is_stale(name)
 
 
+def test_the_shared_modes_body_is_in_the_build_id_of_both_its_libraries(rdf, tmp_path, monkeypatch):
+    """csrc/rdf_modes.hpp is compiled into librdf_hip.so (k_mean_shift_fused) and librdf_labels.so (k_weighted_modes): it is a
+    header of both, and a change to it changes both ids -- a librdf_hip.so from before the change would otherwise pass the
+    build-id check.  (On a copy of the sources: nothing in the tree is touched.)"""
+    build, _ = _modules()
+    users = [name for name in LIBS if "rdf_modes.hpp" in map(os.path.basename, build.LIBRARIES[name].headers)]
+    assert users == ["hip", "labels"]
+    in_tree = {name: build.source_id(name) for name in LIBS}
+    copies = {}
+    for name in LIBS:
+        rec = build.LIBRARIES[name]
+        os.mkdir(tmp_path / name)
+        copies[name] = rec._replace(sources=[shutil.copy(p, tmp_path / name) for p in rec.sources],
+                                    headers=[shutil.copy(p, tmp_path / name) for p in rec.headers])
+    monkeypatch.setattr(build, "LIBRARIES", copies)
+    assert {name: build.source_id(name) for name in LIBS} == in_tree
+    for name in users:
+        with open(tmp_path / name / "rdf_modes.hpp", "a") as f:
+            f.write("// touched\n")
+    touched = {name: build.source_id(name) for name in LIBS}
+    assert touched["hip"] != in_tree["hip"] and touched["labels"] != in_tree["labels"]
+    assert touched["frontend"] == in_tree["frontend"]
+
+
 @pytest.mark.parametrize("name", LIBS)
 def test_code_object_targets_gfx950(name, rdf):
     build = import_module("3d-beats_amd._build")

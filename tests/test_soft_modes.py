@@ -3,7 +3,8 @@ LayeredDecisionForest.composite_weights[_batch], HandPipeline / BeatsSession wit
 tests/soft_modes_numpy.py.  The CPU tests pin the restatement to answers worked by hand, check the preconditions under which the
 kernel's factorised weights and the restatement's single exponential agree, the restatement's own rounding, the header, the
 bindings and the argument checks (which launch nothing).  On the GPU the weights and round 0 are bit for bit, later rounds
-within BOUND_PX = 1e-9 px (the bound of the mean-shift row), and every result is the same bits twice."""
+within BOUND_PX = 1e-9 px (the bound of the mean-shift row), every result is the same bits twice, and without weights every
+round is the mean shift's bits (one kernel body, csrc/rdf_modes.hpp)."""
 import ctypes
 import importlib
 import os
@@ -12,6 +13,7 @@ import re
 import numpy as np
 import pytest
 
+import mean_shift_cases as mc
 import posterior_cases as pc
 import posterior_numpy as pn
 import session_cases as sc
@@ -160,6 +162,7 @@ def test_mode_cases_meet_the_preconditions_and_the_restatements_error_is_small()
     assert all(int(((both.labels == k) & (both.weights != 0)).sum()) > cap for k in (1, 2))
     assert smc.uses_tables(smc.case("tables_3069"))[0] and not smc.uses_tables(smc.case("no_tables_3070"))[0]
     assert np.isnan(smc.trace("blobs_120x212")[0][4]).all() and smc.case("narrow_45x7").labels.shape[1] < 8
+    assert [smc.case(n).labels.shape for n in ("wrap_9x8", "wrap_7x9", "wrap_5x15")] == [(9, 8), (7, 9), (5, 15)]
     for name in ("blobs_33x65", "blobs_120x212", "blobs_240x424"):
         c = smc.case(name)
         on = c.weights[(c.labels >= 1) & (c.labels <= c.L)]
@@ -277,27 +280,55 @@ def test_composite_weights_bit_exact(shape, rdf, gpu_runtime):
 
 @pytest.mark.gpu
 def test_without_weights_and_with_uniform_weights_it_is_the_mean_shift(rdf, gpu_runtime):
+    """Both kernels are one body (csrc/rdf_modes.hpp): with every weight 1 -- no weight map, or a map of ones -- the weighted
+    policy multiplies by 1.0 where the unweighted one does nothing, and while a class is under both list caps it sums the same
+    entries in the same order: the mean shift's bits at every round.  Other uniform weights round in the later rounds."""
     ms = _mod("cuda.mean_shift").MeanShift()
     wm = _wm(rdf)
     for seed, (h, w), L in ((5, (33, 65), 2), (3, (120, 212), 6)):
         lab = smc.blob_labels(seed, h, w, L, absent=(5,) if L > 4 else ())
+        assert max(int((lab == k).sum()) for k in range(1, L + 1)) < min(wm.list_cap, mc.LIST_CAP) // 4      # far below both caps
         var = rdf.to_device(np.linspace(6.0, 14.0, L).astype(np.float32))
         dl = rdf.to_device(lab[None])
+        ones = rdf.to_device(np.ones((1, h, w), np.uint16))
         for rounds in (1, 2, 6, 7):                                  # round 0 alone, then through rounds 1, 5 and 6
             want = ms.run(rounds, dl, L, var)
             got = wm.run(rounds, dl, None, L, var)
             assert got.shape == (L, 2) and got.dtype == np.float64
-            if rounds == 1:
-                assert np.array_equal(_canon(got), _canon(want)), (h, w, got, want)
-            assert np.array_equal(np.isnan(got), np.isnan(want))
-            ok = ~np.isnan(want)
-            err = np.abs(got[ok] - want[ok]).max()
-            print(f"{h}x{w} rounds={rounds}: max |weighted(NULL) - mean shift| = {err:.3e} px")
-            assert err < BOUND_PX
+            assert np.array_equal(_canon(got), _canon(want)), (h, w, rounds, got, want)
+            if rounds == 6:
+                assert np.array_equal(_canon(wm.run(rounds, dl, ones, L, var)), _canon(want)), (h, w, got, want)
         unweighted = wm.run(1, dl, None, L, var)
         for k in (1, 7, 65535):
             got = wm.run(1, dl, rdf.to_device(np.full((1, h, w), k, np.uint16)), L, var)
             assert np.array_equal(_canon(got), _canon(unweighted)), k
+
+
+@pytest.mark.gpu
+def test_without_weights_heights_and_frames_are_the_mean_shifts(rdf, gpu_runtime):
+    """Three frames in one launch with the heights riding on it: WeightedModes without a weight map against
+    MeanShift.run_device_with_heights_batch, means and heights bit for bit."""
+    ms = _mod("cuda.mean_shift").MeanShift()
+    wm = _wm(rdf)
+    h, w, L, r = 33, 65, 2, 2
+    labs = rdf.to_device(np.stack([smc.blob_labels(5 + i, h, w, L) for i in range(3)]))
+    depths = rdf.to_device(np.stack([smc.height_inputs(h, w, r, 80 + i)[0] for i in range(3)]))
+    _, plane, intr = smc.height_inputs(h, w, r, 80)
+    ids = np.array([2, 1, 3, 0, 2], np.int32)                        # 3 and 0 name no class
+    d_ids, d_plane, dv = rdf.to_device(ids), rdf.to_device(plane), rdf.to_device(np.array([5.0, 7.0], np.float32))
+    out = {}
+    for name in ("weighted", "mean_shift"):
+        means = rdf.DeviceArray((3, L, 2), np.float64).fill(7.0)
+        hts = rdf.DeviceArray((3, len(ids)), np.float64).fill(7.0)
+        if name == "weighted":
+            wm.run_device_with_heights(6, labs, None, L, dv, d_ids, len(ids), depths, r, intr, d_plane, means.ptr, hts.ptr, len(ids))
+        else:
+            ms.run_device_with_heights_batch(6, labs, L, dv, d_ids, len(ids), depths, r, intr, d_plane, means.ptr, hts.ptr, len(ids))
+        out[name] = (means.get(), hts.get())
+    (m_w, h_w), (m_s, h_s) = out["weighted"], out["mean_shift"]
+    assert np.isfinite(m_s).all() and np.isfinite(h_s[:, [0, 1, 4]]).all() and np.isnan(h_s[:, [2, 3]]).all()
+    assert np.array_equal(_canon(m_w), _canon(m_s)), (m_w, m_s)
+    assert np.array_equal(_canon(h_w), _canon(h_s)), (h_w, h_s)
 
 
 @pytest.mark.gpu
@@ -342,8 +373,10 @@ def _check(wm, dl, dw, dv, c, name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["blobs_33x65", "blobs_120x212", "blobs_240x424", "narrow_45x7"])
+@pytest.mark.parametrize("name", ["blobs_33x65", "blobs_120x212", "blobs_240x424", "narrow_45x7", "wrap_9x8", "wrap_7x9", "wrap_5x15"])
 def test_random_blobs_and_weights(name, rdf, gpu_runtime):
+    """(narrow_45x7: rows under eight pixels, the lister's write-out that wraps more than once; wrap_*: the narrowest rows of the
+    unrolled write-out, a lane's eight pixels exactly a row or wrapping once.)"""
     wm = _wm(rdf)
     c = smc.case(name)
     dv = rdf.to_device(c.variances)
