@@ -36,8 +36,9 @@ LIBRARIES = {lib.key: lib for lib in (
     # glove-colour recordings to training labels, the re-render that augments them, the score of predicted label maps, and
     # labelled frames of the articulated hand, the fit of that hand's pose to a labelled depth frame, and the stereo depth
     # sensor that turns a left and a right render of those frames into what a camera would report, and the refit of a trained
-    # forest's leaf distributions on such frames (its walk takes the reference-layout feature step -- the offset coordinate and
-    # the bounds-checked read -- from rdf_device.hpp, the forest and training kernels' header), and the forest's posterior:
+    # forest's leaf distributions on such frames and the pruning of the forest on the same counts (the refit's walk takes the
+    # reference-layout feature step -- the offset coordinate and the bounds-checked read -- from rdf_device.hpp, the forest
+    # and training kernels' header), and the forest's posterior:
     # the same walk ending in per-pixel class sums, a confidence and a gated label where inference ends in an argmax, and the
     # consumer of that confidence: composite weights of a layered stack and the weighted mean shift (soft modes), whose kernel
     # body is the mean shift's own: rdf_modes.hpp is a header of this library and of "hip", and a change to it rebuilds both
@@ -45,8 +46,8 @@ LIBRARIES = {lib.key: lib for lib in (
             [os.path.join(HERE, "csrc", "labels_hip.hip"), os.path.join(HERE, "csrc", "rerender_hip.hip"),
              os.path.join(HERE, "csrc", "score_hip.hip"), os.path.join(HERE, "csrc", "hand_scene_hip.hip"),
              os.path.join(HERE, "csrc", "pose_fit_hip.hip"), os.path.join(HERE, "csrc", "stereo_sensor_hip.hip"),
-             os.path.join(HERE, "csrc", "forest_refit_hip.hip"), os.path.join(HERE, "csrc", "forest_posterior_hip.hip"),
-             os.path.join(HERE, "csrc", "soft_modes_hip.hip")],
+             os.path.join(HERE, "csrc", "forest_refit_hip.hip"), os.path.join(HERE, "csrc", "forest_prune_hip.hip"),
+             os.path.join(HERE, "csrc", "forest_posterior_hip.hip"), os.path.join(HERE, "csrc", "soft_modes_hip.hip")],
             [os.path.join(HERE, "..", "include", "rdf_labels.h"), os.path.join(HERE, "csrc", "rdf_kernel_util.hpp"),
              os.path.join(HERE, "csrc", "rdf_raster.hpp"), os.path.join(HERE, "csrc", "rdf_device.hpp"),
              os.path.join(HERE, "csrc", "rdf_modes.hpp")], "rdf_labels_"),

@@ -228,6 +228,10 @@ BINDINGS = {
         "rdf_labels_refit_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
         "rdf_labels_refit_apply": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, ctypes.c_uint64, _c_int, _c_void_p,
                                             _c_void_p, _c_void_p]),
+        "rdf_labels_prune_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int]),
+        "rdf_labels_prune_plan": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, ctypes.c_uint64, ctypes.c_uint64, _c_int,
+                                           _c_void_p, _c_void_p, _c_void_p]),
+        "rdf_labels_prune_apply": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
         "rdf_labels_forest_posterior": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p,
                                                  _c_int, _c_int, _c_float, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
         "rdf_labels_confidence_counts": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p,

@@ -265,9 +265,39 @@ def refit_saved_model(model_path, dataset_dir, num_images, out_path, min_count=1
     return report
 
 
+def _prune_on_dataset(forest, dataset_dir, num_images, cost_per_leaf, min_count, max_levels, truncate):
+    """Prune `forest` (a DecisionForest) on `num_images` random images of a dataset directory (0: all of them); returns (the
+    pruned forest -- `forest` itself, or with `truncate` the shallower one that is left --, the ForestPruner's report)."""
+    from .device import DeviceArray
+    from .prune import ForestPruner
+    num_images = num_images or DecisionTreeDatasetConfig(dataset_dir).total_available_images
+    ds = DecisionTreeDatasetConfig(dataset_dir, num_images=num_images, imgs_name='prune')
+    assert ds.num_classes() <= int(forest.num_classes), "the dataset has classes the forest does not have"
+    depth, labels = DeviceArray(ds.images_shape(), np.uint16), DeviceArray(ds.images_shape(), np.uint16)
+    ds.get_depth_block_cu(0, depth)
+    ds.get_labels_block_cu(0, labels)
+    pruner = ForestPruner(forest).add(depth, labels)
+    report = pruner.plan(cost_per_leaf, min_count, max_levels)
+    pruner.apply()
+    return (pruner.truncated() if truncate else forest), report
+
+
+def prune_saved_model(model_path, dataset_dir, num_images, out_path, cost_per_leaf=0, min_count=0, max_levels=None, truncate=True):
+    """Reduced-error pruning of a saved forest (prune.ForestPruner) on `num_images` random images (0: all) of a dataset directory
+    -- frames the trainer has not seen --, read as score_saved_model reads them, and saved as the reference's .npy at `out_path`:
+    with `truncate` at the depth that is left, which the loader infers from the shape, else at the model's own depth with
+    records of zeros below the folded subtrees.  Returns the report of ForestPruner.plan."""
+    from .decision_tree import DecisionForest
+    forest = DecisionForest.load(model_path)
+    pruned, report = _prune_on_dataset(forest, dataset_dir, num_images, cost_per_leaf, min_count, max_levels, truncate)
+    np.save(out_path, pruned.forest_cu.get())
+    return report
+
+
 def train_forest(dataset_dir, num_train, num_test, proposals, proposals_block, out_trees, max_depth, out_path=None,
                  trees_to_try=None, train_block=None, log=print, tree_seed=None, group=None, device_score=False,
-                 refit_dir=None, refit_images=0, refit_min_count=1, refit_fallback='keep'):
+                 refit_dir=None, refit_images=0, refit_min_count=1, refit_fallback='keep',
+                 prune_dir=None, prune_images=0, prune_cost=0, prune_min_count=0, prune_max_levels=None):
     """The flow of src/train_model.py:52-139 without its GLFW window: train `trees_to_try` candidate trees, keep
     the `out_trees` best by test accuracy, evaluate the forest, save it as the reference's .npy.
 
@@ -285,7 +315,13 @@ def train_forest(dataset_dir, num_train, num_test, proposals, proposals_block, o
     refit_dir (not in the reference): the finished forest's leaf PDFs are re-estimated on `refit_images` random images (0: all) of that
     dataset directory (refit.LeafRefitter, with refit_min_count and refit_fallback) before the forest is scored and saved:
     train on clean renders, refit on what the camera reports.  The candidates are selected as trained.  Without it nothing
-    changes."""
+    changes.
+
+    prune_dir (not in the reference): after the optional refit and before the forest is scored and saved, it is pruned on
+    `prune_images` random images (0: all) of that dataset directory -- frames the trainer has not seen -- by prune.ForestPruner
+    with prune_cost a leaf, prune_min_count and prune_max_levels (its cost_per_leaf, min_count and max_levels), and cut to the
+    depth D' that is left: the returned array and the saved .npy have depth D', which the loader infers from the shape, and the
+    score is the pruned forest's.  The candidates are selected as trained.  Without it nothing changes."""
     from .decision_tree import DecisionForest, DecisionTree, DecisionTreeEvaluator, DecisionTreeTrainer
     from .device import DeviceArray
     from .util import MAX_UINT16
@@ -349,6 +385,12 @@ def train_forest(dataset_dir, num_train, num_test, proposals, proposals_block, o
         forest_cpu = forest.forest_cu.get()
         log(f'refit on {refit_images or "all"} images: {report["own"]} of {report["leaf_slots"]} leaf slots from their own counts, '
             f'{report["ancestor"]} from an ancestor, {report["kept"]} kept')
+    if prune_dir is not None:
+        forest, report = _prune_on_dataset(forest, prune_dir, prune_images, prune_cost, prune_min_count, prune_max_levels, True)
+        forest_cpu = forest.forest_cu.get()
+        log(f'pruned on {prune_images or "all"} images: {report["leaf_slots_before"]} -> {report["leaf_slots_after"]} leaf slots, '
+            f'depth {report["depth"]}, errors of the trees alone {report["errors_before"]} -> {report["errors_after"]} of '
+            f'{report["pixels"]} walks')
     out_cu.fill(MAX_UINT16)
     evaluator.get_labels_forest(forest, test_depth, out_cu)
     if device_score:

@@ -16,6 +16,8 @@
  * pattern, a census transform and a block matcher, integer like the colour kernels.
  * And the leaf refit (rdf_labels_refit_count, rdf_labels_refit_apply): a trained forest's leaf distributions re-estimated
  * from labelled frames, in integer counts.
+ * And the pruning of such a forest on those counts (rdf_labels_prune_plan, rdf_labels_prune_apply): subtrees that label held-out
+ * frames no better than one leaf are folded into one.
  * And what the forest knows beyond its argmax (rdf_labels_forest_posterior, rdf_labels_confidence_counts): per-pixel class
  * sums, a confidence, a reject option and a reliability histogram.
  *
@@ -52,7 +54,7 @@ extern "C" {
 /*
  * 1: first version.  The number changes when something declared here is removed or re-typed; a pure addition (as
  * rdf_points_center, rdf_rerender, rdf_hand_scene_render and the pose fit -- rdf_pose_cost, rdf_pose_propose, rdf_pose_select,
- * rdf_pose_fit_workspace_bytes and rdf_pose_fit --, the stereo sensor's three, the leaf refit's three and the forest posterior's two were) keeps it, since every caller of the older entry points still links and runs.
+ * rdf_pose_fit_workspace_bytes and rdf_pose_fit --, the stereo sensor's three, the leaf refit's three, the forest posterior's two and the pruning's three were) keeps it, since every caller of the older entry points still links and runs.
  * Two builds with the same number are told apart by rdf_labels_build_id().
  */
 #define RDF_LABELS_ABI_VERSION 1
@@ -538,6 +540,56 @@ int rdf_labels_refit_count(const uint16_t *depth, const uint16_t *labels, int n_
 size_t rdf_labels_refit_workspace_bytes(int n_trees, int max_depth, int n_classes);
 int rdf_labels_refit_apply(float *forest, int n_trees, int max_depth, int n_classes, const uint64_t *counts, uint64_t min_count,
                            int fallback, void *workspace, uint64_t *report, void *stream);
+
+/*
+ * Pruning: reduced-error (cost-complexity) pruning of a trained forest on held-out counts.  The trainer grows every tree until
+ * a side is pure or the depth is used up; a subtree that a handful of training pixels asked for costs a dependent node fetch
+ * per level and gives the least reliable leaves.  rdf_labels_prune_plan decides, from the counts of rule R2 taken on frames the
+ * trainer has not seen, which subtrees label those frames no better than one leaf would; rdf_labels_prune_apply folds them.
+ * The reference has no counterpart; the rules below are this library's own, tests/prune_numpy.py restates them, and the kernels
+ * match that bit for bit.  Layout, leaf slot, the floor of a flag, "reachable" and sub[t][a][c] are those of the leaf refit
+ * above.  level(n) = floor(log2(n + 1)); node n has the children 2n + 1 + s.  All arithmetic is in unsigned 64-bit integers
+ * except the final PDFs.  Parameters: 0 <= cost_per_leaf < 2^32, min_count >= 0, 1 <= max_levels <= D.
+ *
+ * P1. A leaf slot's error.  For a leaf slot (t, n, s) with counts cnt[c] and S their sum, k* is the argmax of the slot's current
+ *     PDF by the evaluator's rule: start at 0.0f, strict >, the first index wins, NaN never wins, none above 0 gives class 0.
+ *     err_slot = S - cnt[k*].
+ * P2. Bottom-up, per node a.  For each side s: a leaf slot gives e_s = err_slot, l_s = 1; else, if the child c = 2a + 1 + s
+ *     exists and collapse(c), e_s = Z(c) - max_k sub[c][k], l_s = 1; else, if the child exists, e_s = err(c), l_s = leaves(c);
+ *     else (a "go on" at level D - 1, where walks fall off) e_s = 0, l_s = 0.  err(a) = e_0 + e_1, leaves(a) = l_0 + l_1; errB(a)
+ *     and leavesB(a) are the same recursion with no collapse anywhere.  Z(a) = sum_k sub[a][k], err_leaf(a) = Z(a) - max_k
+ *     sub[a][k].  collapse(a) is true iff a is not the root and level(a) >= max_levels, or Z(a) < min_count, or
+ *     err_leaf(a) <= err(a) + cost_per_leaf * max(leaves(a) - 1, 0).  Note the <=: a tie collapses.
+ * P3. Top-down (rdf_labels_prune_apply).  Reachability is made again on the way down: the root is reachable; for a reachable
+ *     node n and a "go on" side s whose child c exists, if collapse(c) then rec[5 + s] := +0.0f, the side's PDF becomes
+ *     (float)sub[a][k] / (float)Z(a) -- uint64 to fp32 rounded to nearest even, one IEEE divide -- with a the nearest of c,
+ *     parent(c), ..., root that has Z(a) >= 1, or all +0.0f if there is none, and counts[t][n][s][:] := sub[c][:]; else c is
+ *     reachable.  After the call every node that is not reachable has a record of all +0.0f and counts of 0.  rec[0..4] of
+ *     reachable nodes, PDFs of leaf slots that were leaf slots before, and "go on" flags at level D - 1 keep their bytes.  Where
+ *     the counts were 0 outside reachable leaf slots (as rule R2 leaves them), their sum is unchanged.
+ * P4. report uint64 [8], written by the plan: [0] reachable leaf slots before, [1] after, [2] "go on" slots turned into leaf
+ *     slots, [3] the new depth D' = 1 + the deepest level that holds a reachable node after, [4] sum_t errB(root), [5] sum_t
+ *     err(root), [6] sum_t Z(root), [7] reachable nodes after.  The first 2^D' - 1 records of each tree are a forest of depth D'
+ *     that labels every pixel as the pruned one does.
+ *
+ * rdf_labels_prune_plan reads forest and counts and writes workspace and report; it may be called any number of times, with
+ * other parameters, before one rdf_labels_prune_apply, which uses the workspace of the last plan and must be given the forest
+ * and counts that plan read, unchanged.  workspace: rdf_labels_prune_workspace_bytes(T, D, C) bytes (0 for a rejected shape),
+ * 8-byte aligned, contents irrelevant before a plan.  After a plan it begins with one byte per node, uint8 [T][N]: bit 0
+ * reachable before, bit 1 collapse(n) (made for the nodes reachable before only), bit 2 reachable after.  A shape outside the
+ * ranges of the leaf refit, cost_per_leaf >= 2^32, max_levels outside 1..D or a misaligned pointer (4 bytes for forest, 8 for
+ * the others) is RDF_ERR_BAD_ARG, else a NULL pointer RDF_ERR_NULL_PTR; nothing is launched then and every buffer keeps its
+ * bytes.  Stream-ordered, nothing read back.  A plan is four launches and two memsets whatever the depth: the levels with T *
+ * 2^j <= 1024 are swept by one workgroup with a barrier between levels, in both directions; every node of the first level
+ * below them roots a subtree that one workgroup sweeps the same way.  apply is two launches.  A packed table made of this
+ * forest (rdf_forest_pack) holds the old tree: pack again.
+ */
+size_t rdf_labels_prune_workspace_bytes(int n_trees, int max_depth, int n_classes);
+int rdf_labels_prune_plan(const float *forest, int n_trees, int max_depth, int n_classes, const uint64_t *counts,
+                          uint64_t cost_per_leaf, uint64_t min_count, int max_levels, void *workspace, uint64_t *report,
+                          void *stream);
+int rdf_labels_prune_apply(float *forest, int n_trees, int max_depth, int n_classes, uint64_t *counts, const void *workspace,
+                           void *stream);
 
 /*
  * Forest posteriors: what rdf_eval_forest sums per pixel and discards.  rdf_labels_forest_posterior evaluates a forest as
