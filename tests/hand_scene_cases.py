@@ -15,10 +15,18 @@ Frames differ in every part's transform and in the table, so a wrong frame strid
 
 `case`              the scene at the SIZES, one and MAX_FRAMES frames, under every row of VARIANTS.
 `many_frames_case`  the same mesh at 16 x 13 in 65541 frames that cycle through seven settings of the transforms and tables
-                    (`part_tforms_cycle`, `tables_cycle`): more frames than k_hand_raster's grid has rows."""
+                    (`part_tforms_cycle`, `tables_cycle`): more frames than k_hand_raster's grid has rows.
+`OWN_CASES`         one rule of T, E and H each on a 16 x 16 frame; `grid_case` draws rerender_cases.GRID_CASES as meshes.
+
+MUTANTS names wrong readings of the rules, `mutant(name)` loads tests/hand_scene_numpy.py with that reading (tests/mutants.py),
+KILLS says which device case must notice which, EQUIVALENT which readings no input can tell from the rule, and why."""
+import functools
+
 import numpy as np
 
 import hand_scene_numpy as hs
+import mutants
+import rerender_cases as rc
 
 F = np.float32
 FOCAL = 64.
@@ -135,3 +143,143 @@ def case(W, H):
                                                  geometry=geometry[:n_frames])
         _cases[W, H] = {"cam": cam, "mesh": m, "tforms": t, "tables": tables(), "geometry": geometry, "want": want}
     return _cases[W, H]
+
+
+# ------------------------------------------------------------------ one rule each ---------------------------------------------
+# OWN_CASES: what rdf_hand_scene_render has beyond the shared rasteriser (rules T, E and H) on a 16 x 16 frame with focal
+# length 64, one mesh quad at depth 512 (screen 2.5 .. 10.5 by 3.5 .. 11.5: pixels 2 .. 9 by 3 .. 10, its edges on pixel
+# centres) and tables that face the camera, (0, 0, 1, d): t = 1 and zt = d exactly at every pixel.  The rasteriser's own
+# cases are rerender_cases.GRID_CASES, drawn here as meshes (`grid_case`).
+OWN_SIZE, OWN_CAM = (16, 16), (FOCAL, 7.5, 7.25)
+QUAD_PIXELS = (slice(3, 11), slice(2, 10))
+
+
+def _own_mesh():
+    pts, _ = rc.grid(16, 16, OWN_CAM, rc.lattice((2.5, 10.5), (3.5, 11.5), 512.))
+    return rc.as_mesh(pts)
+
+
+def _facing(*d):
+    return np.array([(0., 0., 1., v) for v in d], np.float32)
+
+
+def _own_cases():
+    out = {}
+
+    def add(name, tables, zmin=50., zmax=50000., empty=0, seed=SEED, holes=0, noise=0):
+        out[name] = {"W": 16, "H": 16, "cam": OWN_CAM, "mesh": _own_mesh(), "tables": tables, "zmin": zmin, "zmax": zmax, "empty": empty,
+                     "tforms": np.tile(np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], np.float32), (len(tables), 1, 1)),
+                     "seed": seed, "holes": holes, "noise": noise}
+    add("quad coplanar with the table", _facing(512.))
+    add("tables at the ends of the depth range", _facing(1024., rc.ULP_UP(1024.), 256., rc.ULP_DOWN(256.)), zmin=256., zmax=1024., empty=7)
+    # the threshold is the hash of one drawn pixel of frame 0, the median one: it stays, every pixel with a smaller hash goes
+    h = hs.hashes(SEED, 0, 256)[0]
+    add("hole threshold on a pixel's own hash", _facing(1024., 1024.), holes=int(np.sort(h)[128]))
+    add("noise against both clamps", _facing(2., 65533.), zmin=1., zmax=70000., noise=5)
+    return out
+
+
+OWN_CASES = _own_cases()
+
+
+def grid_case(name):
+    """rerender_cases.GRID_CASES[name] as rdf_hand_scene_render's arguments: no table, empty depth 0, one frame."""
+    c = rc.GRID_CASES[name]
+    return {"W": c["W"], "H": c["H"], "cam": c["cam"], "mesh": rc.as_mesh(c["pts"]), "tables": None, "zmin": c["zmin"], "zmax": c["zmax"],
+            "empty": 0, "tforms": np.ascontiguousarray(c["M"][:3]).reshape(1, 1, 12), "seed": 0, "holes": 0, "noise": 0,
+            "depth": c["depth"]}
+
+
+def render_of(mod, c):
+    """(depth, labels) of an OWN_CASES or grid_case record under the module `mod`."""
+    with np.errstate(all="ignore"):
+        return mod.render(c["W"], c["H"], *c["mesh"], c["tforms"], c["tables"], *c["cam"], c["zmin"], c["zmax"], c["empty"], c["seed"],
+                          c["holes"], c["noise"])[:2]
+
+
+_wants = {}
+
+
+def want_of(name):
+    """The restatement's (depth, labels) of a case of OWN_CASES or, as "grid: <name>", of rerender_cases.GRID_CASES."""
+    if name not in _wants:
+        _wants[name] = render_of(hs, grid_case(name[6:]) if name.startswith("grid: ") else OWN_CASES[name])
+    return _wants[name]
+
+
+# ------------------------------------------------------------------ mutants ---------------------------------------------------
+# rerender_cases.FRAGMENT_EDITS reach this restatement through the functions it imports; VERTEX_EDITS apply to its own
+# `vertices`, which spells rule 3 as rerender_numpy does.  Its own spelling of rule 2's rows and rules V, T, E and H:
+OWN_EDITS = {
+    "vertex rows contracted": [("xt, yt, zt = (((m[:, 4 * r] * x + m[:, 4 * r + 1] * y) + m[:, 4 * r + 2] * z) + m[:, 4 * r + 3] for r in range(3))",
+                                "xt, yt, zt = (_fma(m[:, 4 * r + 2], z, _fma(m[:, 4 * r], x, m[:, 4 * r + 1] * y)) + m[:, 4 * r + 3] for r in range(3))")],
+    "a part out of range read as part 0": [("ok = known & (zt > 0)", "ok = (zt > 0)")],
+    "table against mesh tie read as <": [("~(zm <= zt)", "~(zm < zt)")],
+    "table zmin exclusive": [("(zt >= F(zmin))", "(zt > F(zmin))")],
+    "table zmax exclusive": [("(zt <= F(zmax))", "(zt < F(zmax))")],
+    "table without a depth range": [("there = (t > 0) & (zt >= F(zmin)) & (zt <= F(zmax))", "there = (t > 0) & (zt == zt)")],
+    "table t >= 0": [("there = (t > 0) &", "there = (t >= 0) &")],
+    "table ray without the + 0.5": [("(i.astype(np.float32) + F(0.5))", "i.astype(np.float32)"), ("(j.astype(np.float32) + F(0.5))", "j.astype(np.float32)")],
+    "table of frame 0 in every frame": [(".reshape(-1, 4)[n]", ".reshape(-1, 4)[0]")],
+    "hole test read as <=": [("(h < U32(hole_threshold))", "(h <= U32(hole_threshold))")],
+    "a hole keeps its label": [("labels[n] = np.where(drawn, lab, 0)", "labels[n] = lab")],
+    "hash ignores the frame": [("h, h2 = hashes(seed, n, n_px)", "h, h2 = hashes(seed, 0, n_px)")],
+    "noise clamped at 0": [("- noise_amp, 1, 65534)", "- noise_amp, 0, 65534)")],
+    "noise clamped at 65535": [("- noise_amp, 1, 65534)", "- noise_amp, 1, 65535)")],
+    "noise on an empty pixel": [("depth[n] = np.where(drawn, d, empty_depth)", "depth[n] = np.where(drawn | (noise_amp > 0), d, empty_depth)")],
+    "stored depth rounded": [("np.minimum(np.trunc(z), F(65535))", "np.minimum(np.floor(z + F(0.5)), F(65535))")],
+}
+EDITS = {**OWN_EDITS, **rc.VERTEX_EDITS}
+MUTANTS = tuple(rc.FRAGMENT_EDITS) + tuple(EDITS)
+
+EQUIVALENT = {
+    "z' >= 0 drawable": rc.EQUIVALENT["z' >= 0 drawable"],
+    "a triangle of area 0 kept": rc.EQUIVALENT["a triangle of area 0 kept"],
+    "table t >= 0": "t = +-0 makes zt = d / t an infinity, or a NaN where d is 0 or NaN: zt <= zmax fails for +inf and NaN, "
+                    "zmin <= zt for -inf, so there is no table at that pixel under either reading.",
+}
+
+
+@functools.lru_cache(maxsize=None)
+def mutant(name=None):
+    """tests/hand_scene_numpy.py under one wrong reading; without a name the unchanged copy, drawing with an unchanged copy
+    of rerender_numpy's functions."""
+    r = rc.mutant(name if name in rc.FRAGMENT_EDITS else None)
+    mod = mutants.load("hand_scene_numpy", EDITS.get(name, ()) if name else (), fragments=r.fragments, resolve=r.resolve,
+                       depth_key=r.depth_key)
+    # an edit of rules T, E or H stands in `render` and `table_depth` alone: `rasterise` is the restatement's, text for text
+    mod.RASTERISES_ALIKE = name in OWN_EDITS and name not in ("vertex rows contracted", "a part out of range read as part 0")
+    return mod
+
+
+# device case -> the mutants it must kill.  "scene 33 x 17" is the hand-built scene under every row of VARIANTS;
+# "grid: <name>" a rasteriser case of rerender_cases.GRID_CASES as a mesh; every other key is one of OWN_CASES.
+KILLS = {
+    "scene 33 x 17": ("no fill rule: every edge in", "no fill rule: every edge out", "left edge read as D.Y > 0",
+                      "q summed in another order", "box one pixel short on the right", "box one pixel short at the top",
+                      "column 0 outside the box", "depth ties to the highest id", "farthest fragment wins", "one winding only",
+                      "a part out of range read as part 0", "table ray without the + 0.5", "table of frame 0 in every frame",
+                      "a hole keeps its label", "hash ignores the frame", "noise on an empty pixel", "stored depth rounded",
+                      "snap by truncation", "snap without the + 0.5"),
+    "grid: edges on pixel centres": ("top edge read as D.X < 0", "no fill rule: every edge in", "no fill rule: every edge out",
+                                     "left edge read as D.Y > 0"),
+    "grid: folded back at one depth": ("depth ties to the highest id",),
+    "grid: surface at zmin": ("zmin exclusive",),
+    "grid: surface at zmax": ("zmax exclusive",),
+    "grid: surface one float below zmin": ("no depth range",),
+    "grid: surface one float above zmax": ("no depth range",),
+    "grid: x snapped to +2^20": ("|X| <= 2^20 read as <",),
+    "grid: x snapped to -2^20": ("|X| <= 2^20 read as <",),
+    "grid: y snapped to +2^20": ("|Y| <= 2^20 read as <",),
+    "grid: y snapped to -2^20": ("|Y| <= 2^20 read as <",),
+    "grid: x snapped to +(2^20 + 1)": ("no limit on |X|",),
+    "grid: x snapped to -(2^20 + 1)": ("no limit on |X|", "behind the camera drawable"),
+    "grid: y snapped to +(2^20 + 1)": ("no limit on |Y|",),
+    "grid: y snapped to -(2^20 + 1)": ("no limit on |Y|",),
+    "grid: rows that a contraction would snap elsewhere": ("vertex rows contracted",),
+    "grid: sums that another order would round elsewhere": ("w summed in another order", "q summed in another order"),
+    "quad coplanar with the table": ("table against mesh tie read as <",),
+    "tables at the ends of the depth range": ("table zmin exclusive", "table zmax exclusive", "table without a depth range"),
+    "hole threshold on a pixel's own hash": ("hole test read as <=",),
+    "noise against both clamps": ("noise clamped at 0", "noise clamped at 65535"),
+}

@@ -13,6 +13,7 @@ surface at Z = fB / d, the right render is the left one moved by exactly d colum
 `variant_case`      the second GPU shape under each row of CONFIG_VARIANTS: every field of the config away from its default,
                     one at a time, and rule I's numerator at its 32-bit limit.
 `box_case`          the `box` with sn.sense's record of its one frame.
+`column0_case`      a 9 x 5 frame in which a disparity beyond the left border wins at column 0: x - d* = -1.
 Every expected result is computed once and shared."""
 import numpy as np
 
@@ -170,3 +171,34 @@ def box_case():
         depth_l, labels, depth_r, cfg = box()
         _cache["box"] = {"in": (depth_l, labels, depth_r), "cfg": cfg, "want": sn.sense(depth_l, labels, depth_r, cfg, keep=True)}
     return _cache["box"]
+
+
+# ------------------------------------------------------------------ a winner left of the right image -------------------------
+# Rule W's left-right check asks x - d* >= 0 first.  The box of a d = x + 1 holds at least 15 cells of 62, and in no other
+# case of this module does such a d win at a pixel that is otherwise valid.  These two renders (found by a seeded
+# hill-climb on the CPU over per-pixel depths; dense dots, no census margin, no noise) make d* = 1 win at pixel (0, 4),
+# uniquely and with dq >= dq_min: the pixel fails the check for x - d* = -1 alone.  lr_max = 255, so a kernel that went on
+# to compare dR at a clamped column would pass it.
+COLUMN0_PIXEL = (4, 0)               # (y, x)
+COLUMN0_LEFT = ((12000, 2000, 4000, 12000, 5000, 2000, 1500, 6000, 2500),
+                (16000, 4000, 5000, 1500, 16000, 2000, 12000, 4000, 8000),
+                (16000, 0, 16000, 12000, 6000, 12000, 32000, 2500, 6000),
+                (65535, 6000, 65535, 3500, 12000, 2000, 3000, 65535, 2500),
+                (0, 12000, 65535, 2000, 6000, 32000, 12000, 0, 3000))
+COLUMN0_RIGHT = ((3500, 32000, 16000, 32000, 6000, 2500, 8000, 5000, 8000),
+                 (32000, 2500, 4000, 4000, 8000, 3500, 2000, 65535, 16000),
+                 (12000, 3500, 65535, 8000, 3000, 16000, 16000, 0, 0),
+                 (2000, 0, 2500, 2000, 4000, 12000, 3000, 1500, 65535),
+                 (2000, 65535, 12000, 12000, 16000, 12000, 3000, 32000, 8000))
+
+
+def column0_case():
+    """gpu_case's record (with sn.sense's "frames") of the 9 x 5 frame above, every pixel labelled 3."""
+    if "column 0" not in _cache:
+        depth_l, depth_r = np.array([COLUMN0_LEFT], np.uint16), np.array([COLUMN0_RIGHT], np.uint16)
+        labels = np.full(depth_l.shape, 3, np.uint16)
+        cfg = sn.config(64000, 25600, max_disparity=4, dot_threshold=0xC0000000, pattern_seed=988811432, ambient=64, ir_noise_amp=0,
+                        census_margin=0, uniqueness=0, lr_max=255, dq_min=1)
+        _cache["column 0"] = {"in": (depth_l, labels, depth_r), "cfg": cfg,
+                              "want": sn.sense(depth_l, labels, depth_r, cfg, seed=SEED, empty_depth=EMPTY, keep=True)}
+    return _cache["column 0"]

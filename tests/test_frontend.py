@@ -10,8 +10,10 @@ import subprocess
 import numpy as np
 import pytest
 
+import frontend_cases as fc
 import frontend_numpy as fnp
 import grouping_numpy as gnp
+import mutants
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "frontend_v1.npz")
@@ -123,6 +125,69 @@ def test_gaussian_restatement_ties_corners_and_saturation():
     assert fnp.float2uint_rd(np.array([np.nan, -3.5, 65536.7, 1e20], np.float32)).tolist() == [0, 0, 65536, 4294967295]
     # uint32 -> uint16 keeps the low bits: a quotient that rounds up to 65536 wraps to 0
     assert fnp.gaussian(np.array([[65535]], np.uint16), np.array([[np.float32(1.0000001)]], np.float32)).dtype == np.uint16
+
+
+# ------------------------------------------------------------------ CPU: do the device cases bite? --------------------------
+_true_outputs = {}
+
+
+def _true(name):
+    if name not in _true_outputs:
+        _true_outputs[name] = fc.outputs(fnp, name)
+    return _true_outputs[name]
+
+
+def test_the_unchanged_copy_is_the_restatement_bit_for_bit():
+    copy = fc.mutant()
+    assert copy is not fnp and copy.frame_front is not fnp.frame_front
+    for name in fc.KILLS:
+        assert mutants.same(fc.outputs(copy, name), _true(name)), name
+
+
+def test_a_mutant_that_no_longer_applies_fails_loudly():
+    with pytest.raises(AssertionError, match="0 times"):
+        mutants.load("frontend_numpy", [("np.where(w_0 > wn, 0,", "np.where(w_0 >= wn, 0,")])
+    with pytest.raises(AssertionError, match="2 times"):
+        mutants.load("frontend_numpy", [("pts[..., 3] == 1", "pts[..., 3] != 0")])
+
+
+@pytest.mark.parametrize("name", list(fc.KILLS))
+def test_each_mutant_changes_the_case_meant_for_it(name, capsys):
+    """A wrong reading of a rule that leaves a case's outputs unchanged would pass the GPU test of that case."""
+    killed = {m: mutants.changed(fc.outputs(fc.mutant(m), name), _true(name)) for m in fc.MUTANTS}
+    with capsys.disabled():
+        print(f"\n  {name}: outputs changed by " + ", ".join(f"{m}: {k}" for m, k in killed.items() if k), end="")
+    for m in fc.KILLS[name]:
+        assert killed[m] > 0, (name, m)
+
+
+def test_every_mutant_is_met_by_some_case():
+    assert set(m for ms in fc.KILLS.values() for m in ms) == set(fc.MUTANTS) and not fc.EQUIVALENT
+    names = list(fc.CHAIN_PLANES) + [t[0] for t in fc.TIES] + [f"shape {W} x {H}" for W, H in fc.SHAPES] + list(fc.SELECT_COUNTS)
+    assert set(fc.KILLS) == set(names) | {"inlier edge points"}
+
+
+def test_the_small_cases_hold_what_they_name():
+    for name in fc.CHAIN_PLANES:                        # the chain's images worked by hand
+        depth, pts = _true(name)[:2]
+        assert np.array_equal(depth, fc.CHAIN_WANT_DEPTH[name]) and _eq(pts, fc.chain_want_points(name)), name
+    lift = fc.CHAIN_PLANES["last row (0, 0, 0, 1), z' on -T"]
+    z = fnp.transform_xyzw(lift, np.float32(0), np.float32(0), np.float32([60, 61]), np.float32(1))[2]
+    assert z.tolist() == [-fc.T, -fc.T + 1] and fc.CHAIN_DEPTH.shape == (3, 3, 5)
+    for name, want in fc.TIES_WANT.items():
+        assert _true(name)[0].tolist() == want and _true(name)[1][0].tolist() == want, name
+    for W, H in fc.SHAPES:
+        depth, plane = fc.shape_case(W, H)
+        clean = fnp.frame_front(depth, *fc.SHAPE_CAM, plane, fc.T)[0]
+        assert (W * H) % 2 == 1 and depth.shape == (3, H, W) and (W * H == 1 or 0.2 < (clean > 0).mean() < 0.7 * (depth > 0).mean())
+    assert any(W < 32 and H < 8 for W, H in fc.SHAPES) and any(W < 20 and H < 20 and H > 8 for W, H in fc.SHAPES)
+    for name, (best, count, status) in fc.SELECT_WANT_BEST.items():
+        plane, got = _true(name)[:2]
+        assert got.tolist() == [best, count, status], name
+        assert plane.tolist() == ([1., 0., 0., 0., best, 1., 0., 0., 0., 0., 2., -8., 0., 0., 0., 1.] if status == 0 else [5.] * 16), name
+    counts = fc.SELECT_COUNTS["equal best counts at 300, 520 and 599"]
+    assert np.nonzero(counts == counts.max())[0].tolist() == [300, 520, 599] and len({300 % 256, 520 % 256, 599 % 256}) == 3
+    assert _true("inlier edge points")[0].tolist() == fc.INLIER_WANT
 
 
 def test_candidate_draws_misses_duplicates_and_start_mat():
@@ -311,16 +376,9 @@ def test_candidates_counts_and_plane_match_the_restatement(G, H, W, rdf, gpu_run
 
 @pytest.mark.gpu
 def test_inlier_kernel_edge_points(rdf, gpu_runtime):
-    M = np.eye(4, dtype=np.float32).reshape(16)
-    pts = np.array([[0, 0, T, 1], [0, 0, -T, 1], [0, 0, np.nextafter(np.float32(T), 0), 1], [0, 0, -39.5, 1],
-                    [0, 0, 0, 2], [0, 0, 0, 0], [np.nan, 0, 0, 1], [0, np.inf, 0, 1]], np.float32)
-    far = M.copy()
-    far[11] = 1e6
-    nan = np.full(16, np.nan, np.float32)
-    cand = np.stack([M, far, nan, M])
-    init = np.array([0, 5, -1, 3], np.int32)
+    pts, cand, init = fc.inlier_case()
     got = _inliers_on_device(rdf, pts, cand, init)
-    assert got.tolist() == fnp.plane_inliers(pts, cand, T, init).tolist() == [2, 5, -1, 5]
+    assert got.tolist() == fnp.plane_inliers(pts, cand, T, init).tolist() == fc.INLIER_WANT == [2, 5, -1, 5]
 
 
 @pytest.mark.gpu
@@ -367,6 +425,99 @@ def test_frame_front_matches_the_chain_and_the_restatement(n, rdf, gpu_runtime):
     assert fe.rdf_frame_front(d.ptr, n, W, H, fpp[1], fpp[2], fpp[0], M.ptr, T, wd.ptr, 41, d.ptr, None, s) == -1
     assert fe.rdf_frame_front(d.ptr, n, W, H, fpp[1], fpp[2], fpp[0], M.ptr, T, wd.ptr, 43, out.ptr, None, s) == -1
     assert fe.rdf_frame_front(None, n, W, H, fpp[1], fpp[2], fpp[0], M.ptr, T, None, 0, out.ptr, None, s) == -2
+
+
+def _front(rdf, depth, cam, plane, w, with_pts):
+    """rdf_frame_front on `depth` [n, H, W]: (depth_out, pts_out or None), every output pre-filled with what no pixel gets."""
+    fe, s = _fe(), rdf.get_runtime().stream()
+    n, H, W = depth.shape
+    d, M = rdf.to_device(np.ascontiguousarray(depth)), rdf.to_device(np.ascontiguousarray(plane, np.float32))
+    wd = None if w is None else rdf.to_device(np.ascontiguousarray(w, np.float32))
+    out = rdf.DeviceArray(depth.shape, np.uint16).fill(1)
+    pts = rdf.DeviceArray(depth.shape + (4,), np.float32).fill(9) if with_pts else None
+    rc = fe.rdf_frame_front(d.ptr, n, W, H, *(float(v) for v in cam), M.ptr, fc.T, None if wd is None else wd.ptr,
+                            0 if w is None else len(w), out.ptr, pts.ptr if with_pts else None, s)
+    assert rc == 0
+    assert np.array_equal(d.get(), depth)
+    return out.get(), (pts.get() if with_pts else None)
+
+
+def _gauss(rdf, frame, w):
+    """rdf_gaussian_depth_filter on one frame [H, W]."""
+    fe, s = _fe(), rdf.get_runtime().stream()
+    H, W = frame.shape
+    d, wd = rdf.to_device(np.ascontiguousarray(frame)), rdf.to_device(np.ascontiguousarray(w, np.float32))
+    out = rdf.DeviceArray((H, W), np.uint16).fill(1)
+    assert fe.rdf_gaussian_depth_filter(W, H, len(w), wd.ptr, d.ptr, out.ptr, s) == 0
+    return out.get()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(fc.CHAIN_PLANES))
+def test_frame_front_on_planes_whose_last_row_decides(name, rdf, gpu_runtime):
+    plane = fc.CHAIN_PLANES[name]
+    for w in (None, fc.UNIFORM3):
+        want_d, want_p = fnp.frame_front(fc.CHAIN_DEPTH, *fc.CHAIN_CAM, plane, fc.T, w)
+        for with_pts in (True, False):
+            got_d, got_p = _front(rdf, fc.CHAIN_DEPTH, fc.CHAIN_CAM, plane, w, with_pts)
+            print(f"{name}, Gaussian {'off' if w is None else 'on'}, pts_out {'given' if with_pts else 'NULL'}: "
+                  f"{int((got_d != want_d).sum())} depths differ")
+            if w is None:                               # worked by hand
+                assert np.array_equal(got_d, fc.CHAIN_WANT_DEPTH[name]), name
+            assert _eq(got_d, want_d), (name, w is None, with_pts)
+            if with_pts:
+                assert _eq(got_p, fc.chain_want_points(name)) and _eq(got_p, want_p), (name, w is None)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,frame,w", fc.TIES, ids=[t[0] for t in fc.TIES])
+def test_gaussian_ties_corners_and_saturation_through_both_entry_points(name, frame, w, rdf, gpu_runtime):
+    want = fnp.gaussian(frame, w)
+    alone = _gauss(rdf, frame, w)
+    fused, _ = _front(rdf, frame[None], fc.CHAIN_CAM, fc.FAR_BELOW, w, True)
+    print(f"{name}: {int((alone != want).sum())} pixels differ alone, {int((fused[0] != want).sum())} fused")
+    if name in fc.TIES_WANT:                            # worked by hand
+        assert alone.tolist() == fc.TIES_WANT[name] and fused[0].tolist() == fc.TIES_WANT[name]
+    assert _eq(alone, want) and _eq(fused[0], want)
+    assert _eq(fused, fnp.frame_front(frame[None], *fc.CHAIN_CAM, fc.FAR_BELOW, fc.T, w)[0])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("W,H", fc.SHAPES)
+def test_frame_front_on_frames_smaller_than_a_tile_and_than_the_filter(W, H, rdf, gpu_runtime):
+    depth, plane = fc.shape_case(W, H)
+    clean = fnp.frame_front(depth, *fc.SHAPE_CAM, plane, fc.T)[0]
+    for k in fc.SHAPE_K:
+        w = fc.shape_weights(k)
+        want_d, want_p = fnp.frame_front(depth, *fc.SHAPE_CAM, plane, fc.T, w)
+        for with_pts in (True, False):
+            got_d, got_p = _front(rdf, depth, fc.SHAPE_CAM, plane, w, with_pts)
+            print(f"{W} x {H}, k = {k}, pts_out {'given' if with_pts else 'NULL'}: {int((got_d > 0).sum())} pixels kept, "
+                  f"{int((got_d != want_d).sum())} differ")
+            assert _eq(got_d, want_d), (k, with_pts)
+            if with_pts:
+                assert _eq(got_p, want_p), k
+        if k:
+            for i in range(fc.SHAPE_N):
+                assert _eq(_gauss(rdf, clean[i], w), fnp.gaussian(clean[i], w)), (k, i)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(fc.SELECT_COUNTS))
+def test_plane_select_ties_across_lanes_and_sets_without_a_plane(name, rdf, gpu_runtime):
+    fe, s = _fe(), gpu_runtime.stream()
+    counts_np = fc.SELECT_COUNTS[name]
+    cand, counts = rdf.to_device(fc.SELECT_CANDIDATES), rdf.to_device(counts_np)
+    plane = rdf.to_device(fc.PLANE_IN)
+    res = rdf.DeviceArray((112,), np.uint8)
+    assert fe.rdf_plane_select(fc.SELECT_G, cand.ptr, counts.ptr, plane.ptr, res.ptr, s) == 0
+    rec = res.get().view(importlib.import_module("3d-beats_amd.calibrated_plane").RESULT_DTYPE)[0]
+    wp, wb, wc, c, st = fnp.plane_select(fc.SELECT_CANDIDATES, counts_np, fc.PLANE_IN)
+    got = (int(rec["best_index"]), int(rec["best_count"]), int(rec["status"]))
+    print(f"{name}: best index, count, status {got}")
+    assert got == fc.SELECT_WANT_BEST[name] == (wb, wc, st)                     # worked by hand, and the restatement's
+    assert np.array_equal(rec["c"].view(np.uint64), c.view(np.uint64))
+    assert _eq(plane.get(), wp) and _eq(rec["plane"], wp)
 
 
 @pytest.mark.gpu

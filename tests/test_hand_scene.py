@@ -12,6 +12,8 @@ import pytest
 
 import hand_scene_cases as hc
 import hand_scene_numpy as hs
+import mutants
+import rerender_cases as rc
 from abi_helpers import declared
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -231,6 +233,145 @@ def test_the_many_frames_case_reaches_the_frame_loop_and_its_settings_differ():
     assert not np.array_equal(c["want"]["without a table"][0], c["want"]["with the cycling tables"][0])
 
 
+# ------------------------------------------------------------------ CPU: do the device cases bite? --------------------------
+def _outputs(mod, name):
+    """What the device test of case `name` compares, under the restatement module `mod`."""
+    if name != "scene 33 x 17":
+        return list(hc.render_of(mod, hc.grid_case(name[6:]) if name.startswith("grid: ") else hc.OWN_CASES[name]))
+    c = hc.case(33, 17)
+    m, out = c["mesh"], []
+    with np.errstate(all="ignore"):
+        alike = getattr(mod, "RASTERISES_ALIKE", False)         # (then the scene's own record of rules V and 3 to 6 serves)
+        geometry = c["geometry"] if alike else mod.rasterise(33, 17, m[0], m[1], m[2], c["tforms"], *c["cam"])
+        for _, with_table, empty, holes, noise in hc.VARIANTS:
+            out += list(mod.render(33, 17, *m, c["tforms"], c["tables"] if with_table else None, *c["cam"], empty_depth=empty,
+                                   seed=hc.SEED, hole_threshold=holes, noise_amp=noise, geometry=geometry)[:2])
+    return out
+
+
+_true_outputs = {}
+
+
+def _true(name):
+    if name not in _true_outputs:
+        _true_outputs[name] = _outputs(hs, name)
+    return _true_outputs[name]
+
+
+def test_the_unchanged_copy_is_the_restatement_bit_for_bit():
+    copy = hc.mutant()
+    assert copy is not hs and copy.render is not hs.render and copy.fragments is not hs.fragments
+    for name in hc.KILLS:
+        assert mutants.same(_outputs(copy, name), _true(name)), name
+    c = hc.case(33, 17)
+    assert all(np.array_equal(a, b) for a, b in zip(_true("scene 33 x 17"), [x for v in hc.VARIANTS for x in c["want"][3, v[0]][:2]]))
+
+
+def test_a_mutant_that_no_longer_applies_fails_loudly():
+    with pytest.raises(AssertionError, match="0 times"):
+        mutants.load("hand_scene_numpy", [("~(zm <= z_t)", "~(zm < z_t)")])
+    with pytest.raises(AssertionError, match="2 times"):
+        mutants.load("hand_scene_numpy", [(".astype(np.float32) + F(0.5))", ".astype(np.float32))")])
+
+
+@pytest.mark.parametrize("name", list(hc.KILLS))
+def test_each_mutant_changes_the_case_meant_for_it(name, capsys):
+    """A wrong reading of a rule that leaves a case's images unchanged would pass the GPU test of that case."""
+    killed = {m: mutants.changed(_outputs(hc.mutant(m), name), _true(name)) for m in hc.MUTANTS}
+    with capsys.disabled():
+        print(f"\n  {name}: outputs changed by " + ", ".join(f"{m}: {k}" for m, k in killed.items() if k), end="")
+    for m in hc.KILLS[name]:
+        assert killed[m] > 0, (name, m)
+    for m in hc.EQUIVALENT:
+        assert killed[m] == 0, (name, m)
+
+
+def test_every_mutant_is_met_by_some_case():
+    met = set(m for ms in hc.KILLS.values() for m in ms)
+    assert met | set(hc.EQUIVALENT) == set(hc.MUTANTS) and not met & set(hc.EQUIVALENT)
+    assert set(hc.KILLS) == {"scene 33 x 17"} | {"grid: " + n for n in rc.GRID_CASES} | set(hc.OWN_CASES)
+    assert set(rc.FRAGMENT_EDITS) | set(rc.VERTEX_EDITS) <= set(hc.MUTANTS) and all(len(why) > 40 for why in hc.EQUIVALENT.values())
+
+
+def test_equivalent_z_ge_0_and_area_0_draw_the_same_meshes():
+    tiny = np.array([1], np.uint32).view(np.float32)[0]
+    vals = (0., 3.5, -2., np.inf, -np.inf, np.nan)
+    verts = np.array([(x, y, z) for z in (0., -0., tiny) for x in vals for y in vals] + [(10., -20., 640.), (60., -20., 640.), (10., 30., 640.)],
+                     np.float32)
+    n = len(verts)
+    # every aimed vertex in a triangle with two ordinary ones; triangles without area: one point thrice, and three on a line
+    tris = [(k, n - 3, n - 2) for k in range(n - 3)] + [(n - 3, n - 2, n - 1), (n - 3, n - 3, n - 3), (n - 3, n - 2, n - 2)]
+    line = np.array([rc.grid(1, 1, (64., 0., 0.), {(0, 0): (1.5 + k, 1.5 + k, 256.)})[0][0, 0, :3] for k in range(3)], np.float32)
+    verts = np.concatenate([verts, line])
+    tris += [(n, n + 1, n + 2)]
+    label = np.arange(1, len(tris) + 1, dtype=np.uint16)
+    for name in ("z' >= 0 drawable", "a triangle of area 0 kept"):
+        m = hc.mutant(name)
+        for cam in ((64., 0., 0.), (64., 3.5, 2.25), (3e38, 0., 0.)):
+            with np.errstate(all="ignore"):
+                assert mutants.same(list(hs.vertices(verts, np.zeros(len(verts), np.int32), EYE12, *cam)),
+                                    list(m.vertices(verts, np.zeros(len(verts), np.int32), EYE12, *cam))), (name, cam)
+                want = hs.render(8, 8, verts, np.zeros(len(verts), np.int32), tris, label, EYE12.reshape(1, 1, 12), None, *cam)[:2]
+                got = m.render(8, 8, verts, np.zeros(len(verts), np.int32), tris, label, EYE12.reshape(1, 1, 12), None, *cam)[:2]
+            assert mutants.same(list(want), list(got)), (name, cam)
+    with np.errstate(all="ignore"):
+        X, Y, _, ok = hs.vertices(verts, np.zeros(len(verts), np.int32), EYE12, 64., 0., 0.)
+        labels = hs.render(8, 8, verts, np.zeros(len(verts), np.int32), tris, label, EYE12.reshape(1, 1, 12), None, 64., 0., 0.)[1]
+    assert ok[-6:].all() and ok[:n - 3].sum() == 1 and X[n:].tolist() == Y[n:].tolist() == [384, 640, 896]      # centres on the line
+    assert (labels > 0).sum() >= 3                  # the ordinary triangle is drawn
+
+
+def test_equivalent_table_t_ge_0_shows_no_other_table():
+    m = hc.mutant("table t >= 0")
+    none = np.zeros((0, 3), np.float32)
+    cam = (64., 3.5, 2.5)               # pixel (3, 2) looks along rx = ry = 0
+    rows = []
+    for d in (0., -0., 5., -5., 1000., np.inf, -np.inf, np.nan):
+        # t = +0 everywhere; -0 everywhere; +0 in column 3 only; -0 in column 3 (rx = +-0 times -1, plus -0); +0 at one pixel
+        rows += [(0., 0., 0., d), (-0., -0., -0., d), (1., 0., 0., d), (-1., -0., -0., d), (1., 1., 0., d), (0., 0., 1., d)]
+    tables = np.array(rows, np.float32)
+    args = (8, 6, none, [], np.zeros((0, 3), np.int32), [], np.zeros((len(tables), 1, 12), np.float32), tables, *cam)
+    with np.errstate(all="ignore"):
+        for zmin, zmax in ((50., 50000.), (1e-30, 3e38)):
+            want, got = hs.render(*args, zmin, zmax, 7)[:2], m.render(*args, zmin, zmax, 7)[:2]
+            assert mutants.same(list(want), list(got))
+            t0 = [hs.table_depth(tb, 8, 6, *cam, zmin, zmax) for tb in tables]
+            t1 = [m.table_depth(tb, 8, 6, *cam, zmin, zmax) for tb in tables]
+            assert all(mutants.same(a[1], b[1]) for a, b in zip(t0, t1))
+    # the inputs are aimed: t is +0 and -0 at pixels of these tables, and an ordinary table among them shows
+    j, i = np.mgrid[:6, :8]
+    rx = ((i.astype(np.float32) + F(0.5)) - F(3.5)) / F(64.)
+    assert rx[0, 3] == 0 and (want[0][5::6] != 7).any() and (want[0][:4] == 7).all()
+    t = (F(-1.) * rx + F(-0.) * rx) + F(-0.)
+    assert t[0, 3] == 0 and np.signbit(t[0, 3])
+
+
+def test_the_own_cases_hold_what_they_name():
+    inside = np.zeros((16, 16), bool)
+    inside[hc.QUAD_PIXELS] = True
+    depth, labels = hc.want_of("quad coplanar with the table")
+    assert (depth == 512).all() and np.array_equal(labels[0] > 0, inside)                  # worked by hand: z == zt, the mesh shows
+    depth, labels = hc.want_of("tables at the ends of the depth range")
+    assert np.array_equal(depth[0], np.where(inside, 512, 1024)) and np.array_equal(depth[1], np.where(inside, 512, 7))
+    assert (depth[2] == 256).all() and not labels[2].any() and np.array_equal(depth[3], depth[1])
+    assert all(np.array_equal(l > 0, inside) for l in labels[[0, 1, 3]])
+    c = hc.OWN_CASES["hole threshold on a pixel's own hash"]
+    h = hs.hashes(c["seed"], 0, 256)[0]
+    depth, labels = hc.want_of("hole threshold on a pixel's own hash")
+    at = int(np.nonzero(h == c["holes"])[0][0])
+    assert depth[0].reshape(-1)[at] != 0 and (depth[0].reshape(-1)[h < c["holes"]] == 0).all() and (h < c["holes"]).sum() == 128
+    assert (depth[0].reshape(-1)[h >= c["holes"]] != 0).all()
+    depth, labels = hc.want_of("noise against both clamps")
+    assert depth[0].min() == 1 and (depth[0] == 1).sum() > 50 and depth[0].max() == 7
+    assert depth[1].max() == 65534 and (depth[1] == 65534).sum() > 30 and depth[1][~inside].min() == 65528
+    for name in rc.GRID_CASES:
+        want = rc.GRID_CASES[name]["depth"]
+        if want is not None:
+            assert np.array_equal(hc.want_of("grid: " + name)[0][0], want), name
+        # one grid, two restatements: the same depths, and the label of the triangle whose colour the re-render shows
+        assert np.array_equal(hc.want_of("grid: " + name)[0][0], rc.grid_want(name)[0]), name
+
+
 # ------------------------------------------------------------------ CPU: the model ------------------------------------------
 def test_every_part_is_a_closed_consistently_wound_mesh():
     hm = _hm()
@@ -433,7 +574,7 @@ def test_the_new_names_are_public(rdf):
 
 
 # ------------------------------------------------------------------ GPU -----------------------------------------------------
-def _render_raw(rdf, W, H, mesh, tforms, table, cam, empty, seed, holes, noise, keys=None, runs=1):
+def _render_raw(rdf, W, H, mesh, tforms, table, cam, empty, seed, holes, noise, keys=None, runs=1, zmin=50., zmax=50000.):
     """rdf_hand_scene_render on an arbitrary mesh: [(depth, labels)] of `runs` calls in a row on one workspace, and the
     workspace's bytes after the last."""
     _lib = importlib.import_module("3d-beats_amd._lib")
@@ -452,7 +593,7 @@ def _render_raw(rdf, W, H, mesh, tforms, table, cam, empty, seed, holes, noise, 
         depth.fill(7)
         labels.fill(7)
         rc = lib.rdf_hand_scene_render(N, W, H, len(verts), dev[0].ptr, dev[1].ptr, len(tris), dev[2].ptr, dev[3].ptr, P, dev[4].ptr,
-                                       tb.ptr if tb is not None else None, *(float(v) for v in cam), 50., 50000., empty, seed, holes,
+                                       tb.ptr if tb is not None else None, *(float(v) for v in cam), float(zmin), float(zmax), empty, seed, holes,
                                        noise, keys.ptr, depth.ptr, labels.ptr, rt.stream())
         _lib.check(lib, rc, "rdf_hand_scene_render")
         out.append((depth.get(), labels.get()))
@@ -474,6 +615,28 @@ def test_hand_built_scenes_match_the_restatement_bit_for_bit(W, H, n_frames, rdf
         # the workspace is left empty: the second call on it gives the same images
         assert np.array_equal(runs[1][0], runs[0][0]) and np.array_equal(runs[1][1], runs[0][1]), name
         assert (keys == 0xFF).all(), name
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["grid: " + n for n in rc.GRID_CASES] + list(hc.OWN_CASES))
+def test_one_rule_cases_match_the_restatement_bit_for_bit(name, rdf, gpu_runtime):
+    c = hc.grid_case(name[6:]) if name.startswith("grid: ") else hc.OWN_CASES[name]
+    want_depth, want_labels = hc.want_of(name)
+    runs, keys = _render_raw(rdf, c["W"], c["H"], c["mesh"], c["tforms"], c["tables"], c["cam"], c["empty"], c["seed"], c["holes"],
+                             c["noise"], zmin=c["zmin"], zmax=c["zmax"])
+    depth, labels = runs[0]
+    print(f"{name}: {int((want_labels > 0).sum())} mesh pixels, {int((depth != want_depth).sum())} depths and "
+          f"{int((labels != want_labels).sum())} labels differ")
+    if c.get("depth") is not None:                      # the images worked by hand
+        assert np.array_equal(depth[0], c["depth"]), name
+    if name == "quad coplanar with the table":
+        inside = np.zeros((16, 16), bool)
+        inside[hc.QUAD_PIXELS] = True
+        assert (depth == 512).all() and np.array_equal(labels[0] > 0, inside)
+    if name == "noise against both clamps":
+        assert (depth[0] == 1).any() and (depth[1] == 65534).any()
+    assert np.array_equal(depth, want_depth) and np.array_equal(labels, want_labels), name
+    assert (keys == 0xFF).all(), name
 
 
 @pytest.mark.gpu

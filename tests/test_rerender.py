@@ -12,6 +12,8 @@ import pytest
 
 import frontend_numpy as fnp
 import labels_numpy as lnp
+import mutants
+import rerender_cases as rc
 import rerender_numpy as rn
 from abi_helpers import declared
 
@@ -23,8 +25,7 @@ PALETTE8 = np.array([[220, 40, 40], [40, 200, 60], [50, 60, 230], [230, 220, 50]
 EYE = np.identity(4, np.float32)
 
 
-def _make_transform(*a, **kw):
-    return importlib.import_module("3d-beats_amd.rerender").SceneRerender.make_transform(*a, **kw)
+_make_transform, _plane, _case = rc.make_transform, rc.plane, rc.case
 
 
 def _flat(W, H, d, f=64., color=(10, 200, 30)):
@@ -132,17 +133,6 @@ def test_nothing_is_drawn_outside_the_depth_range_or_behind_the_camera():
     assert not rn.rerender(pts, color, M, *cam)[2].any()
 
 
-def _plane(tilt_deg=25., spin_deg=40., t=(3000., -7000., 10000.)):
-    """An orthonormal plane matrix (rotation about x, then about z) with translations of up to 10^4, float32."""
-    a, b = np.deg2rad(tilt_deg), np.deg2rad(spin_deg)
-    rx = np.array([[1, 0, 0], [0, np.cos(a), -np.sin(a)], [0, np.sin(a), np.cos(a)]])
-    rz = np.array([[np.cos(b), -np.sin(b), 0], [np.sin(b), np.cos(b), 0], [0, 0, 1]])
-    P = np.identity(4)
-    P[:3, :3] = rz @ rx
-    P[:3, 3] = t
-    return P.astype(np.float32)
-
-
 def test_make_transform():
     P = _plane()
     c = np.array([120., -340., 55.])
@@ -235,43 +225,7 @@ def test_draw_order_and_the_two_unrandomised_first_frames():
     assert scale != 1. and not skew.any() and rotate == 0. and not translate.any()
 
 
-# ------------------------------------------------------------------ GPU ------------------------------------------------------
-def _scene(W, H, seed):
-    """An ellipse of valid points with holes and a depth step on an empty background, random colours: (pts, colour, cam)."""
-    rng = np.random.default_rng(seed)
-    f, ppx, ppy = F(W), F((W - 1) / 2 + 0.3), F((H - 1) / 2 - 0.2)
-    yy, xx = np.mgrid[:H, :W]
-    ell = ((xx - W / 2) / (0.42 * W)) ** 2 + ((yy - H / 2) / (0.40 * H)) ** 2 <= 1.
-    d = np.where(xx > 0.55 * W, 800 + 2 * yy + xx % 5, 600 + (3 * xx + yy) % 11 + yy)
-    d = np.where(ell, d, 0)
-    d[rng.random((H, W)) < 0.03] = 0
-    pts = fnp.deproject(d.astype(np.uint16), ppx, ppy, f)
-    color = rng.integers(0, 256, (H, W, 3)).astype(np.uint8)
-    return pts, color, (float(f), float(ppx), float(ppy))
-
-
-def _transforms(pts):
-    P = _plane(20., 0., (0., 30., 650.))
-    s = rn.center_sums(fnp.transform(pts, P))
-    c = s[:3] / s[3]
-    return [("identity", EYE),
-            ("scale 0.8 with skew", _make_transform(P, c, 0.8, (0.05, -0.1, 0.02))),
-            ("scale 1.25", _make_transform(P, c, 1.25)),
-            ("rotated and pushed out of the frame", _make_transform(P, c, 1., (0., 0., 0.), 0.3, (210., 40., 0.))),
-            ("partly beyond zmax", np.diag([70., 70., 70., 1.]).astype(np.float32))]
-
-
-_cases = {}
-
-
-def _case(W, H):
-    """Scene, transforms and the restatement's images for one size, computed once."""
-    if (W, H) not in _cases:
-        pts, color, cam = _scene(W, H, W * 1000 + H)
-        _cases[W, H] = (pts, color, cam, [(name, M, rn.rerender(pts, color, M, *cam)) for name, M in _transforms(pts)])
-    return _cases[W, H]
-
-
+# ------------------------------------------------------------------ CPU: the scenes of the device tests -------------------
 def test_the_gpu_scenes_exercise_what_they_are_meant_to():
     pts, color, cam, cases = _case(33, 17)
     by = {name: want for name, _, want in cases}
@@ -286,8 +240,166 @@ def test_the_gpu_scenes_exercise_what_they_are_meant_to():
     assert 0 < (far > 0).sum() < (by["identity"][0] > 0).sum() and far.max() <= 50000 and far[far > 0].min() > 40000
 
 
+# ------------------------------------------------------------------ CPU: do the device cases bite? --------------------------
+def _outputs(mod, name):
+    """What the device test of case `name` compares, under the restatement module `mod`."""
+    if name == "scenes 33 x 17":
+        pts, color, cam, cases = rc.case(33, 17)
+        return [a for _, M, _ in cases for a in mod.rerender(pts, color, M, *cam)[:2]]
+    return list(rc.rerender_of(mod, rc.GRID_CASES[name]))
+
+
+_true_outputs = {}
+
+
+def _true(name):
+    if name not in _true_outputs:
+        with np.errstate(all="ignore"):
+            _true_outputs[name] = _outputs(rn, name)
+    return _true_outputs[name]
+
+
+def test_the_unchanged_copy_is_the_restatement_bit_for_bit():
+    copy = rc.mutant()
+    assert copy is not rn and copy.rerender is not rn.rerender
+    with np.errstate(all="ignore"):
+        for name in rc.KILLS:
+            assert mutants.same(_outputs(copy, name), _true(name)), name
+
+
+def test_a_mutant_that_no_longer_applies_fails_loudly():
+    with pytest.raises(AssertionError, match="0 times"):
+        mutants.load("rerender_numpy", [("zz >= F(z_min)", "zz > F(z_min)")])
+    with pytest.raises(AssertionError, match="2 times"):
+        mutants.load("rerender_numpy", [("np.floor(((F(f) * ", "np.trunc(((F(f) * ")])
+
+
+@pytest.mark.parametrize("name", list(rc.KILLS))
+def test_each_mutant_changes_the_case_meant_for_it(name, capsys):
+    """A wrong reading of a rule that leaves a case's images unchanged would pass the GPU test of that case."""
+    killed = {}
+    with np.errstate(all="ignore"):
+        for m in rc.MUTANTS:
+            killed[m] = mutants.changed(_outputs(rc.mutant(m), name), _true(name))
+    with capsys.disabled():
+        print(f"\n  {name}: outputs changed by " + ", ".join(f"{m}: {k}" for m, k in killed.items() if k), end="")
+    for m in rc.KILLS[name]:
+        assert killed[m] > 0, (name, m)
+    for m in rc.EQUIVALENT:
+        assert killed[m] == 0, (name, m)
+
+
+def test_every_mutant_is_met_by_some_case():
+    assert set(m for ms in rc.KILLS.values() for m in ms) | set(rc.EQUIVALENT) == set(rc.MUTANTS)
+    assert not set(m for ms in rc.KILLS.values() for m in ms) & set(rc.EQUIVALENT)
+    assert set(rc.KILLS) == {"scenes 33 x 17"} | set(rc.GRID_CASES) and all(len(why) > 40 for why in rc.EQUIVALENT.values())
+
+
+def _aimed_vertices():
+    """Points and an identity transform that put z' on +0, -0 and the smallest subnormal with x' and y' each of 0, finite,
+    inf and NaN; one ordinary point, so that the comparison is not of nothing."""
+    tiny = np.array([1], np.uint32).view(np.float32)[0]
+    vals = (0., 3.5, -2., np.inf, -np.inf, np.nan)
+    rows = [(x, y, z, 1.) for z in (0., -0., tiny) for x in vals for y in vals] + [(10., -20., 640., 1.)]
+    return np.array(rows, np.float32).reshape(1, -1, 4)
+
+
+def test_equivalent_z_ge_0_draws_no_other_vertex():
+    m = rc.mutant("z' >= 0 drawable")
+    pts = _aimed_vertices()
+    with np.errstate(all="ignore"):
+        for cam in ((64., 0., 0.), (64., 3.5, 2.25), (1e-30, 0., 0.), (3e38, 0., 0.)):
+            want, got = rn.vertices(pts, EYE, *cam), m.vertices(pts, EYE, *cam)
+            assert mutants.same(list(want), list(got)), cam
+    # what is drawable: the ordinary point, and a subnormal z' only where x' = y' = 0 (any other finite x' overflows)
+    ok = rn.vertices(pts, EYE, 64., 0., 0.)[4].reshape(-1)
+    assert ok[-1] and ok.sum() == 2 and ok[72] and pts[0, 72].tolist()[:2] == [0., 0.] and not ok[:72].any()
+    # and a grid that holds such points draws the same image
+    grid_pts = np.zeros((8, 8, 4), np.float32)
+    grid_pts[:, :] = pts.reshape(-1, 4)[:64].reshape(8, 8, 4)
+    color = np.full((8, 8, 3), 9, np.uint8)
+    with np.errstate(all="ignore"):
+        assert mutants.same(list(rn.rerender(grid_pts, color, EYE, 64., 0., 0.)), list(m.rerender(grid_pts, color, EYE, 64., 0., 0.)))
+
+
+def test_equivalent_a_kept_triangle_of_area_0_covers_nothing():
+    m = rc.mutant("a triangle of area 0 kept")
+    # quads whose triangles have no area: all four points on one screen position, on a horizontal, a vertical and a
+    # diagonal line through pixel centres (where an e_k of 0 would count on a top or left edge), and one proper quad
+    placed = {}
+    for c, (dx, dy) in enumerate(((0., 0.), (1., 0.), (0., 1.), (1., 1.))):
+        for k, (r, cc) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
+            placed[r + 2 * c, cc] = (1.5 + k * dx, 1.5 + k * dy, 256.)
+    placed.update({(r + 8, c): (2.25 + 4 * c, 8.25 + 4 * r, 256.) for r in range(2) for c in range(2)})
+    pts, color = rc.grid(16, 16, (64., 7.5, 7.25), placed)
+    X, Y, _, has, ok = rn.vertices(pts, EYE, 64., 7.5, 7.25)
+    ids, tris = rn.mesh(has)
+    area = rn._edge(*(a.reshape(-1)[tris[:, k]] for k in (0, 1) for a in (X, Y)), X.reshape(-1)[tris[:, 2]], Y.reshape(-1)[tris[:, 2]])
+    assert (area == 0).sum() >= 8 and (area != 0).sum() >= 2       # (the rows between the four also make quads)
+    with np.errstate(all="ignore"):
+        want, got = rn.rerender(pts, color, EYE, 64., 7.5, 7.25), m.rerender(pts, color, EYE, 64., 7.5, 7.25)
+    assert mutants.same(list(want), list(got)) and want[2].sum() >= 16
+
+
+def test_the_grid_cases_hold_what_they_name():
+    for name, c in rc.GRID_CASES.items():
+        depth, color, count = rc.grid_want(name)
+        if c["depth"] is not None:                      # the images worked by hand
+            assert np.array_equal(depth, c["depth"]), name
+        assert c["W"] <= 16 and c["H"] <= 16
+    X, Y, _, _, ok = rn.vertices(rc.GRID_CASES["edges on pixel centres"]["pts"], EYE, 64., 7.5, 7.25)
+    assert sorted(set(X[:3, :3].ravel().tolist())) == [256 * i + 128 for i in (2, 6, 10)]
+    assert sorted(set(Y[:3, :3].ravel().tolist())) == [256 * j + 128 for j in (3, 7, 11)]
+    assert rc.grid_want("edges on pixel centres")[2].max() == 1           # no pixel twice, shared edges and diagonals included
+    # the fold: every drawn pixel is reached by two fragments of one z, and the lower id's colour is not the higher's
+    c = rc.GRID_CASES["folded back at one depth"]
+    depth, color, count = rc.grid_want("folded back at one depth")
+    assert (count[depth > 0] == 2).all() and (depth > 0).sum() == 64
+    other = rc.mutant("depth ties to the highest id").rerender(c["pts"], c["color"], c["M"], *c["cam"])
+    assert np.array_equal(other[0], depth) and (other[1] != color).any(-1)[depth > 0].mean() > 0.9
+    # the limits: the far vertex snaps to +-2^20 exactly, or one beyond
+    for axis, k in (("x", 0), ("y", 1)):
+        for sign, s in ((1, "+"), (-1, "-")):
+            for past in (0, 1):
+                c = rc.GRID_CASES[f"{axis} snapped to {s}" + ("(2^20 + 1)" if past else "2^20")]
+                with np.errstate(all="ignore"):
+                    fx = np.floor(((F(64.) * c["pts"][..., k]) / c["pts"][..., 2]) * F(256) + F(0.5))
+                assert (fx[:2, :2] == sign * (2 ** 20 + past)).sum() == 1, (axis, sign, past)
+    # the fma literals: the rounded rows snap A and the point below it on column 2's centres, the contracted rows beyond
+    c = rc.GRID_CASES["rows that a contraction would snap elsewhere"]
+    X = rn.vertices(c["pts"], c["M"], *c["cam"])[0]
+    Xc = rc.mutant("vertex rows contracted").vertices(c["pts"], c["M"], *c["cam"])[0]
+    assert X[0, 0] == X[1, 0] == rc.FMA_X == 256 * 2 + 128 and Xc[0, 0] == Xc[1, 0] == rc.FMA_X_CONTRACTED
+    depth = rc.grid_want("rows that a contraction would snap elsewhere")[0]
+    assert (depth[:7, 2] > 0).all() and not depth[:, :2].any()
+    # the sums: an edge function beyond 2^24
+    c = rc.GRID_CASES["sums that another order would round elsewhere"]
+    X, Y, _, _, _ = rn.vertices(c["pts"], EYE, *c["cam"])
+    assert abs(int(rn._edge(X[0, 0], Y[0, 0], X[0, 1], Y[0, 1], X[1, 0], Y[1, 0]))) > 2 ** 24
+
+
+# ------------------------------------------------------------------ GPU ------------------------------------------------------
 @pytest.mark.gpu
-@pytest.mark.parametrize("W,H", [(33, 17), (70, 130), (130, 70)])
+@pytest.mark.parametrize("name", list(rc.GRID_CASES))
+def test_rerender_of_the_grid_cases_matches_the_restatement_bit_for_bit(name, rdf, gpu_runtime):
+    c = rc.GRID_CASES[name]
+    W, H = c["W"], c["H"]
+    want_depth, want_color, _ = rc.grid_want(name)
+    rr = rdf.SceneRerender((H, W), c["cam"], z_near=c["zmin"], z_far=c["zmax"])
+    p, col = rdf.to_device(c["pts"]), rdf.to_device(c["color"])
+    depth, out = rdf.DeviceArray((H, W), np.uint16).fill(7), rdf.DeviceArray((H, W, 3), np.uint8).fill(7)
+    rr.run(p, col, c["M"], depth, out)
+    got_depth, got_color = depth.get(), out.get()
+    print(f"{name}: {int((want_depth > 0).sum())} pixels drawn, {int((got_depth != want_depth).sum())} depths and "
+          f"{int((got_color != want_color).any(-1).sum())} colours differ")
+    if c["depth"] is not None:
+        assert np.array_equal(got_depth, c["depth"]), name
+    assert np.array_equal(got_depth, want_depth) and np.array_equal(got_color, want_color), name
+    assert (rr._keys.get() == 0xFF).all(), name
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("W,H", rc.SIZES)
 def test_rerender_matches_the_restatement_bit_for_bit(W, H, rdf, gpu_runtime):
     pts, color, cam, cases = _case(W, H)
     rr = rdf.SceneRerender((H, W), cam)

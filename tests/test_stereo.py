@@ -271,6 +271,42 @@ def test_the_device_matches_the_restatement_bit_for_bit(name, rdf, gpu_runtime):
     assert rc == 0 and np.array_equal(bare["depth"], want["depth"]) and np.array_equal(bare["labels"], want["labels"])
 
 
+def test_the_column_0_case_holds_a_winner_left_of_the_right_image():
+    """x - d* == -1 at one pixel that is unique and has dq >= dq_min: it fails for the left-right check's first clause alone,
+    and a reading that accepts x - d* == -1 (comparing dR at the clamped column, within lr_max = 255) would show it."""
+    import mutants
+    c = sc.column0_case()
+    y, x = sc.COLUMN0_PIXEL
+    frame, want = c["want"]["frames"][0], c["want"]
+    assert c["in"][0].shape == (1, 5, 9) and x == 0 and frame["d"][y, x] == 1 and x - frame["d"][y, x] == -1
+    assert want["reason"][0, y, x] == sn.REASON_LR and want["depth"][0, y, x] == sc.EMPTY and want["labels"][0, y, x] == 0
+    assert want["dq"][0, y, x] >= c["cfg"]["dq_min"] and (want["reason"] == 0).sum() > 20
+    loose = mutants.load("stereo_numpy", [("lr = (xr >= 0) &", "lr = (xr >= -1) &")])
+    got = loose.sense(*c["in"], c["cfg"], seed=sc.SEED, empty_depth=sc.EMPTY)
+    differ = {k: np.argwhere(got[k] != want[k]).tolist() for k in ("depth", "labels", "dq", "reason")}
+    assert differ == {"depth": [[0, y, x]], "labels": [[0, y, x]], "dq": [], "reason": [[0, y, x]]}
+    assert got["reason"][0, y, x] == 0 and got["labels"][0, y, x] == 3
+    # and no other device case of the sensor tells the two readings apart
+    for name in sc.GPU_SHAPES:
+        g = sc.gpu_case(name)
+        other = loose.sense(*g["in"], g["cfg"], seed=sc.SEED, empty_depth=sc.EMPTY)
+        assert all(np.array_equal(other[k], g["want"][k]) for k in ("depth", "labels", "dq", "reason")), name
+
+
+@pytest.mark.gpu
+def test_a_winner_left_of_the_right_image_fails_the_left_right_check(rdf, gpu_runtime):
+    c = sc.column0_case()
+    want = c["want"]
+    y, x = sc.COLUMN0_PIXEL
+    rc, got = _sense_raw(rdf, c["in"], c["cfg"], sc.SEED, sc.EMPTY)
+    assert rc == 0
+    print(f"pixel ({x}, {y}): dq {int(got['dq'][0, y, x])}, reason {int(got['reason'][0, y, x])}, depth {int(got['depth'][0, y, x])}; "
+          f"differing {({k: int((got[k] != want[k]).sum()) for k in OUTPUTS})}")
+    assert got["reason"][0, y, x] == sn.REASON_LR and got["depth"][0, y, x] == sc.EMPTY and got["labels"][0, y, x] == 0
+    for k in OUTPUTS:
+        assert np.array_equal(got[k], want[k]), k
+
+
 def test_the_gpu_cases_decide_something():
     """The shapes of the GPU comparison reach valid and invalid pixels of every kind, and their frames differ."""
     seen = np.zeros(8, np.int64)
