@@ -36,10 +36,11 @@ LIBRARIES = {lib.key: lib for lib in (
     # glove-colour recordings to training labels, the re-render that augments them, the score of predicted label maps, and
     # labelled frames of the articulated hand, the fit of that hand's pose to a labelled depth frame, and the stereo depth
     # sensor that turns a left and a right render of those frames into what a camera would report, and the refit of a trained
-    # forest's leaf distributions on such frames and the pruning of the forest on the same counts (the refit's walk takes the
-    # reference-layout feature step -- the offset coordinate and the bounds-checked read -- from rdf_device.hpp, the forest
-    # and training kernels' header), and the forest's posterior:
-    # the same walk ending in per-pixel class sums, a confidence and a gated label where inference ends in an argmax, and the
+    # forest's leaf distributions on such frames and the pruning of the forest on the same counts, and the forest's posterior:
+    # the refit's walk ending in per-pixel class sums, a confidence and a gated label where inference ends in an argmax (these
+    # three read the reference-layout forest through rdf_forest_ref.hpp, a header of this library alone: its layout, its flag
+    # rule, the one walk and the ancestor's PDF; the walk's feature step -- the offset coordinate and the bounds-checked read
+    # -- is that of rdf_device.hpp, the forest and training kernels' header), and the
     # consumer of that confidence: composite weights of a layered stack and the weighted mean shift (soft modes), whose kernel
     # body is the mean shift's own: rdf_modes.hpp is a header of this library and of "hip", and a change to it rebuilds both
     Library("labels", os.path.join(HERE, "csrc", "librdf_labels.so"),
@@ -50,7 +51,7 @@ LIBRARIES = {lib.key: lib for lib in (
              os.path.join(HERE, "csrc", "forest_posterior_hip.hip"), os.path.join(HERE, "csrc", "soft_modes_hip.hip")],
             [os.path.join(HERE, "..", "include", "rdf_labels.h"), os.path.join(HERE, "csrc", "rdf_kernel_util.hpp"),
              os.path.join(HERE, "csrc", "rdf_raster.hpp"), os.path.join(HERE, "csrc", "rdf_device.hpp"),
-             os.path.join(HERE, "csrc", "rdf_modes.hpp")], "rdf_labels_"),
+             os.path.join(HERE, "csrc", "rdf_modes.hpp"), os.path.join(HERE, "csrc", "rdf_forest_ref.hpp")], "rdf_labels_"),
 )}
 
 # No -ffast-math, no -fgpu-flush-denormals-to-zero: the fp32 divide must stay IEEE-correct

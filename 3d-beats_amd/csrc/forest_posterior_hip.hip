@@ -7,8 +7,8 @@
 //
 // k_posterior: one lane per label pixel, a wave takes 64 consecutive label pixels and leaves at once when none of them is to
 // be evaluated (background, holes, filtered out: most of a live frame).  A lane walks the trees of the reference-layout
-// forest one after the other, as k_refit_count does and with the same helpers of rdf_device.hpp; the level loop runs while any
-// lane of the wave still walks.  The C sums live in registers: the kernel is instantiated for class capacities 4, 8 and 16 and
+// forest one after the other with walk_tree of rdf_forest_ref.hpp, the walk that k_refit_count takes; the level loop runs while
+// any lane of the wave still walks.  The C sums live in registers: the kernel is instantiated for class capacities 4, 8 and 16 and
 // every class loop is unrolled over the capacity and guarded by c < C, so no register array is indexed by a runtime value
 // and nothing goes to scratch.  No LDS, no atomics.  Which outputs are present is a wave-uniform test of three pointers
 // (an absent output costs no store); stores are 2 bytes a lane for the two maps and one dword a lane per class plane.
@@ -21,24 +21,21 @@
 #include <stdint.h>
 
 #include "../../include/rdf_labels.h"
-#include "rdf_device.hpp"
-#include "rdf_kernel_util.hpp"
+#include "rdf_forest_ref.hpp"
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxDepth = 30;
 constexpr int kCountBlocks = 512;     // the counts kernel: larger calls stride over the grid (two workgroups a compute unit)
 constexpr int kMaxBins = 1024;
 
-struct PosteriorArgs {
+struct PosteriorArgs : ForestShape {
     const uint16_t *depth, *filter;
     const float *forest;
     uint16_t *labels, *conf;
     float *sums;
     uint32_t n_lpx, lpix, pix;        // label pixels of the call (< 2^31) and of one image, depth pixels of one image
     int W, H, Wl, r;
-    int T, D, C;
     int filter_class, min_conf;
     float scale;
 };
@@ -62,39 +59,22 @@ __global__ void __launch_bounds__(kThreads) k_posterior(const PosteriorArgs a)
     }
     if (__ballot(live) == 0ull) return;                             // (most of a frame is background)
 
-    const int T = a.T, D = a.D, C = a.C, E = 7 + 2 * C;
-    const size_t N = ((size_t)1 << D) - 1;
-    const float df = (float)d, s = a.scale;
+    const int C = a.C;
+    const WalkPixel p = {frame, a.W, a.H, x, y, (float)d, a.scale};
     float acc[CAP];
 #pragma unroll
     for (int c = 0; c < CAP; ++c) acc[c] = 0.f;
 
-    // Q2: rule R2's walk; a leaf slot's PDF is added class by class, trees in index order
-    for (int t = 0; t < T; ++t) {
-        const float *__restrict__ tree = a.forest + (size_t)t * N * E;
-        uint32_t g = 0u;
-        bool walking = live;
-        for (int j = 0; j < D && __ballot(walking) != 0ull; ++j) {
-            if (!walking) continue;
-            const uint32_t n = ((1u << j) - 1u) + g;
-            const float *__restrict__ rec = tree + (size_t)n * E;
-            const int ux = offset_coord(x, s * rec[0], df), uy = offset_coord(y, s * rec[1], df);
-            const int vx = offset_coord(x, s * rec[2], df), vy = offset_coord(y, s * rec[3], df);
-            const float f = depth_or_no_pixel<uint32_t>(frame, a.W, a.H, ux, uy) - depth_or_no_pixel<uint32_t>(frame, a.W, a.H, vx, vy);
-            const uint32_t side = f < rec[4] ? 0u : 1u;             // NaN goes right
-            if (floor_i32(rec[5 + side]) != -1) {                   // a leaf slot, at every level
-                walking = false;
-                const float *__restrict__ pdf = rec + 7 + side * (uint32_t)C;
+    // Q2: rule R2's walk; a leaf slot's PDF is added class by class, trees in index order; a walk that falls off adds nothing
+    for (int t = 0; t < a.T; ++t)
+        walk_tree(a.forest + a.rec(t, 0), a.D, a.E(), p, live,
+                  [&](int, uint32_t, uint32_t side, const float *__restrict__ rec) {
+                      const float *__restrict__ pdf = rec + 7 + side * (uint32_t)C;
 #pragma unroll
-                for (int c = 0; c < CAP; ++c)
-                    if (c < C) acc[c] = acc[c] + pdf[c];
-            } else if (j == D - 1) {                                // "go on" and no level to go to: nothing is added
-                walking = false;
-            } else {
-                g = g * 2u + side;
-            }
-        }
-    }
+                      for (int c = 0; c < CAP; ++c)
+                          if (c < C) acc[c] = acc[c] + pdf[c];
+                  },
+                  [] {});
     if (!live) return;
 
     // Q3: the inference argmax.  Q4: the winner's share of the vote
@@ -185,6 +165,7 @@ int rdf_labels_forest_posterior(const uint16_t *depth, int n_img, int dim_x, int
                                 float scale_factor, int min_conf, uint16_t *labels_out, uint16_t *conf_out, float *sums_out,
                                 void *stream)
 {
+    // (rule Q6, not bad_forest_shape: too many classes are RDF_ERR_TOO_LARGE here, after the alignment checks)
     if (n_trees < 1 || max_depth < 1 || max_depth > kMaxDepth || n_classes < 1 || labels_reduce < 1 || n_img < 0 || dim_x < 0 ||
         dim_y < 0 || filter_class < -1 || filter_class > 65535 || min_conf < 0 || min_conf > 65535)
         return RDF_ERR_BAD_ARG;
@@ -198,7 +179,7 @@ int rdf_labels_forest_posterior(const uint16_t *depth, int n_img, int dim_x, int
     if (n_img == 0 || Wl == 0 || Hl == 0) return RDF_OK;
     if (!depth || !forest || (!labels_out && !conf_out && !sums_out) || (!filter && filter_class != -1)) return RDF_ERR_NULL_PTR;
 
-    PosteriorArgs a;
+    PosteriorArgs a = {{n_trees, max_depth, n_classes}};
     a.depth = depth;
     a.filter = filter;
     a.forest = forest;
@@ -212,9 +193,6 @@ int rdf_labels_forest_posterior(const uint16_t *depth, int n_img, int dim_x, int
     a.H = dim_y;
     a.Wl = (int)Wl;
     a.r = labels_reduce;
-    a.T = n_trees;
-    a.D = max_depth;
-    a.C = n_classes;
     a.filter_class = filter_class;
     a.min_conf = min_conf;
     a.scale = scale_factor;

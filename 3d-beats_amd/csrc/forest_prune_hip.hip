@@ -1,9 +1,9 @@
 // forest_prune_hip.hip -- reduced-error pruning of a trained forest on held-out counts: subtrees whose split does not pay for
-// its leaves are folded into one leaf slot of their parent.  rdf_labels_prune_plan reads the reference-layout forest (float32
-// [T][2^D - 1][7 + 2C]) and the counts of the leaf refit (uint64 [T][N][2][C], where labelled pixels land) and decides;
-// rdf_labels_prune_apply rewrites forest and counts by the last plan.  Built into librdf_labels.so.  The contract (rules P1 to
-// P4) is in include/rdf_labels.h and tests/prune_numpy.py restates it; everything but the final PDFs is unsigned 64-bit
-// integer arithmetic, so two runs give the same bytes.
+// its leaves are folded into one leaf slot of their parent.  rdf_labels_prune_plan reads the reference-layout forest (through
+// rdf_forest_ref.hpp, as the refit and the posterior do) and the counts of the leaf refit (uint64 [T][N][2][C], where labelled
+// pixels land) and decides; rdf_labels_prune_apply rewrites forest and counts by the last plan.  Built into librdf_labels.so.
+// The contract (rules P1 to P4) is in include/rdf_labels.h and tests/prune_numpy.py restates it; everything but the final PDFs
+// is unsigned 64-bit integer arithmetic, so two runs give the same bytes.
 //
 // A plan is three sweeps over the levels: reachability top-down, rule P2 bottom-up, the reachability that is left top-down.
 // rdf_labels_refit_apply pays one launch per level and direction; here the levels are cut in two instead:
@@ -23,60 +23,50 @@
 #include <stdint.h>
 
 #include "../../include/rdf_labels.h"
-#include "rdf_device.hpp"
-#include "rdf_kernel_util.hpp"
+#include "rdf_forest_ref.hpp"
 
 namespace {
 
 constexpr int kTopThreads = 1024;     // the one workgroup of the top levels
 constexpr int kThreads = 256;
-constexpr int kMaxDepth = 30;
 constexpr uint8_t kReachBefore = 1, kCollapse = 2, kReachAfter = 4;
 
 struct Meta { u64 err, errB, leaves, leavesB; };   // rule P2, per node
 
-struct PruneArgs {
+struct PruneArgs : ForestShape {
     float *forest;                    // written by apply only
     u64 *counts;                      // likewise
     uint8_t *state;                   // [T][N]: kReachBefore | kCollapse | kReachAfter
     u64 *sub;                         // [T][N][C]
     Meta *meta;                       // [T][N]
     u64 *report;                      // [8], plan only
-    int T, D, C;
     int top;                          // levels 0 .. top - 1 are the one workgroup's, 1 <= top <= D
     int max_levels;
     u64 cost, min_count;
 };
 
-__device__ __forceinline__ size_t nodes_of(const PruneArgs &a) { return ((size_t)1 << a.D) - 1; }
-
-// reachable before: the root, and a child whose parent is reachable and flags "go on" towards it
+// reachable before (is_reachable): the level above is complete
 __device__ __forceinline__ void reach_step(const PruneArgs &a, size_t t, int j, size_t g)
 {
-    const size_t N = nodes_of(a), n = ((size_t)1 << j) - 1 + g;
-    bool r = true;
-    if (j > 0) {
-        const size_t parent = (n - 1) >> 1;
-        r = (a.state[t * N + parent] & kReachBefore) != 0 &&
-            floor_i32(a.forest[(t * N + parent) * (size_t)(7 + 2 * a.C) + 5 + (g & 1)]) == -1;
-    }
-    if (r) a.state[t * N + n] = kReachBefore;          // (the memset left 0)
+    const size_t n = ((size_t)1 << j) - 1 + g;
+    if (is_reachable(a, a.forest, t, n, [&](size_t parent) { return (a.state[parent] & kReachBefore) != 0; }))
+        a.state[a.at(t, n)] = kReachBefore;            // (the memset left 0)
 }
 
 // rule P2 for one reachable node: sub, err, errB, leaves, leavesB and the collapse bit.  The level below is complete.
 __device__ __forceinline__ void plan_step(const PruneArgs &a, size_t t, int j, size_t g)
 {
-    const int C = a.C, E = 7 + 2 * C;
-    const size_t N = nodes_of(a), n = ((size_t)1 << j) - 1 + g, at = t * N + n;
+    const int C = a.C;
+    const size_t n = ((size_t)1 << j) - 1 + g, at = a.at(t, n);
     if (!(a.state[at] & kReachBefore)) return;
-    const float *rec = a.forest + at * E;
-    u64 *dst = a.sub + at * C;
+    const float *rec = a.forest + a.rec(t, n);
+    u64 *dst = a.sub + a.row(t, n);
     Meta m = {0ull, 0ull, 0ull, 0ull};
     const bool last = j == a.D - 1;
     bool summed = false;                               // dst holds a side's counts already
     for (int s = 0; s < 2; ++s) {
-        if (floor_i32(rec[5 + s]) != -1) {             // a leaf slot: rule P1
-            const u64 *cnt = a.counts + (at * 2 + s) * C;
+        if (is_leaf_slot(rec, s)) {                    // rule P1
+            const u64 *cnt = a.counts + a.cell(t, n, s);
             const float *pdf = rec + 7 + s * C;
             float best = 0.f;
             int k = 0;
@@ -98,8 +88,8 @@ __device__ __forceinline__ void plan_step(const PruneArgs &a, size_t t, int j, s
             m.leaves += 1ull;
             m.leavesB += 1ull;
         } else if (!last) {
-            const size_t child = t * N + 2 * n + 1 + s;
-            const u64 *cs = a.sub + child * C;
+            const size_t child = a.at(t, 2 * n + 1 + s);
+            const u64 *cs = a.sub + a.row(t, 2 * n + 1 + s);
             u64 sum = 0ull, top = 0ull;
             for (int c = 0; c < C; ++c) {
                 const u64 x = cs[c];
@@ -141,18 +131,17 @@ struct AfterSums { uint32_t nodes, turned, deepest; };   // of one lane: reachab
 // it.  Returns whether the node is.
 __device__ __forceinline__ bool after_step(const PruneArgs &a, size_t t, int j, size_t g, AfterSums &sums)
 {
-    const int E = 7 + 2 * a.C;
-    const size_t N = nodes_of(a), n = ((size_t)1 << j) - 1 + g, at = t * N + n;
+    const size_t n = ((size_t)1 << j) - 1 + g, at = a.at(t, n);
     const uint8_t st = a.state[at];
     if (!(st & kReachBefore) || (st & kCollapse)) return false;
-    if (j > 0 && !(a.state[t * N + ((n - 1) >> 1)] & kReachAfter)) return false;     // (its flag said "go on": st has kReachBefore)
+    if (j > 0 && !(a.state[a.at(t, (n - 1) >> 1)] & kReachAfter)) return false;     // (its flag said "go on": st has kReachBefore)
     a.state[at] = st | kReachAfter;
     sums.nodes += 1u;
     sums.deepest = (uint32_t)(j + 1);                   // a lane's levels only grow
     if (j < a.D - 1) {
-        const float *rec = a.forest + at * E;
+        const float *rec = a.forest + a.rec(t, n);
         for (int s = 0; s < 2; ++s)
-            if (floor_i32(rec[5 + s]) == -1 && (a.state[t * N + 2 * n + 1 + s] & kCollapse)) sums.turned += 1u;
+            if (!is_leaf_slot(rec, s) && (a.state[a.at(t, 2 * n + 1 + s)] & kCollapse)) sums.turned += 1u;
     }
     return true;
 }
@@ -190,11 +179,10 @@ __global__ void __launch_bounds__(kTopThreads) k_prune_top_plan(const PruneArgs 
         for (size_t idx = threadIdx.x; idx < all; idx += kTopThreads) plan_step(a, idx >> j, j, idx & (per - 1));
         __syncthreads();
     }
-    const size_t N = nodes_of(a);
     for (size_t t = threadIdx.x; t < (size_t)a.T; t += kTopThreads) {        // rule P4, the roots' part
-        const Meta m = a.meta[t * N];
+        const Meta m = a.meta[a.at(t, 0)];
         u64 Z = 0ull;
-        for (int c = 0; c < a.C; ++c) Z += a.sub[t * N * a.C + c];
+        for (int c = 0; c < a.C; ++c) Z += a.sub[a.row(t, 0) + c];
         atomicAdd(a.report + 0, m.leavesB);
         atomicAdd(a.report + 1, m.leaves);
         atomicAdd(a.report + 4, m.errB);
@@ -216,14 +204,14 @@ __global__ void __launch_bounds__(kThreads) k_prune_deep_up(const PruneArgs a)
 {
     const size_t bid = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
     if (bid >= ((size_t)a.T << a.top)) return;          // (the workgroup as one)
-    const size_t t = bid >> a.top, g0 = bid & (((size_t)1 << a.top) - 1), N = nodes_of(a);
+    const size_t t = bid >> a.top, g0 = bid & (((size_t)1 << a.top) - 1);
     int bottom = a.top - 1;                             // the deepest level with a reachable node of this subtree
     for (int j = a.top; j < a.D; ++j) {
         const size_t width = (size_t)1 << (j - a.top), first = g0 << (j - a.top);
         int any = 0;
         for (size_t i = threadIdx.x; i < width; i += kThreads) {
             reach_step(a, t, j, first + i);
-            any |= a.state[t * N + (((size_t)1 << j) - 1 + first + i)] & kReachBefore;
+            any |= a.state[a.at(t, ((size_t)1 << j) - 1 + first + i)] & kReachBefore;
         }
         if (!__syncthreads_or(any)) break;
         bottom = j;
@@ -253,32 +241,24 @@ __global__ void __launch_bounds__(kThreads) k_prune_deep_after(const PruneArgs a
 // Rule P3 for the nodes that stay: a "go on" side whose child collapses becomes a leaf slot with the child's counts.
 __global__ void __launch_bounds__(kThreads) k_prune_fold(const PruneArgs a)
 {
-    const int C = a.C, E = 7 + 2 * C;
-    const size_t N = nodes_of(a), inner = N >> 1;       // the nodes that have children
+    const int C = a.C;
+    const size_t inner = a.N() >> 1;                    // the nodes that have children
     const size_t idx = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kThreads + threadIdx.x;
     if (idx >= inner * (size_t)a.T) return;
-    const size_t t = idx / inner, n = idx - t * inner, at = t * N + n;
-    if (!(a.state[at] & kReachAfter)) return;
-    float *rec = a.forest + at * E;
+    const size_t t = idx / inner, n = idx - t * inner;
+    if (!(a.state[a.at(t, n)] & kReachAfter)) return;
+    float *rec = a.forest + a.rec(t, n);
     for (int s = 0; s < 2; ++s) {
         const size_t c = 2 * n + 1 + s;
-        if (floor_i32(rec[5 + s]) != -1 || !(a.state[t * N + c] & kCollapse)) continue;
-        const u64 *own = a.sub + (t * N + c) * C;
-        u64 *cnt = a.counts + (at * 2 + s) * C;
+        if (is_leaf_slot(rec, s) || !(a.state[a.at(t, c)] & kCollapse)) continue;
+        const u64 *own = a.sub + a.row(t, c);
+        u64 *cnt = a.counts + a.cell(t, n, s);
         for (int k = 0; k < C; ++k) cnt[k] = own[k];
-        // the nearest of c, parent(c), ..., root with a pixel below it
-        size_t an = c;
-        u64 Z = 0ull;
-        for (;;) {
-            const u64 *cand = a.sub + (t * N + an) * C;
-            Z = 0ull;
-            for (int k = 0; k < C; ++k) Z += cand[k];
-            if (Z >= 1ull || an == 0) break;
-            an = (an - 1) >> 1;
-        }
-        const u64 *src = a.sub + (t * N + an) * C;
-        const float den = (float)Z;                     // uint64 -> fp32, round to nearest even
-        for (int k = 0; k < C; ++k) rec[7 + s * C + k] = Z >= 1ull ? (float)src[k] / den : 0.f;
+        // the nearest of c (of level floor(log2(c + 1))), parent(c), ..., root with a pixel below it; zeros when there is none
+        const SubRow src = nearest_ancestor(a, a.sub, t, c, 63 - __clzll((long long)(c + 1)), 1ull);
+        float *pdf = rec + 7 + s * C;
+        if (src.row) write_pdf(pdf, src.row, src.sum, C);
+        else for (int k = 0; k < C; ++k) pdf[k] = 0.f;
         rec[5 + s] = 0.f;
     }
 }
@@ -288,8 +268,8 @@ __global__ void __launch_bounds__(kThreads) k_prune_fold(const PruneArgs a)
 __global__ void __launch_bounds__(kThreads) k_prune_clear(const PruneArgs a)
 {
     __shared__ uint8_t gone[kThreads];
-    const uint32_t E = 7u + 2u * (uint32_t)a.C, K = 2u * (uint32_t)a.C;
-    const size_t all = nodes_of(a) * (size_t)a.T, n0 = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kThreads;
+    const uint32_t E = (uint32_t)a.E(), K = 2u * (uint32_t)a.C;
+    const size_t all = a.nodes(), n0 = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kThreads;
     if (n0 >= all) return;                              // (the workgroup as one)
     const uint32_t have = all - n0 < (size_t)kThreads ? (uint32_t)(all - n0) : (uint32_t)kThreads;
     const bool g = threadIdx.x < have && !(a.state[n0 + threadIdx.x] & kReachAfter);
@@ -303,14 +283,12 @@ __global__ void __launch_bounds__(kThreads) k_prune_clear(const PruneArgs a)
         if (gone[i / K]) cnts[i] = 0ull;
 }
 
-bool bad_shape(int T, int D, int C) { return T < 1 || D < 1 || D > kMaxDepth || C < 1 || C > 65535; }
-
 size_t state_bytes(size_t nodes) { return (nodes + 7) & ~(size_t)7; }
 
 // the workspace: state bytes, then sub, then meta
 void carve(PruneArgs &a, void *workspace)
 {
-    const size_t nodes = (size_t)a.T * ((((size_t)1) << a.D) - 1);
+    const size_t nodes = a.nodes();
     uint8_t *p = reinterpret_cast<uint8_t *>(workspace);
     a.state = p;
     a.sub = reinterpret_cast<u64 *>(p + state_bytes(nodes));
@@ -332,8 +310,8 @@ extern "C" {
 
 size_t rdf_labels_prune_workspace_bytes(int n_trees, int max_depth, int n_classes)
 {
-    if (bad_shape(n_trees, max_depth, n_classes)) return 0;
-    const size_t nodes = (size_t)n_trees * (((size_t)1 << max_depth) - 1);
+    if (bad_forest_shape(n_trees, max_depth, n_classes)) return 0;
+    const size_t nodes = ForestShape{n_trees, max_depth, n_classes}.nodes();
     return state_bytes(nodes) + nodes * (size_t)n_classes * sizeof(uint64_t) + nodes * sizeof(Meta);
 }
 
@@ -341,27 +319,23 @@ int rdf_labels_prune_plan(const float *forest, int n_trees, int max_depth, int n
                           uint64_t cost_per_leaf, uint64_t min_count, int max_levels, void *workspace, uint64_t *report,
                           void *stream)
 {
-    if (bad_shape(n_trees, max_depth, n_classes) || cost_per_leaf >= (1ull << 32) || max_levels < 1 || max_levels > max_depth)
+    if (bad_forest_shape(n_trees, max_depth, n_classes) || cost_per_leaf >= (1ull << 32) || max_levels < 1 || max_levels > max_depth)
         return RDF_ERR_BAD_ARG;
     if (!forest || !counts || !workspace || !report) return RDF_ERR_NULL_PTR;
     if (misaligned(forest, 4) || misaligned(counts, 8) || misaligned(workspace, 8) || misaligned(report, 8)) return RDF_ERR_BAD_ARG;
 
-    PruneArgs a;
+    PruneArgs a = {{n_trees, max_depth, n_classes}};
     a.forest = const_cast<float *>(forest);             // (no kernel of the plan writes through it)
     a.counts = reinterpret_cast<u64 *>(const_cast<uint64_t *>(counts));
     a.report = reinterpret_cast<u64 *>(report);
-    a.T = n_trees;
-    a.D = max_depth;
-    a.C = n_classes;
     a.max_levels = max_levels;
     a.cost = cost_per_leaf;
     a.min_count = min_count;
     carve(a, workspace);
     hipStream_t s = S(stream);
-    const size_t nodes = (size_t)n_trees * (((size_t)1 << max_depth) - 1);
     hipError_t err = hipMemsetAsync(report, 0, 8 * sizeof(uint64_t), s);
     if (err != hipSuccess) return (int)err;
-    err = hipMemsetAsync(a.state, 0, state_bytes(nodes), s);
+    err = hipMemsetAsync(a.state, 0, state_bytes(a.nodes()), s);
     if (err != hipSuccess) return (int)err;
     const bool deep = a.top < max_depth;
     const dim3 roots = grid_of((size_t)n_trees << a.top);
@@ -375,25 +349,19 @@ int rdf_labels_prune_plan(const float *forest, int n_trees, int max_depth, int n
 int rdf_labels_prune_apply(float *forest, int n_trees, int max_depth, int n_classes, uint64_t *counts, const void *workspace,
                            void *stream)
 {
-    if (bad_shape(n_trees, max_depth, n_classes)) return RDF_ERR_BAD_ARG;
+    if (bad_forest_shape(n_trees, max_depth, n_classes)) return RDF_ERR_BAD_ARG;
     if (!forest || !counts || !workspace) return RDF_ERR_NULL_PTR;
     if (misaligned(forest, 4) || misaligned(counts, 8) || misaligned(workspace, 8)) return RDF_ERR_BAD_ARG;
 
-    PruneArgs a;
+    PruneArgs a = {{n_trees, max_depth, n_classes}};     // (report, cost and min_count, the plan's: zero)
     a.forest = forest;
     a.counts = reinterpret_cast<u64 *>(counts);
-    a.report = nullptr;
-    a.T = n_trees;
-    a.D = max_depth;
-    a.C = n_classes;
     a.max_levels = max_depth;
-    a.cost = a.min_count = 0ull;
     carve(a, const_cast<void *>(workspace));
     hipStream_t s = S(stream);
-    const size_t per_tree = ((size_t)1 << max_depth) - 1, nodes = (size_t)n_trees * per_tree;
     if (max_depth > 1)
-        hipLaunchKernelGGL(k_prune_fold, grid_of(((per_tree >> 1) * (size_t)n_trees + kThreads - 1) / kThreads), dim3(kThreads), 0, s, a);
-    hipLaunchKernelGGL(k_prune_clear, grid_of((nodes + kThreads - 1) / kThreads), dim3(kThreads), 0, s, a);
+        hipLaunchKernelGGL(k_prune_fold, grid_of(((a.N() >> 1) * (size_t)n_trees + kThreads - 1) / kThreads), dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(k_prune_clear, grid_of((a.nodes() + kThreads - 1) / kThreads), dim3(kThreads), 0, s, a);
     return (int)hipGetLastError();
 }
 

@@ -1,10 +1,10 @@
 // forest_refit_hip.hip -- leaf refit: the leaf distributions of a trained forest re-estimated from labelled depth frames,
 // with the tree structure left as it is.  rdf_labels_refit_count walks every labelled pixel through every tree of the
-// reference-layout forest (float32 [T][2^D - 1][7 + 2C], what DecisionForest.forest_cu holds) exactly as inference walks it
-// and ends in a 64-bit histogram over (tree, node, side, class) where inference ends in an argmax;
-// rdf_labels_refit_apply turns the histogram into leaf PDFs.  Built into librdf_labels.so.  The contract (rules R) is in
-// include/rdf_labels.h and tests/refit_numpy.py restates it; all counts are integers, so no result depends on the order
-// in which pixels are visited and two runs give the same bytes.
+// reference-layout forest exactly as inference walks it and ends in a 64-bit histogram over (tree, node, side, class) where
+// inference ends in an argmax; rdf_labels_refit_apply turns the histogram into leaf PDFs.  Built into librdf_labels.so.  The
+// forest's layout, the flag rule, the walk (walk_tree) and the ancestor's PDF are in rdf_forest_ref.hpp, shared with the
+// pruning and the posterior.  The contract (rules R) is in include/rdf_labels.h and tests/refit_numpy.py restates it; all
+// counts are integers, so no result depends on the order in which pixels are visited and two runs give the same bytes.
 //
 // k_refit_count: one lane per pixel, a wave takes 64 consecutive pixels and leaves at once when none of them carries a label
 // (about 85 % of a frame).  A lane walks the trees one after the other; the level loop runs while any lane of the wave is
@@ -29,8 +29,7 @@
 #include <stdint.h>
 
 #include "../../include/rdf_labels.h"
-#include "rdf_device.hpp"
-#include "rdf_kernel_util.hpp"
+#include "rdf_forest_ref.hpp"
 
 namespace {
 
@@ -40,14 +39,12 @@ constexpr int kLdsCells = 4096;       // 16 KB of 32-bit counters
 constexpr int kAggIters = 4;          // distinct keys a wave aggregates before its remaining lanes add one each
 constexpr int kTableBits = 11;        // 2048 (cell, count) pairs of 32 bits: another 16 KB
 constexpr uint32_t kNoTag = 0xffffffffu;
-constexpr int kMaxDepth = 30;
 
-struct CountArgs {
+struct CountArgs : ForestShape {
     const uint16_t *depth, *labels;
     uint32_t n_px, pix;               // all pixels (< 2^31), pixels of one image
     int W, H;
     const float *forest;
-    int T, D, C;
     int lds_levels;                   // L
     float scale;
     u64 *counts, *totals;
@@ -74,11 +71,10 @@ __global__ void __launch_bounds__(kThreads) k_refit_count(const CountArgs a)
     __shared__ uint32_t hist[kLdsCells];
     __shared__ uint32_t tags[1 << kTableBits], vals[1 << kTableBits];
     const int tid = threadIdx.x, lane = tid & 63;
-    const int T = a.T, D = a.D, C = a.C, E = 7 + 2 * C, L = a.lds_levels;
-    const size_t N = ((size_t)1 << D) - 1;
+    const int T = a.T, C = a.C, L = a.lds_levels;
     const uint32_t lds_nodes = (1u << L) - 1u;                      // per tree
     const uint32_t lds_cells = (uint32_t)T * lds_nodes * 2u * (uint32_t)C;
-    const bool use_table = (u64)T * N * 2u * (u64)C < (u64)kNoTag;  // a cell's index is its tag
+    const bool use_table = (u64)a.nodes() * 2u * (u64)C < (u64)kNoTag;   // a cell's index is its tag
     for (uint32_t i = tid; i < lds_cells; i += kThreads) hist[i] = 0u;
     for (uint32_t i = tid; i < (1u << kTableBits); i += kThreads) {
         tags[i] = kNoTag;
@@ -111,42 +107,21 @@ __global__ void __launch_bounds__(kThreads) k_refit_count(const CountArgs a)
         if (__ballot(live) == 0ull) continue;
         const uint32_t img = i / a.pix, rem = i - img * a.pix;
         const int y = (int)(rem / (uint32_t)a.W), x = (int)(rem - (uint32_t)y * (uint32_t)a.W);
-        const uint16_t *__restrict__ frame = a.depth + (size_t)img * a.pix;
-        const float df = (float)d;
+        const WalkPixel p = {a.depth + (size_t)img * a.pix, a.W, a.H, x, y, (float)d, a.scale};
 
         for (int t = 0; t < T; ++t) {
-            const float *__restrict__ tree = a.forest + (size_t)t * N * E;
-            uint32_t g = 0u, key = 0u;
-            bool walking = live, has_key = false;
-            for (int j = 0; j < D && __ballot(walking) != 0ull; ++j) {
-                if (!walking) continue;
-                const uint32_t n = ((1u << j) - 1u) + g;
-                const float *__restrict__ rec = tree + (size_t)n * E;
-                const float s = a.scale;
-                // `uv_scale * u.x / d_f`: one multiply and one IEEE divide, both rounded to nearest (no contraction, no
-                // reciprocal: the library's flags); floor with saturation, NaN -> 0; a wrapping add
-                const int ux = offset_coord(x, s * rec[0], df), uy = offset_coord(y, s * rec[1], df);
-                const int vx = offset_coord(x, s * rec[2], df), vy = offset_coord(y, s * rec[3], df);
-                const float f = depth_or_no_pixel<uint32_t>(frame, a.W, a.H, ux, uy) - depth_or_no_pixel<uint32_t>(frame, a.W, a.H, vx, vy);
-                const uint32_t side = f < rec[4] ? 0u : 1u;         // NaN goes right
-                if (floor_i32(rec[5 + side]) != -1) {               // a leaf slot, at every level
-                    walking = false;
-                    if (j < L) {
-                        atomicAdd(&hist[(((uint32_t)t * lds_nodes + n) * 2u + side) * (uint32_t)C + l], 1u);
-                    } else {
-                        has_key = true;
-                        key = (n * 2u + side) * (uint32_t)C + l;    // < 2^32: the launcher checks
-                    }
-                } else if (j == D - 1) {                            // the flag says "go on" and there is no level to go to
-                    walking = false;
-                    ++n_fell;
-                } else {
-                    g = g * 2u + side;
-                }
-            }
+            uint32_t key = 0u;
+            bool has_key = false;
+            walk_tree(a.forest + a.rec(t, 0), a.D, a.E(), p, live,
+                      [&](int j, uint32_t n, uint32_t side, const float *) {
+                          has_key = j >= L;                               // below the LDS histogram's levels
+                          if (has_key) key = (n * 2u + side) * (uint32_t)C + l;    // < 2^32: the launcher checks
+                          else atomicAdd(&hist[(((uint32_t)t * lds_nodes + n) * 2u + side) * (uint32_t)C + l], 1u);
+                      },
+                      [&] { ++n_fell; });
             u64 todo = __ballot(has_key);
             if (todo == 0ull) continue;
-            const size_t cell0 = (size_t)t * N * 2u * (size_t)C;   // of the tree's first cell in counts
+            const size_t cell0 = a.cell(t, 0, 0);                   // of the tree's first cell in counts
             for (int it = 0; it < kAggIters && todo != 0ull; ++it) {
                 const KeyGroup grp = wave_key_group(todo, (int)key, has_key);
                 if (lane == grp.src) add_deep(tags, vals, use_table, a.counts, cell0 + (uint32_t)grp.key, (uint32_t)__popcll(grp.lanes));
@@ -170,20 +145,20 @@ __global__ void __launch_bounds__(kThreads) k_refit_count(const CountArgs a)
         const uint32_t v = hist[i];
         if (v) {
             const uint32_t t = i / per_tree;
-            atomicAdd(a.counts + (size_t)t * N * 2u * (size_t)C + (i - t * per_tree), (u64)v);
+            atomicAdd(a.counts + a.cell(t, 0, 0) + (i - t * per_tree), (u64)v);
         }
     }
     for (uint32_t i = tid; i < (1u << kTableBits); i += kThreads)
         if (vals[i]) atomicAdd(a.counts + tags[i], (u64)vals[i]);
 }
 
-struct ApplyArgs {
+struct ApplyArgs : ForestShape {
     float *forest;
     const u64 *counts;
     u64 *sub;                         // [T][N][C], NULL without the ancestor fallback
     uint8_t *reach;                   // [T][N]
     u64 *report;
-    int T, D, C, level;
+    int level;
     int fallback;
     u64 min_count;
 };
@@ -192,16 +167,16 @@ struct ApplyArgs {
 // sums (nothing at level D - 1, whose "go on" sides lead nowhere).  The level below is complete: launches are ordered.
 __global__ void __launch_bounds__(kThreads) k_refit_subtree(const ApplyArgs a)
 {
-    const int C = a.C, E = 7 + 2 * C, j = a.level;
-    const size_t N = ((size_t)1 << a.D) - 1, level_nodes = (size_t)1 << j;
+    const int C = a.C, j = a.level;
+    const size_t level_nodes = (size_t)1 << j;
     const size_t idx = (size_t)blockIdx.x * kThreads + threadIdx.x;
     if (idx >= level_nodes * (size_t)a.T) return;
     const size_t t = idx >> j, g = idx & (level_nodes - 1), n = level_nodes - 1 + g;
-    const float *rec = a.forest + (t * N + n) * E;
-    const u64 *own = a.counts + (t * N + n) * 2 * C;
-    u64 *dst = a.sub + (t * N + n) * C;
-    const bool leaf0 = floor_i32(rec[5]) != -1, leaf1 = floor_i32(rec[6]) != -1, last = j == a.D - 1;
-    const u64 *child = a.sub + (t * N + (2 * level_nodes - 1 + 2 * g)) * C;      // the left child's sums; the right one's follow
+    const float *rec = a.forest + a.rec(t, n);
+    const u64 *own = a.counts + a.cell(t, n, 0);
+    u64 *dst = a.sub + a.row(t, n);
+    const bool leaf0 = is_leaf_slot(rec, 0), leaf1 = is_leaf_slot(rec, 1), last = j == a.D - 1;
+    const u64 *child = a.sub + a.row(t, 2 * n + 1);                // the left child's sums; the right one's follow
     for (int c = 0; c < C; ++c) {
         const u64 v0 = leaf0 ? own[c] : last ? 0ull : child[c];
         const u64 v1 = leaf1 ? own[C + c] : last ? 0ull : child[C + c];
@@ -209,52 +184,32 @@ __global__ void __launch_bounds__(kThreads) k_refit_subtree(const ApplyArgs a)
     }
 }
 
-// One level, top-down.  A lane owns node n of tree t: reachable iff it is the root or its parent is reachable and the
-// parent's flag towards it floors to -1.  Reachable leaf slots get their PDF by rule R3.
+// One level, top-down.  A lane owns node n of tree t and learns from its parent whether it is reachable (the root is).
+// Reachable leaf slots get their PDF by rule R3.
 __global__ void __launch_bounds__(kThreads) k_refit_apply(const ApplyArgs a)
 {
-    const int C = a.C, E = 7 + 2 * C, j = a.level;
-    const size_t N = ((size_t)1 << a.D) - 1, level_nodes = (size_t)1 << j;
+    const int C = a.C, j = a.level;
+    const size_t level_nodes = (size_t)1 << j;
     const size_t idx = (size_t)blockIdx.x * kThreads + threadIdx.x;
     uint32_t n_own = 0u, n_anc = 0u, n_kept = 0u;
     if (idx < level_nodes * (size_t)a.T) {
         const size_t t = idx >> j, g = idx & (level_nodes - 1), n = level_nodes - 1 + g;
-        float *rec = a.forest + (t * N + n) * E;
-        bool reachable = true;
-        if (j > 0) {
-            const size_t parent = (level_nodes >> 1) - 1 + (g >> 1);
-            reachable = a.reach[t * N + parent] != 0 && floor_i32(a.forest[(t * N + parent) * E + 5 + (g & 1)]) == -1;
-        }
-        a.reach[t * N + n] = reachable ? 1 : 0;
+        float *rec = a.forest + a.rec(t, n);
+        const bool reachable = is_reachable(a, a.forest, t, n, [&](size_t parent) { return a.reach[parent] != 0; });
+        a.reach[a.at(t, n)] = reachable ? 1 : 0;
         if (reachable) {
             for (int s = 0; s < 2; ++s) {
-                if (floor_i32(rec[5 + s]) == -1) continue;
-                const u64 *src = a.counts + ((t * N + n) * 2 + s) * C;
-                u64 sum = 0ull;
-                for (int c = 0; c < C; ++c) sum += src[c];
-                if (sum >= a.min_count) {
+                if (!is_leaf_slot(rec, s)) continue;
+                SubRow src = {a.counts + a.cell(t, n, s), 0ull};
+                for (int c = 0; c < C; ++c) src.sum += src.row[c];
+                if (src.sum >= a.min_count) {
                     ++n_own;
                 } else {
-                    src = nullptr;
-                    if (a.fallback == RDF_REFIT_FALLBACK_ANCESTOR) {        // the nearest ancestor-or-self with enough pixels
-                        size_t an = n;
-                        for (int lv = j; lv >= 0; --lv) {
-                            const u64 *cand = a.sub + (t * N + an) * C;
-                            sum = 0ull;
-                            for (int c = 0; c < C; ++c) sum += cand[c];
-                            if (sum >= a.min_count) {
-                                src = cand;
-                                break;
-                            }
-                            an = (an - 1) >> 1;     // (not followed at the root: lv ends the loop)
-                        }
-                    }
-                    if (src) ++n_anc; else ++n_kept;
+                    src.row = nullptr;
+                    if (a.fallback == RDF_REFIT_FALLBACK_ANCESTOR) src = nearest_ancestor(a, a.sub, t, n, j, a.min_count);
+                    if (src.row) ++n_anc; else ++n_kept;
                 }
-                if (src) {
-                    const float den = (float)sum;                          // uint64 -> fp32, round to nearest even
-                    for (int c = 0; c < C; ++c) rec[7 + s * C + c] = (float)src[c] / den;
-                }
+                if (src.row) write_pdf(rec + 7 + s * C, src.row, src.sum, C);
             }
         }
     }
@@ -268,8 +223,6 @@ __global__ void __launch_bounds__(kThreads) k_refit_apply(const ApplyArgs a)
     }
 }
 
-bool bad_shape(int T, int D, int C) { return T < 1 || D < 1 || D > kMaxDepth || C < 1 || C > 65535; }
-
 }  // namespace
 
 extern "C" {
@@ -278,9 +231,10 @@ int rdf_labels_refit_count(const uint16_t *depth, const uint16_t *labels, int n_
                            int n_trees, int max_depth, int n_classes, float scale_factor, uint64_t *counts, uint64_t *totals,
                            void *stream)
 {
-    if (n_img < 0 || dim_x < 0 || dim_y < 0 || bad_shape(n_trees, max_depth, n_classes)) return RDF_ERR_BAD_ARG;
+    if (n_img < 0 || dim_x < 0 || dim_y < 0 || bad_forest_shape(n_trees, max_depth, n_classes)) return RDF_ERR_BAD_ARG;
+    CountArgs a = {{n_trees, max_depth, n_classes}};
     // a (slot, class) index within one tree is 32-bit
-    if ((((unsigned long long)1 << max_depth) - 1) * 2ull * (unsigned long long)n_classes >= (1ull << 32)) return RDF_ERR_TOO_LARGE;
+    if ((u64)a.N() * 2ull * (u64)n_classes >= (1ull << 32)) return RDF_ERR_TOO_LARGE;
     if (n_img == 0 || dim_x == 0 || dim_y == 0) return RDF_OK;
     if (!depth || !labels || !forest || !counts || !totals) return RDF_ERR_NULL_PTR;
     const long long pix = (long long)dim_x * dim_y;
@@ -288,7 +242,6 @@ int rdf_labels_refit_count(const uint16_t *depth, const uint16_t *labels, int n_
     if (misaligned(depth, 2) || misaligned(labels, 2) || misaligned(forest, 4) || misaligned(counts, 8) || misaligned(totals, 8))
         return RDF_ERR_BAD_ARG;
 
-    CountArgs a;
     a.depth = depth;
     a.labels = labels;
     a.n_px = (uint32_t)(pix * n_img);
@@ -296,9 +249,6 @@ int rdf_labels_refit_count(const uint16_t *depth, const uint16_t *labels, int n_
     a.W = dim_x;
     a.H = dim_y;
     a.forest = forest;
-    a.T = n_trees;
-    a.D = max_depth;
-    a.C = n_classes;
     a.scale = scale_factor;
     a.counts = reinterpret_cast<u64 *>(counts);
     a.totals = reinterpret_cast<u64 *>(totals);
@@ -314,30 +264,26 @@ int rdf_labels_refit_count(const uint16_t *depth, const uint16_t *labels, int n_
 
 size_t rdf_labels_refit_workspace_bytes(int n_trees, int max_depth, int n_classes)
 {
-    if (bad_shape(n_trees, max_depth, n_classes)) return 0;
-    const size_t nodes = (size_t)n_trees * (((size_t)1 << max_depth) - 1);
-    return nodes * (size_t)n_classes * sizeof(uint64_t) + ((nodes + 7) & ~(size_t)7);
+    if (bad_forest_shape(n_trees, max_depth, n_classes)) return 0;
+    const ForestShape f = {n_trees, max_depth, n_classes};
+    return f.nodes() * (size_t)n_classes * sizeof(uint64_t) + ((f.nodes() + 7) & ~(size_t)7);
 }
 
 int rdf_labels_refit_apply(float *forest, int n_trees, int max_depth, int n_classes, const uint64_t *counts, uint64_t min_count,
                            int fallback, void *workspace, uint64_t *report, void *stream)
 {
-    if (bad_shape(n_trees, max_depth, n_classes) || min_count < 1 ||
+    if (bad_forest_shape(n_trees, max_depth, n_classes) || min_count < 1 ||
         (fallback != RDF_REFIT_FALLBACK_KEEP && fallback != RDF_REFIT_FALLBACK_ANCESTOR))
         return RDF_ERR_BAD_ARG;
     if (!forest || !counts || !workspace || !report) return RDF_ERR_NULL_PTR;
     if (misaligned(forest, 4) || misaligned(counts, 8) || misaligned(workspace, 8) || misaligned(report, 8)) return RDF_ERR_BAD_ARG;
 
-    const size_t nodes = (size_t)n_trees * (((size_t)1 << max_depth) - 1);
-    ApplyArgs a;
+    ApplyArgs a = {{n_trees, max_depth, n_classes}};
     a.forest = forest;
     a.counts = reinterpret_cast<const u64 *>(counts);
     a.sub = reinterpret_cast<u64 *>(workspace);
-    a.reach = reinterpret_cast<uint8_t *>(workspace) + nodes * (size_t)n_classes * sizeof(uint64_t);
+    a.reach = reinterpret_cast<uint8_t *>(a.sub + a.nodes() * (size_t)n_classes);
     a.report = reinterpret_cast<u64 *>(report);
-    a.T = n_trees;
-    a.D = max_depth;
-    a.C = n_classes;
     a.fallback = fallback;
     a.min_count = min_count;
     hipStream_t s = S(stream);

@@ -115,9 +115,17 @@ def test_the_shared_modes_body_is_in_the_build_id_of_both_its_libraries(rdf, tmp
     """csrc/rdf_modes.hpp is compiled into librdf_hip.so (k_mean_shift_fused) and librdf_labels.so (k_weighted_modes): it is a
     header of both, and a change to it changes both ids -- a librdf_hip.so from before the change would otherwise pass the
     build-id check.  (On a copy of the sources: nothing in the tree is touched.)"""
-    build, _ = _modules()
-    users = [name for name in LIBS if "rdf_modes.hpp" in map(os.path.basename, build.LIBRARIES[name].headers)]
+    users, in_tree, touched = _ids_after_touching("rdf_modes.hpp", tmp_path, monkeypatch)
     assert users == ["hip", "labels"]
+    assert touched["hip"] != in_tree["hip"] and touched["labels"] != in_tree["labels"]
+    assert touched["frontend"] == in_tree["frontend"]
+
+
+def _ids_after_touching(header, tmp_path, monkeypatch):
+    """The libraries that list `header`, every library's id in the tree, and every library's id on a copy of the sources in
+    which each user's copy of `header` has a line more."""
+    build, _ = _modules()
+    users = [name for name in LIBS if header in map(os.path.basename, build.LIBRARIES[name].headers)]
     in_tree = {name: build.source_id(name) for name in LIBS}
     copies = {}
     for name in LIBS:
@@ -128,11 +136,23 @@ def test_the_shared_modes_body_is_in_the_build_id_of_both_its_libraries(rdf, tmp
     monkeypatch.setattr(build, "LIBRARIES", copies)
     assert {name: build.source_id(name) for name in LIBS} == in_tree
     for name in users:
-        with open(tmp_path / name / "rdf_modes.hpp", "a") as f:
+        with open(tmp_path / name / header, "a") as f:
             f.write("// touched\n")
-    touched = {name: build.source_id(name) for name in LIBS}
-    assert touched["hip"] != in_tree["hip"] and touched["labels"] != in_tree["labels"]
-    assert touched["frontend"] == in_tree["frontend"]
+    return users, in_tree, {name: build.source_id(name) for name in LIBS}
+
+
+def test_the_reference_layout_forest_header_is_in_the_build_id_of_the_labels_library_alone(rdf, tmp_path, monkeypatch):
+    """csrc/rdf_forest_ref.hpp holds the walk of the refit, the pruning and the posterior, all of librdf_labels.so: the three
+    sources include it, it is a header of that library and of no other, and a change to it changes that id and leaves the
+    forest evaluation's and the front end's as they were."""
+    build, _ = _modules()
+    for src in ("forest_refit_hip.hip", "forest_prune_hip.hip", "forest_posterior_hip.hip"):
+        path, = [p for p in build.LIBRARIES["labels"].sources if os.path.basename(p) == src]
+        assert '#include "rdf_forest_ref.hpp"' in open(path).read(), src
+    users, in_tree, touched = _ids_after_touching("rdf_forest_ref.hpp", tmp_path, monkeypatch)
+    assert users == ["labels"]
+    assert touched["labels"] != in_tree["labels"]
+    assert touched["hip"] == in_tree["hip"] and touched["frontend"] == in_tree["frontend"]
 
 
 @pytest.mark.parametrize("name", LIBS)
