@@ -24,6 +24,7 @@ from .hand_model import HandModel  # noqa: F401
 from .hand_scene import HandSceneRenderer  # noqa: F401
 from .hand_state import HandState  # noqa: F401
 from .host_stream import HostFramesEvaluator  # noqa: F401
+from .joint_votes import JointVoter, VoteFitter, VoteTable  # noqa: F401
 from .pipeline import HandPipeline  # noqa: F401
 from .pose_fit import PoseFitter  # noqa: F401
 from .prune import ForestPruner  # noqa: F401
@@ -62,6 +63,6 @@ def install_reference_aliases(force=False):
 
 
 __all__ = ["DecisionTree", "DecisionForest", "LayeredDecisionForest", "DecisionTreeEvaluator", "DecisionTreeTrainer",
-           "GpuBuffer", "CalibratedPlane", "ColorLabeler", "RecordingConverter", "SceneRerender", "HandModel", "HandSceneRenderer", "StereoSensor", "PoseFitter", "LabelScorer", "Score", "ConfidenceScorer", "Calibration", "LeafRefitter", "ForestPruner", "FrameFrontEnd", "DepthPostFilter", "HandGrouping", "HandPipeline", "HandState", "BeatsSession", "WeightedModes", "HostFramesEvaluator",
+           "GpuBuffer", "CalibratedPlane", "ColorLabeler", "RecordingConverter", "SceneRerender", "HandModel", "HandSceneRenderer", "StereoSensor", "PoseFitter", "LabelScorer", "Score", "ConfidenceScorer", "Calibration", "LeafRefitter", "ForestPruner", "VoteFitter", "VoteTable", "JointVoter", "FrameFrontEnd", "DepthPostFilter", "HandGrouping", "HandPipeline", "HandState", "BeatsSession", "WeightedModes", "HostFramesEvaluator",
            "DeviceArray", "HipRuntime", "MAX_UINT16", "RdfError", "device_ptr", "get_runtime", "set_runtime",
            "to_device", "host_mapped_array", "library_path", "synth", "install_reference_aliases"]

@@ -242,6 +242,14 @@ BINDINGS = {
                                                _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float,
                                                _c_float, _c_void_p, _c_void_p, _c_int, _c_void_p]),
         "rdf_labels_weighted_modes_list_cap": (ctypes.c_uint32, []),
+        "rdf_labels_votes_count": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_int,
+                                            _c_float, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p]),
+        "rdf_labels_votes_fit": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_void_p, ctypes.c_uint64, ctypes.c_uint64,
+                                          _c_void_p, _c_void_p, _c_void_p]),
+        "rdf_labels_votes_workspace_bytes": (_c_size_t, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+        "rdf_labels_votes_cast": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int,
+                                           _c_float, _c_void_p, _c_int, _c_int, _c_int, ctypes.c_uint32, _c_void_p, _c_void_p,
+                                           _c_void_p]),
         "rdf_labels_abi_version": (_c_int, []),
         "rdf_labels_build_id": (ctypes.c_char_p, []),
         "rdf_labels_error_string": (ctypes.c_char_p, [_c_int]),

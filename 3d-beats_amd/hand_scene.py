@@ -86,6 +86,31 @@ class HandSceneRenderer:
         assert len(left) == len(t)
         return np.ascontiguousarray(np.concatenate([t, left], 1))
 
+    def fingertip_targets(self, poses, plane, left_poses=None):
+        """Host int32 [N, 5 or 10, 3] = (tx, ty, tz): where the end points of the fingertips of `poses` (thumb..pinky, then the
+        left hand's of `left_poses`) fall in the image of a camera whose table plane is `plane` -- the targets of
+        VoteFitter.add.  HandModel.fingertips in camera space, projected with this renderer's own focal length and principal
+        point in float64: tx = floor(f X / Z + ppx), ty alike, tz = round(Z) (numpy's rint).  (tx, ty) may lie outside the frame.  tz = 0, the
+        joint is absent, when Z is outside [z_near, z_far] or tz outside 1..65534."""
+        cam_from_plane = np.linalg.inv(np.asarray(plane, np.float64).reshape(4, 4))
+        tips = self.model.fingertips(poses, cam_from_plane)
+        if left_poses is not None:
+            left = self.left_model.fingertips(left_poses, cam_from_plane)
+            assert len(left) == len(tips)
+            tips = np.concatenate([tips, left], 1)
+        X, Y, Z = tips[..., 0], tips[..., 1], tips[..., 2]
+        seen = (Z >= self.z_near) & (Z <= self.z_far)
+        Zs = np.where(seen, Z, 1.)
+        tz = np.rint(Zs)
+        seen &= (tz >= 1.) & (tz <= 65534.)
+        lim = float(2 ** 31 - 1)
+        out = np.zeros(tips.shape, np.int32)
+        out[..., 0] = np.clip(np.floor(self.f * X / Zs + self.ppx), -lim, lim)
+        out[..., 1] = np.clip(np.floor(self.f * Y / Zs + self.ppy), -lim, lim)
+        out[..., 2] = np.where(seen, tz, 0.)
+        out[~seen, :2] = 0
+        return out
+
     def render(self, part_tforms, labels='fine', table=None, empty_depth=65535, seed=0, hole_rate=0., noise_amp=0,
                depth_out=None, labels_out=None, sensor=None):
         """part_tforms: host float32 [N, 16, 12] (one hand) or [N, 32, 12] (two).  labels: see tri_labels.  table: None, or

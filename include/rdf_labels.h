@@ -712,6 +712,92 @@ int rdf_labels_weighted_modes(const uint16_t *labels, const uint16_t *weights, i
                               float ppx, float ppy, const float *plane, double *heights_out, int heights_stride, void *stream);
 uint32_t rdf_labels_weighted_modes_list_cap(void);
 
+/*
+ * Joint votes: a second use of a trained forest's structure.  Classification finds a fingertip only where pixels of its class
+ * are seen; here every leaf slot stores, per joint, a depth-normalised offset towards the joint, every hand pixel of a frame,
+ * whatever its label, casts the votes of the leaf slots it reaches into a coarse accumulator per (frame, joint), and the joint
+ * is the accumulator's mode -- also where the joint itself is hidden.  rdf_labels_votes_count sums offsets on frames whose
+ * joints are known, rdf_labels_votes_fit turns the sums into a vote table, rdf_labels_votes_cast casts and finds the modes.
+ * The reference has no counterpart; the rules below are this library's own, tests/votes_numpy.py restates them, and the
+ * kernels match that bit for bit: all arithmetic is in integers, so no result depends on the order in which pixels are visited.
+ *
+ *   forest   float32 [T][N][E], the reference layout of the leaf refit above, with its leaf slots, rule R2's walk and rule R3's
+ *            "reachable".  1 <= T, 1 <= D <= 30, 1 <= C <= 65535 (the classes' PDFs are not read).
+ *   J        n_joints, 1 .. RDF_VOTES_MAX_JOINTS;  radius 0 .. RDF_VOTES_MAX_RADIUS.
+ *   sums     uint64 [T][N][2][J][5]: count, sum ox, sum oy, sum oz, sum (ox^2 + oy^2).  The three signed sums are kept in two's
+ *            complement: the adds wrap.  totals uint64 [4].  Both 8-byte aligned.
+ *   votes    int32 [T][N][2][J][4] = (mx, my, mz, w), 16-byte aligned; w == 0: no vote.
+ *   targets  int32 [n_img][J][3] = (tx, ty, tz): pixel x, pixel y, depth units; 4-byte aligned.  (tx, ty) may lie outside the
+ *            frame.  Joint j is ABSENT from frame i iff tz <= 0 or tz >= 65535.
+ *   floordiv(a, b), b > 0: the integer floor of a / b (towards minus infinity), exact, in 64 bits.
+ *
+ * V1. Pixels of the count (rdf_labels_votes_count).  depth, labels uint16 [n_img][dim_y][dim_x].  For every pixel (x, y) of
+ *     image i, with l its label and d its depth:  l == 0: ignored; any other l is "hand" (the class is not used: l >= C is
+ *     fine).  d == 0 or d == 65535: totals[1] += 1, ignored.  Else totals[0] += 1 and the pixel walks every tree by rule R2,
+ *     unchanged.  A walk that is told to go on at level D - 1 does totals[2] += 1 and adds nothing.  At the leaf slot (t, n, s)
+ *     a walk ends in, for every joint j not absent from frame i: dx = tx - x, dy = ty - y; if |dx| > radius or |dy| > radius
+ *     the joint is skipped; else ox = floordiv(dx * d, 64), oy = floordiv(dy * d, 64), oz = tz - d, the five words of
+ *     sums[t][n][s][j] get +1, +ox, +oy, +oz, +(ox^2 + oy^2), and totals[3] += 1.  With radius <= 255, |ox| < 2^18, so one
+ *     square term is below 2^37 and a slot of fewer than 2^26 pixels cannot wrap the last word.
+ *     The call ADDS onto sums and totals; the caller zeroes them.  A negative dimension, T, D or C outside the ranges, J or
+ *     radius outside theirs or a misaligned pointer is RDF_ERR_BAD_ARG; zero pixels is a successful no-op; else a NULL pointer
+ *     is RDF_ERR_NULL_PTR; n_img * dim_y * dim_x >= 2^31 (callers split the batch by images) or N * 2 * J * 5 >= 2^32 is
+ *     RDF_ERR_TOO_LARGE.  Rejected arguments leave sums and totals untouched.  One launch, nothing read back: one lane per
+ *     pixel, a wave whose 64 pixels carry no label does nothing, five 64-bit atomics per (pixel, tree, joint in reach).
+ * V2. Votes (rdf_labels_votes_fit).  Every element of votes is written.  A slot that is not a reachable leaf slot gets zeros.
+ *     For a reachable leaf slot and joint j, with n the count:  n < min_count or n >= 2^26: (0, 0, 0, 0), DROPPED FOR SUPPORT
+ *     (the upper bound is what keeps the sum of squares from wrapping).  Else mx = floordiv(sum ox, n), my and mz alike (the
+ *     sums read as signed); var = max(0, floordiv(sum (ox^2 + oy^2), n) - (mx^2 + my^2)); var > max_var: (0, 0, 0, 0), DROPPED
+ *     FOR SPREAD; else w = 256 - floordiv(var * 256, max_var + 1), which is in 1..256, and the entry is (mx, my, mz, w).
+ *     min_count >= 1, max_var <= 2^38.  Sums that rule V1 cannot have made (a mean outside int32) give an unspecified entry,
+ *     never an access out of range.  report uint64 [4], overwritten: reachable leaf slots, (slot, joint) pairs with a vote,
+ *     pairs dropped for support, pairs dropped for spread; the last three sum to J times the first.  A shape, J, min_count or
+ *     max_var outside the ranges or a misaligned pointer (4 bytes for forest, 8 for sums and report, 16 for votes) is
+ *     RDF_ERR_BAD_ARG, N * 2 * J * 5 >= 2^32 RDF_ERR_TOO_LARGE, else a NULL pointer RDF_ERR_NULL_PTR; nothing is launched then.
+ *     One launch whatever the depth (a lane owns a node and climbs to the root for its reachability), stream-ordered, nothing
+ *     read back.  A table belongs to the forest's structure: after rdf_labels_prune_apply, fit again.
+ * V3. Pixels of the cast (rdf_labels_votes_cast).  depth uint16 [n_img][dim_y][dim_x]; with r = labels_reduce >= 1, Hl = dim_y
+ *     / r, Wl = dim_x / r, pixels are chosen as rule Q1 chooses them: label pixel (x, y) of image i reads depth pixel (xd, yd) =
+ *     (x * r, y * r).  gate uint16 [n_img][Hl][Wl] may be NULL; with a gate a pixel takes part iff its gate value is neither 0
+ *     nor 65535, so a label map, a composite or a gated posterior's label map serves as it is.  A pixel whose depth d is 0 or
+ *     65535 does not take part.  A pixel that takes part walks every tree by rule R2 at (xd, yd); a walk that falls off casts
+ *     nothing.
+ * V4. A vote.  At the slot reached, for every j whose w is in 1..256 (any other w, which rule V2 never writes, is no vote):
+ *     vx = xd + floordiv(128 * mx + d, 2 * d) and vy alike with my -- the inverse of V1's normalisation, rounded half up --
+ *     and vz = d + mz.  The vote is dropped if vx is outside [0, dim_x), vy outside [0, dim_y) or vz outside [1, 65534].  Else,
+ *     with a = cell_shift (0 .. RDF_VOTES_MAX_CELL_SHIFT), (cx, cy) = (vx >> a, vy >> a), Wa = ((dim_x - 1) >> a) + 1 and Ha
+ *     alike:  acc[i][j][cy][cx] += w (uint32) and zacc[i][j][cy][cx] += w * vz (uint64).
+ * V5. A joint.  Per (i, j), with b = box (0 .. RDF_VOTES_MAX_BOX):  S(cx, cy) = the sum of acc over |ex| <= b, |ey| <= b,
+ *     clipped to the grid, in 64 bits; best = max S; the winner is the first cell in row-major order (lowest cy, then lowest
+ *     cx) with S == best.  best < max(min_support, 1): joints_out[i][j] = (-1, -1, 0, 0).  Else, over the winner's clipped box:
+ *     X = floordiv(sum acc * (16 * (cx << a) + 8 * 2^a), best) and Y alike, in 1/16 pixel with a pixel's centre at +8 (the
+ *     renderer's half-pixel convention); Z = floordiv(sum zacc, best); joints_out[i][j] = (X, Y, Z, min(best, 2^31 - 1)).
+ *     joints_out int32 [n_img][J][4], 16-byte aligned; every element is written.
+ * V6. Workspace, arguments, launches.  rdf_labels_votes_workspace_bytes(n_img, dim_x, dim_y, n_joints, cell_shift) bytes, 8-byte
+ *     aligned: zacc, then acc; contents irrelevant before and after; 0 for a rejected shape.  A negative dimension, r < 1, a
+ *     shape, J, cell_shift or box outside the ranges or a misaligned pointer (2 bytes for depth and gate, 4 for forest, 16 for
+ *     votes and joints_out, 8 for workspace) is RDF_ERR_BAD_ARG; dim_x or dim_y above 65535, n_img * dim_y * dim_x >= 2^31,
+ *     n_img * J >= 2^31 or Hl * Wl * T * 256 >= 2^32 (acc could wrap, and best stays below 2^32) RDF_ERR_TOO_LARGE; zero frames
+ *     is a successful no-op; else a NULL pointer (gate excepted) RDF_ERR_NULL_PTR.  A rejected call launches nothing and writes
+ *     nothing.  An accepted call is one clear of the workspace, one vote launch (one lane per label pixel, a wave leaves at
+ *     once when none of its 64 pixels takes part, one 16-byte load and two atomics per vote) and one mode launch (one workgroup
+ *     per (frame, joint)) on the caller's stream; nothing is read back, and any number of frames goes in one call.
+ */
+#define RDF_VOTES_MAX_JOINTS 16
+#define RDF_VOTES_MAX_RADIUS 255
+#define RDF_VOTES_MAX_CELL_SHIFT 4
+#define RDF_VOTES_MAX_BOX 4
+int rdf_labels_votes_count(const uint16_t *depth, const uint16_t *labels, const int32_t *targets, int n_img, int dim_x, int dim_y,
+                           const float *forest, int n_trees, int max_depth, int n_classes, float scale_factor, int n_joints,
+                           int radius, uint64_t *sums, uint64_t *totals, void *stream);
+int rdf_labels_votes_fit(const float *forest, int n_trees, int max_depth, int n_classes, int n_joints, const uint64_t *sums,
+                         uint64_t min_count, uint64_t max_var, int32_t *votes, uint64_t *report, void *stream);
+size_t rdf_labels_votes_workspace_bytes(int n_img, int dim_x, int dim_y, int n_joints, int cell_shift);
+int rdf_labels_votes_cast(const uint16_t *depth, int n_img, int dim_x, int dim_y, const uint16_t *gate, int labels_reduce,
+                          const float *forest, int n_trees, int max_depth, int n_classes, float scale_factor, const int32_t *votes,
+                          int n_joints, int cell_shift, int box, uint32_t min_support, void *workspace, int32_t *joints_out,
+                          void *stream);
+
 int rdf_labels_abi_version(void);
 const char *rdf_labels_build_id(void);
 const char *rdf_labels_error_string(int code);
