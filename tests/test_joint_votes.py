@@ -8,6 +8,7 @@ import importlib
 import numpy as np
 import pytest
 
+import mutants
 import refit_numpy as rn
 import votes_cases as vc
 import votes_numpy as vn
@@ -227,6 +228,232 @@ def test_rejected_arguments_launch_nothing(rdf):
     for name in ("depth", "forest", "votes", "workspace", "out"):
         assert cs(**{name: None}) == NULL
     assert cast(None, 0, 8, 8, None, 1, None, 2, 4, 3, 1., None, 5, 2, 1, 1, None, None, None) == 0        # zero frames: a no-op
+
+
+# ------------------------------------------------------------------ CPU: the newer cases -------------------------------------
+def test_the_tie_layouts_are_worked_by_hand():
+    """Every layout's joint as TIE_LAYOUTS states it, and the reading that each layout is there to tell from the rule."""
+    m = vc.TIES
+    assert (m["H"] * m["W"], vn.grid(m["H"], 0) * vn.grid(m["W"], 0)) == (800, 800) and 800 > 2 * 256     # a thread meets three cells and more
+    assert vc._yx(4, 6, 100, 300, 44, 556) == ((0, 4), (0, 6), (2, 20), (7, 20), (1, 4), (13, 36))
+    assert (300 - 256, 556 - 512) == (44, 44) and 100 > 300 - 256                 # cell 300 and cell 556 are thread 44's
+    for name, (shift, box, pixels, want) in vc.TIE_LAYOUTS.items():
+        depth, forest, votes, gate, shift, box = vc.tie_case(name)
+        acc, zacc = vn.cast(depth, forest, votes, gate=gate, shift=shift)
+        assert int(acc.sum()) == 100 * len(pixels) and int(zacc.sum()) == 7000 * len(pixels), name
+        assert tuple(vn.modes(acc, zacc, shift, box, 1)[0, 0].tolist()) == want, name
+        S = np.array([[int(acc[0, 0, max(cy - box, 0):cy + box + 1, max(cx - box, 0):cx + box + 1].sum()) for cx in range(acc.shape[3])]
+                      for cy in range(acc.shape[2])])
+        ties = np.argwhere(S == S.max())
+        assert len(ties) >= 2 or "largest cell" in name, name                     # equal best sums
+        if "largest cell" in name:
+            cy, cx = np.unravel_index(np.argmax(acc[0, 0]), acc.shape[2:])
+            wy, wx = ties[0]
+            assert acc[0, 0].max() == 400 and S.max() == 900 and (abs(cy - wy) > box or abs(cx - wx) > box), name
+    three = vc.TIE_LAYOUTS["three cells, the middle one leftmost"][2]
+    assert sorted(three)[1] == (3, 2) == min(three, key=lambda p: (p[1], p[0]))   # the middle one in row-major order, the first in column-major
+    # the two border layouts under the other order: the other tie wins, whose box another border clips
+    d, f, v, g, shift, box = vc.tie_case("box 1: equal sums under the top and on the left border")
+    assert vc.mutant("column-major ties").vote(d, f, v, gate=g, shift=shift, box=box)[0, 0].tolist() == [13, 168, 70, 300]       # (0, 10): columns 0..1
+    d, f, v, g, shift, box = vc.tie_case("box 1: equal sums on the left and the right border")
+    assert vc.mutant("last tie wins").vote(d, f, v, gate=g, shift=shift, box=box)[0, 0].tolist() == [(632 + 632 + 616) // 3, 184, 70, 300]   # (39, 11): columns 38..39
+    acc, _ = vn.cast(d, f, v, gate=g, shift=shift)
+    assert acc[0, 0].reshape(-1)[10 * 40 - 1] == 0 and acc[0, 0].reshape(-1)[11 * 40 - 1] == 100       # in memory, left of (0, 11) lies (39, 10): a vote
+
+
+def test_the_new_cases_contain_what_they_are_meant_to():
+    # a box sum above 2^31 - 1: the closed form against the restatement's cast at T = 2 on 48 x 48
+    m = vc.SUM
+    assert vc.SUM_BEST == 2149908480 and (1 << 31) - 1 < vc.SUM_BEST < 1 << 32 and m["H"] // 16 * (m["W"] // 16) == 81
+    depth, forest, votes = vc.sum_case(2, 48, 48)
+    acc, zacc = vn.cast(depth, forest, votes, shift=m["shift"])
+    want = vc.full_grid(48, 48, 2, m["d"], m["mz"], m["shift"])
+    assert mutants.same([acc, zacc], list(want)) and acc[0, 0, 1, 1] == 256 * 2 * 256
+    acc, zacc = vc.full_grid(m["H"], m["W"], m["T"], m["d"], m["mz"], m["shift"])
+    assert int(acc.sum(dtype=np.uint64)) == vc.SUM_BEST and int(acc[0, 0, 0, 0]) == 256 * 405 * 256 == 26542080
+    got = [vn.modes(acc, zacc, m["shift"], box, support)[0, 0].tolist() for box, support in vc.SUM_RUNS]
+    assert got == [[1152, 1152, 1007, 2147483647], [128, 128, 1007, 26542080], [1152, 1152, 1007, 2147483647], [-1, -1, 0, 0]]
+    assert vn.M64 > 81 * 26542080 * (16 * 128 + 128) > 1 << 32                  # sx needs 64 bits
+    # 128 m + d on both sides of +-2^31, column by column
+    depth, forest, votes, gate = vc.wide_case()
+    num = lambda j, i: 128 * vc.WIDE_JOINTS[j][0] + vc.WIDE_PIXELS[i][1]          # noqa: E731
+    assert [num(0, 0), num(0, 1), num(1, 2), num(1, 3)] == [2 ** 31 - 1, 2 ** 31, -2 ** 31 + 1, -2 ** 31]
+    moved = lambda j, i: vc.WIDE_PIXELS[i][0] + vn.vote_pixels(vc.WIDE_JOINTS[j][0], vc.WIDE_PIXELS[i][1])     # noqa: E731
+    assert [moved(0, 0), moved(0, 1), moved(1, 2), moved(1, 3)] == [16431, 16447, 2591, 2607] and all(c % 16 == 15 for c in (16431, 16447, 2591, 2607))
+    assert moved(2, 3) == 19024 + 24624 >= 20000 and 19024 + ((128 * 25165824 + 65408 - 2 ** 32) // (2 * 65408)) == 10816 < 20000
+    got = vn.vote(depth, forest, votes, gate=gate, shift=vc.WIDE["shift"], box=0)
+    none = [-1, -1, 0, 0]
+    own = [[256 * (x >> 4) + 128, 128, d, 256] for x, d in vc.WIDE_PIXELS]       # joint 11: the pixel's own cell
+    assert got[0].tolist() == [[256 * 1026 + 128, 128, 65407, 9]] + [none] * 10 + [own[0]]
+    assert got[1].tolist() == [[256 * 1027 + 128, 128, 65408, 9]] + [none] * 10 + [own[1]]
+    assert got[2].tolist() == [none, [256 * 161 + 128, 128, 65409, 9]] + [none] * 9 + [own[2]]
+    assert got[3].tolist() == [none, [256 * 162 + 128, 128, 65408, 9]] + [none] * 9 + [own[3]]
+    assert votes[0, 0, 0, 6:11, 3].tolist() == [257, -1, -256, 2 ** 31 - 1, -2 ** 31]
+    # a fall-off in the second of three trees: three pixels fall off there and are summed in the first and the third
+    depth, labels, targets, forest = vc.middle_case()
+    sums, totals = vn.count(depth, labels, targets, forest, radius=vc.HAND["radius"])
+    assert totals.tolist() == [4, 1, 3, 7] and sums[:, 0, :, 0, 0].tolist() == [[2, 1], [0, 1], [3, 0]]
+    votes, report = vn.fit(forest, sums, **vc.MIDDLE_FIT)
+    assert report.tolist() == [5, 4, 1, 0] and votes[2, 0, 0, 0].tolist() == [1, 0, 6, 181] and not votes[1, 0, 0].any()
+    acc, _ = vn.cast(depth, forest, votes, gate=labels, shift=vc.HAND["shift"])
+    assert int(acc.sum()) == 2 * 226 + 4 * 181 + 2 * 256        # all four through the third tree; (0, 3)'s vote of the first leaves the frame
+    # min_support 0 on an accumulator without a vote
+    depth, forest, votes, gate_one, _ = vc.border_case()
+    got = vn.vote(depth, forest, votes, gate=gate_one, shift=0, box=0, min_support=0)
+    assert got[0, 1].tolist() == none and got[0, 8].tolist() == [88, 24, 70, 100]
+
+
+def test_the_sweep_cases_are_larger_than_one_sweep():
+    """forest_votes_hip.hip, lines 32 to 34: kThreads = 256, kMaxBlocks = 1024, kMaxModeBlocks = 65536."""
+    assert vc.SWEEP == 1024 * 256 == 262144 and vc.MODE_SWEEP == 65536
+    # count
+    depth, labels, targets, forest = vc.count_sweep_case()
+    pix = depth.shape[1] * depth.shape[2]
+    assert depth.shape == (2, 367, 401) and pix % 64 == 31 and depth.size == 294334 > vc.SWEEP and depth.size % 64 != 0
+    flat = np.flatnonzero(labels)
+    assert {0, vc.SWEEP - 1, vc.SWEEP, pix - 1, pix, depth.size - 1} <= set(flat.tolist()) and (pix - 1) // 64 == pix // 64
+    assert (flat < vc.SWEEP).sum() >= 40 and (flat >= vc.SWEEP).sum() >= 40 and len(flat) < 100
+    sums, totals = vn.count(depth, labels, targets, forest, radius=vc.COUNT_SWEEP["radius"])
+    late = labels.copy()
+    late.reshape(-1)[:vc.SWEEP] = 0
+    late_sums, late_totals = vn.count(depth, late, targets, forest, radius=vc.COUNT_SWEEP["radius"])
+    assert int(late_totals[3]) > 40 and int(totals[3]) > int(late_totals[3]) + 40 and int(totals[1]) > 0 and int(late_totals[1]) > 0
+    assert (late_sums[0, 0, :, 0, 0] > 0).all() and (sums[0, 0, :, :, 0] > late_sums[0, 0, :, :, 0]).all()       # both slots, both joints, both sweeps
+    assert int(sums[0, 0, :, 0, 0].sum()) == int(totals[0]) > int(sums[0, 0, :, 1, 0].sum()) > 0                    # joint 0 reaches every pixel
+    # fit
+    forest, sums, slots, leaf = vc.fit_sweep_case()
+    T, N = forest.shape[:2]
+    assert (T, N) == (5, 65535) and T * N == 327675 > vc.SWEEP and len(leaf) == 17 * T
+    node = lambda slot: slot[0] * N + slot[1]                                     # noqa: E731
+    assert sum(node(s) < vc.SWEEP for s in leaf) == 4 * 17 + 2 and sum(node(s) >= vc.SWEEP for s in leaf) == 15       # nodes 0 and 2 of tree 4 are before
+    named = {k: node(v) for k, v in slots.items()}
+    assert node(slots["unreachable"]) > vc.SWEEP and slots["unreachable"][:3] not in leaf and sums[slots["unreachable"]].all()
+    assert all((named[k] >= vc.SWEEP) == k.endswith("tree 4") for k in named if k != "unreachable") and len(named) == 9 * T + 1
+    votes, report = vn.fit(forest, sums, vc.FIT_SWEEP["min_count"], vc.FIT_SWEEP["max_var"])
+    assert report.tolist() == [17 * T, 6 * T, 17 * T - 6 * T - T, T] and np.count_nonzero(votes.any(axis=-1)) == 6 * T
+    for t in range(T):
+        assert votes[slots[f"at_min_count in tree {t}"]].tolist() == [1, 1, 1, 254] and votes[slots[f"negative_sums in tree {t}"]].tolist() == [-2, -3, -6667, 256]
+    # modes
+    depth, forest, votes, kind = vc.modes_sweep_case()
+    assert depth.shape == (4097, 2, 2) and depth.shape[0] * votes.shape[3] == 65552 > vc.MODE_SWEEP
+    want = vc.vote_by_kind(vn)
+    assert mutants.same(want[[0, 4096, 7]], vn.vote(depth[[0, 4096, 7]], forest, votes, shift=0, box=0))
+    assert (want[0] != want[4096]).any(axis=1).all() and (want[0, :, 3] > 0).sum() >= 12 and (want[4096, :, 3] > 0).all()       # every joint of the pair differs
+    assert len(set(kind.tolist())) == len(vc.MODE_KINDS) and (want[..., 3] == 0).any()
+
+
+# ------------------------------------------------------------------ CPU: do the device cases bite? --------------------------
+_true_outputs = {}
+
+
+def _true(name):
+    if name not in _true_outputs:
+        _true_outputs[name] = vc.outputs(vn, name)
+    return _true_outputs[name]
+
+
+def test_the_unchanged_copy_is_the_restatement_bit_for_bit():
+    copy = vc.mutant()
+    assert copy is not vn and copy.cast is not vn.cast and not any(vc.reads_differently(copy, f) for f in ("count", "fit", "vote"))
+    for name in vc.KILLS:
+        assert mutants.same(vc.outputs(copy, name, rerun=True), _true(name)), name
+    for m in vc.MUTANTS:                                    # every reading changes the code of some stage
+        assert any(vc.reads_differently(vc.mutant(m), f) for f in ("count", "fit", "vote")), m
+
+
+def test_a_mutant_that_no_longer_applies_fails_loudly():
+    with pytest.raises(AssertionError, match="0 times"):
+        mutants.load("votes_numpy", [("if S > best_:", "if S >= best:")])
+    with pytest.raises(AssertionError, match="2 times"):
+        mutants.load("votes_numpy", [("8 * (1 << shift)", "8")])
+
+
+@pytest.mark.parametrize("name", list(vc.KILLS))
+def test_each_mutant_changes_the_case_meant_for_it(name, capsys):
+    """A wrong reading of a rule that leaves a case's outputs unchanged would pass the GPU test of that case.  KILLS is exact:
+    a case that comes to notice more, or less, says so here."""
+    killed = {m: mutants.changed(vc.outputs(vc.mutant(m), name), _true(name)) for m in vc.MUTANTS}
+    with capsys.disabled():
+        print(f"\n  {name}: outputs changed by " + ", ".join(f"{m}: {k}" for m, k in killed.items() if k), end="")
+    assert {m for m, k in killed.items() if k} == set(vc.KILLS[name]), name
+    assert len(set(vc.KILLS[name])) == len(vc.KILLS[name])
+
+
+def test_every_mutant_is_met_by_some_case():
+    met = set(m for ms in vc.KILLS.values() for m in ms)
+    assert met | set(vc.EQUIVALENT) == set(vc.MUTANTS) and not met & set(vc.EQUIVALENT)
+    assert all(len(why) > 40 for why in vc.EQUIVALENT.values()) and len(vc.MUTANTS) >= 42 and vc.ADV_FIT == ADV_FIT
+    # set(KILLS) is the set of device cases: every GPU test of this file by name, every parametrisation but the scales
+    gpu_tests = {k[5:] for k, v in globals().items() if k.startswith("test_") and any(mk.name == "gpu" for mk in getattr(v, "pytestmark", []))}
+    assert {k.split("[")[0] for k in vc.KILLS} == gpu_tests and len(gpu_tests) >= 20
+    assert {k for k in vc.KILLS if "[" in k} == ({f"adversarial_count_fit_cast[{J}-{r}]" for J, r in vc.ADV_PARAMS}
+                                                 | {f"cast_cells_and_boxes[{s}-{b}]" for s, b in vc.CELLS_AND_BOXES}
+                                                 | {f"mode_ties[{n}]" for n in vc.TIE_LAYOUTS})
+    assert all(not vc.KILLS[k] and not vc.outputs(vn, k) for k in vc.DEVICE_ALONE) and set(vc.DEVICE_ALONE) <= set(vc.KILLS)
+    # the readings that survived the cases of the first pull request, each with the new case that meets it
+    for m, case in (("S in 32 bits", "box_sums_above_2_31"), ("support not clamped", "box_sums_above_2_31"),
+                    ("128 m + d in 32 bits", "votes_that_need_64_bits_and_weights_that_are_none"),
+                    ("w >= 1 votes", "votes_that_need_64_bits_and_weights_that_are_none"),
+                    ("negative w votes", "votes_that_need_64_bits_and_weights_that_are_none"),
+                    ("column-major ties", "mode_ties[three cells, the middle one leftmost]"), ("min_support 0 is 0", "min_support_0"),
+                    ("a fall-off ends the pixel's sums", "a_fall_off_in_a_middle_tree"), ("gate 65535 passes", "cast_reduce_gates_and_support")):
+        assert m in vc.KILLS[case], (m, case)
+
+
+# ------------------------------------------------------------------ CPU: arguments the Python layer rejects -------------------
+def test_a_vote_table_file_is_checked_on_load(rdf, tmp_path):
+    """Every rejection comes before anything is put on a device."""
+    T, D, C, J = 1, 2, 3, 2
+    good = np.concatenate([np.array([T, D, C, J], np.int32), np.zeros(T * 3 * 2 * J * 4, np.int32)])
+    cases = {"dtype": good.astype(np.int64), "short": good[:3], "size": good[:-1], "two tables": np.concatenate([good, good[4:]]),
+             "two dimensions": good.reshape(2, -1), "J": np.concatenate([np.array([T, D, C, 17], np.int32), np.zeros(T * 3 * 2 * 17 * 4, np.int32)]),
+             "D": np.array([1, 0, 3, 2], np.int32)}
+    for w in (257, -1):
+        bad = good.copy()
+        bad[4 + 3 + 4 * 5] = w                              # the weight of the sixth entry
+        cases[f"weight {w}"] = bad
+    for name, flat in cases.items():
+        path = str(tmp_path / f"{name.replace(' ', '_')}.npy")
+        np.save(path, flat)
+        with pytest.raises(AssertionError, match="weights outside" if name.startswith("weight") else "not a vote table"):
+            rdf.VoteTable.load(path)
+
+
+def test_shapes_and_types_the_python_layer_rejects(rdf, host_runtime):
+    """On the host stand-in: every assertion comes before the entry point is called, which the stand-in does not have."""
+    _mod("_build").build()
+    depth, labels, forest, _ = wc.adversarial_case()
+    n, H, W = depth.shape
+    f = _forest(rdf, forest)
+    d_cu, l_cu = rdf.to_device(depth), rdf.to_device(labels)
+    fitter = rdf.VoteFitter(f, 5)
+    targets = vc.targets_for(5, 255)
+    for bad in (dict(labels=rdf.to_device(labels[:, :-1])), dict(labels=rdf.to_device(labels[:1])), dict(targets=targets.astype(np.int64)),
+                dict(targets=vc.targets_for(16, 255)[:, :6]), dict(targets=targets[:1]), dict(depth=rdf.to_device(depth.astype(np.uint8)))):
+        args = dict(depth=d_cu, labels=l_cu, targets=targets)
+        args.update(bad)
+        with pytest.raises(AssertionError):
+            fitter.add(**args)
+    for J, radius in ((0, 255), (17, 255), (5, -1), (5, 256)):
+        with pytest.raises(AssertionError):
+            rdf.VoteFitter(f, J, radius=radius)
+    table = rdf.VoteTable(rdf.to_device(np.zeros(forest.shape[:2] + (2, 5, 4), np.int32)), rn.dims(forest))
+    voter = rdf.JointVoter(f, table, (H, W), labels_reduce=2)
+    gate = rdf.to_device(np.ones((n, H // 2, W // 2), np.uint16))
+    for bad in (dict(depth=rdf.to_device(depth[:, :-1])), dict(gate=rdf.to_device(np.ones((n, H, W), np.uint16))),
+                dict(gate=rdf.to_device(np.ones((1, H // 2, W // 2), np.uint16))), dict(out=rdf.DeviceArray((n, 5, 3), np.int32)),
+                dict(out=rdf.DeviceArray((n, 5, 4), np.float32)), dict(out=rdf.DeviceArray((n + 1, 5, 4), np.int32))):
+        args = dict(depth=d_cu, gate=gate)
+        args.update(bad)
+        with pytest.raises(AssertionError):
+            voter.vote(**args)
+    for kw in (dict(cell_shift=5), dict(box=5), dict(labels_reduce=0), dict(min_support=1 << 32), dict(min_support=-1), dict(max_frames=0)):
+        with pytest.raises(AssertionError):
+            rdf.JointVoter(f, table, (H, W), **kw)
+    with pytest.raises(AssertionError):
+        rdf.JointVoter(f, table, (H, 65536))                                    # the workspace of a frame too wide has no size
+    with pytest.raises(AssertionError):
+        rdf.VoteTable(rdf.to_device(np.zeros(forest.shape[:2] + (2, 5, 4), np.int64)), rn.dims(forest))
 
 
 # ------------------------------------------------------------------ GPU ------------------------------------------------------
@@ -507,3 +734,167 @@ def test_end_to_end_on_rendered_hands(rdf, gpu_runtime):
     _same(got, vn.vote(depth[n_train:], forest, want_votes), "joints")
     x, y, z, support = rdf.JointVoter.to_float(got)
     print("voted tips", np.stack([x, y, z], -1).round(1).tolist(), "truth", targets[n_train:].tolist(), "support", support.tolist())
+
+
+# ------------------------------------------------------------------ GPU: ties, 2^31, 64-bit votes, fall-offs -----------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(vc.TIE_LAYOUTS))
+def test_mode_ties(name, rdf, gpu_runtime):
+    """Equal cells and equal box sums: the first in row-major order wins, whichever thread of k_votes_modes holds it and on
+    whichever of its trips.  The joint is TIE_LAYOUTS' literal, worked from V5 by hand."""
+    depth, forest, votes, gate, shift, box = vc.tie_case(name)
+    want = vn.vote(depth, forest, votes, gate=gate, shift=shift, box=box)
+    assert want.tolist() == [[list(vc.TIE_LAYOUTS[name][3])]]
+    voter = rdf.JointVoter(_forest(rdf, forest), _table(rdf, forest, votes), depth.shape[1:], cell_shift=shift, box=box)
+    _same(voter.vote(rdf.to_device(depth), gate=rdf.to_device(gate)).get(), want, name)
+
+
+@pytest.mark.gpu
+def test_box_sums_above_2_31(rdf, gpu_runtime):
+    """405 stumps on 144 x 144, every pixel 256 a tree onto its own cell of 16 x 16: each of the 81 cells holds 26542080 and the
+    centre's box of 4 the whole grid, 2149908480: above 2^31 - 1, so the support is clamped, S and the centroid's sums need
+    their 64 bits, and min_support (a uint32) is compared above 2^31.  The expected joints are V5 on the accumulator in closed
+    form (the CPU tests hold that to the restatement's cast at T = 2).  Measured on the MI355X: the four casts of
+    8.4 million votes each, onto 81 cells, take 87 ms together."""
+    m = vc.SUM
+    depth, forest, votes = vc.sum_case()
+    acc, zacc = vc.full_grid(m["H"], m["W"], m["T"], m["d"], m["mz"], m["shift"])
+    f, table, d_cu = _forest(rdf, forest), _table(rdf, forest, votes), rdf.to_device(depth)
+    literal = ([1152, 1152, 1007, 2147483647], [128, 128, 1007, 26542080], [1152, 1152, 1007, 2147483647], [-1, -1, 0, 0])
+    for (box, support), lit in zip(vc.SUM_RUNS, literal):
+        want = vn.modes(acc, zacc, m["shift"], box, support)
+        assert want.tolist() == [[lit]]
+        got = rdf.JointVoter(f, table, depth.shape[1:], cell_shift=m["shift"], box=box, min_support=support).vote(d_cu).get()
+        _same(got, want, f"the joint at box {box}, min_support {support}")
+
+
+@pytest.mark.gpu
+def test_votes_that_need_64_bits_and_weights_that_are_none(rdf, gpu_runtime):
+    """128 m + d = 2^31 - 1 and -2^31 + 1 (the 32-bit division of vote_pixels), 2^31 and -2^31 (the 64-bit one), a vote that
+    only a 32-bit 128 m + d would put into the frame, mx at both ends of int32, and weights of 257, -1, -256, 2^31 - 1 and
+    -2^31, none of which is a vote.  The CPU tests state every column."""
+    depth, forest, votes, gate = vc.wide_case()
+    want = vn.vote(depth, forest, votes, gate=gate, shift=vc.WIDE["shift"], box=0)
+    voter = rdf.JointVoter(_forest(rdf, forest), _table(rdf, forest, votes), depth.shape[1:], cell_shift=vc.WIDE["shift"], box=0)
+    got = voter.vote(rdf.to_device(depth), gate=rdf.to_device(gate)).get()
+    _same(got, want, "joints")
+    assert (got[..., 3] > 0).sum() == 8 and got[0, 0].tolist() == [256 * 1026 + 128, 128, 65407, 9] and got[3, 1].tolist() == [256 * 162 + 128, 128, 65408, 9]
+
+
+@pytest.mark.gpu
+def test_min_support_0(rdf, gpu_runtime):
+    """V5's max(min_support, 1): with min_support 0 a joint without a vote is (-1, -1, 0, 0), not a division by its best 0."""
+    depth, forest, votes, gate_one, _ = vc.border_case()
+    want = vn.vote(depth, forest, votes, gate=gate_one, shift=0, box=0, min_support=0)
+    voter = rdf.JointVoter(_forest(rdf, forest), _table(rdf, forest, votes), depth.shape[1:], cell_shift=0, box=0, min_support=0)
+    out = rdf.DeviceArray(want.shape, np.int32).fill(77)
+    got = voter.vote(rdf.to_device(depth), gate=rdf.to_device(gate_one), out=out).get()
+    _same(got, want, "joints")
+    assert got[0, [1, 2, 4, 7, 9]].tolist() == [[-1, -1, 0, 0]] * 5 and got[0, 8].tolist() == [88, 24, 70, 100] and (got[0, [0, 3, 5, 6], 3] > 0).all()
+
+
+@pytest.mark.gpu
+def test_a_fall_off_in_a_middle_tree(rdf, gpu_runtime):
+    """Three stumps; the second tells the hand pixels with x <= 5 to go on at level D - 1.  They are counted in totals[2] and
+    still sum, and vote, through the first and the third tree."""
+    depth, labels, targets, forest = vc.middle_case()
+    radius, shift = vc.HAND["radius"], vc.HAND["shift"]
+    want_sums, want_totals = vn.count(depth, labels, targets, forest, radius=radius)
+    f, d_cu, l_cu = _forest(rdf, forest), rdf.to_device(depth), rdf.to_device(labels)
+    fitter = rdf.VoteFitter(f, 1, radius=radius).add(d_cu, l_cu, targets)
+    _same(fitter.sums.get(), want_sums, "sums")
+    assert fitter.totals() == {"walked": 4, "no_depth": 1, "fell_off": 3, "offsets": 7} and want_totals.tolist() == [4, 1, 3, 7]
+    assert want_sums[:, 0, :, 0, 0].tolist() == [[2, 1], [0, 1], [3, 0]]
+    want_votes, want_report = vn.fit(forest, want_sums, **vc.MIDDLE_FIT)
+    table = fitter.fit(**vc.MIDDLE_FIT)
+    _same(table.votes.get(), want_votes, "votes")
+    assert list(table.report.values()) == [int(v) for v in want_report] == [5, 4, 1, 0]
+    for box in (0, 1):
+        got = rdf.JointVoter(f, table, depth.shape[1:], cell_shift=shift, box=box).vote(d_cu, gate=l_cu).get()
+        _same(got, vn.vote(depth, forest, want_votes, gate=labels, shift=shift, box=box), f"joints at box {box}")
+
+
+# ------------------------------------------------------------------ GPU: past one sweep of each grid --------------------------
+@pytest.mark.gpu
+def test_count_past_one_sweep(rdf, gpu_runtime):
+    """294334 pixels in two images: k_votes_count's grid of 1024 x 256 lanes takes a second trip, in which a wave holds the
+    last pixels and lanes past them; the image boundary lies inside a wave of the first."""
+    depth, labels, targets, forest = vc.count_sweep_case()
+    radius = vc.COUNT_SWEEP["radius"]
+    want_sums, want_totals = vn.count(depth, labels, targets, forest, radius=radius)
+    f, d_cu, l_cu = _forest(rdf, forest), rdf.to_device(depth), rdf.to_device(labels)
+    fitter = rdf.VoteFitter(f, vc.COUNT_SWEEP["J"], radius=radius).add(d_cu, l_cu, targets)
+    _same(fitter.sums.get(), want_sums, "sums")
+    assert list(fitter.totals().values()) == [int(v) for v in want_totals]
+    whole = fitter.sums.get()
+    fitter.reset()
+    for i in range(depth.shape[0]):
+        fitter.add(d_cu[i], l_cu[i], targets[i:i + 1])
+    assert fitter.sums.get().tobytes() == whole.tobytes() and list(fitter.totals().values()) == [int(v) for v in want_totals]
+
+
+@pytest.mark.gpu
+def test_fit_past_one_sweep(rdf, gpu_runtime):
+    """T5/D16: 327675 nodes, so k_votes_fit's grid takes a second trip, for the last tree from its node 4 on.  VoteFitter.fit
+    makes a new array per call, so "every element is written" is asked of the entry point itself, given an array that holds a
+    pattern."""
+    forest, sums, slots, leaf = vc.fit_sweep_case()
+    m = vc.FIT_SWEEP
+    want, want_report = vn.fit(forest, sums, m["min_count"], m["max_var"])
+    f = _forest(rdf, forest)
+    fitter = rdf.VoteFitter(f, 1)
+    fitter.sums.set(sums)
+    table = fitter.fit(m["min_count"], m["max_var"])
+    _same(table.votes.get(), want, "votes")
+    assert list(table.report.values()) == [int(v) for v in want_report]
+    votes = rdf.DeviceArray(want.shape, np.int32).fill(0x55555555)
+    report = rdf.DeviceArray((4,), np.uint64).fill(np.uint64(77))
+    lib = _mod("_lib").load("labels")
+    rc = lib.rdf_labels_votes_fit(rdf.device_ptr(f.forest_cu), m["T"], m["D"], 1, 1, fitter.sums.ptr, m["min_count"], m["max_var"],
+                                  votes.ptr, report.ptr, gpu_runtime.stream())
+    assert rc == 0
+    _same(votes.get(), want, "votes written over a pattern")
+    assert report.get().tolist() == want_report.tolist()
+    assert want[slots["negative_sums in tree 4"]].tolist() == [-2, -3, -6667, 256] and not want[slots["unreachable"]].any()
+
+
+@pytest.mark.gpu
+def test_modes_past_one_sweep(rdf, gpu_runtime):
+    """4097 frames of 2 x 2 with 16 joints: 65552 (frame, joint) pairs, so 16 workgroups of k_votes_modes' grid of 65536 take a
+    second pair, frame 4096's after frame 0's, and the two frames differ in every joint."""
+    depth, forest, votes, kind = vc.modes_sweep_case()
+    want = vc.vote_by_kind(vn)
+    f, table, d_cu = _forest(rdf, forest), _table(rdf, forest, votes), rdf.to_device(depth)
+    out = rdf.DeviceArray(want.shape, np.int32).fill(77)
+    voter = rdf.JointVoter(f, table, depth.shape[1:], cell_shift=0, box=0, max_frames=vc.MODES["frames"])
+    assert voter.vote(d_cu, out=out) is out
+    whole = out.get()
+    _same(whole, want, "joints")
+    chunked = rdf.JointVoter(f, table, depth.shape[1:], cell_shift=0, box=0, max_frames=64).vote(d_cu).get()
+    assert chunked.tobytes() == whole.tobytes()
+
+
+@pytest.mark.gpu
+def test_a_table_outlives_a_refit_of_the_pdfs(adv, rdf, gpu_runtime):
+    """VoteTable's promise: a table is indexed by leaf slot, so LeafRefitter.apply, which rewrites the PDFs alone, leaves the
+    votes of a frame as they were, and a new fit gives the same table.  A single [H, W] frame is a batch of one."""
+    depth, labels, forest = adv
+    targets = vc.targets_for(5, 255)
+    f = _forest(rdf, forest)
+    d_cu, l_cu = rdf.to_device(depth), rdf.to_device(labels)
+    table = rdf.VoteFitter(f, 5).add(d_cu, l_cu, targets).fit(**ADV_FIT)
+    voter = rdf.JointVoter(f, table, depth.shape[1:])
+    before = voter.vote(d_cu).get()
+    want_votes = vc.adv_table(5, 255)[1]
+    _same(table.votes.get(), want_votes, "votes")
+    _same(before, vn.vote(depth, forest, want_votes, walk=vc.memo_walk), "joints before the refit")
+    assert (before[..., 3] > 0).any()
+    report = rdf.LeafRefitter(f).add(d_cu, l_cu).apply()
+    after = f.forest_cu.get()
+    assert report["own"] > 0 and not np.array_equal(after.view(np.uint32), forest.view(np.uint32))
+    assert np.array_equal(after[:, :, :7].view(np.uint32), forest[:, :, :7].view(np.uint32))          # the structure is as it was
+    assert voter.vote(d_cu).get().tobytes() == before.tobytes()
+    again = rdf.VoteFitter(f, 5).add(d_cu, l_cu, targets).fit(**ADV_FIT)
+    assert again.votes.get().tobytes() == table.votes.get().tobytes() and again.report == table.report
+    one = voter.vote(d_cu[1]).get()
+    assert one.shape == (1, 5, 4) and one.tobytes() == before[1:].tobytes()
