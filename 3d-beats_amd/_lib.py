@@ -250,6 +250,9 @@ BINDINGS = {
         "rdf_labels_votes_cast": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int,
                                            _c_float, _c_void_p, _c_int, _c_int, _c_int, ctypes.c_uint32, _c_void_p, _c_void_p,
                                            _c_void_p]),
+        "rdf_labels_vote_tips": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_int,
+                                          _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _c_float, _c_void_p,
+                                          _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p]),
         "rdf_labels_abi_version": (_c_int, []),
         "rdf_labels_build_id": (ctypes.c_char_p, []),
         "rdf_labels_error_string": (ctypes.c_char_p, [_c_int]),

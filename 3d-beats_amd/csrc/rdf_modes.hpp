@@ -97,21 +97,31 @@ struct HeightArgs {
 //   px,py = int(mean) * labels_reduce; off-frame -> NaN ("reset"); z = depth[py][px];
 //   pt = z * ((px-ppx)/fx, (py-ppy)/fy, 1)  (librealsense rs2_deproject_pixel_to_point, no distortion, fp32);
 //   height = -(plane @ [pt,1]).z  with the fp32 plane matrix promoted to fp64 like numpy's float32 @ float64.
+// The two halves below are also what k_vote_tips (vote_tips_hip.hip, rules T1 and T5) is made of: one bounds test and one
+// deprojection in the package.
+__device__ __forceinline__ bool mode_pixel(double mx, double my, const HeightArgs &h, long long *px, long long *py)
+{
+    if (!(mx == mx && my == my && fabs(mx) < 1e9 && fabs(my) < 1e9)) return false;
+    *px = (long long)mx * h.labels_reduce;      // trunc toward 0
+    *py = (long long)my * h.labels_reduce;
+    return *px >= 0 && *py >= 0 && *px < h.dim_x && *py < h.dim_y;
+}
+
+// depth z at pixel (px, py) -> height above the plane
+__device__ __forceinline__ double height_at_pixel(long long px, long long py, float z, const HeightArgs &h)
+{
+    const float x = ((float)px - h.ppx) / h.fx, y = ((float)py - h.ppy) / h.fy;
+    const double pt[4] = {(double)(z * x), (double)(z * y), (double)z, 1.0};
+    double pz = 0.0;
+    for (int k = 0; k < 4; ++k) pz += (double)h.plane[2 * 4 + k] * pt[k];
+    return -pz;
+}
+
 __device__ __forceinline__ double height_of_mode(double mx, double my, const HeightArgs &h)
 {
-    double out = nan("");
-    if (mx == mx && my == my && fabs(mx) < 1e9 && fabs(my) < 1e9) {
-        const long long px = (long long)mx * h.labels_reduce, py = (long long)my * h.labels_reduce;   // trunc toward 0
-        if (px >= 0 && py >= 0 && px < h.dim_x && py < h.dim_y) {
-            const float z = (float)h.depth[py * h.dim_x + px];
-            const float x = ((float)px - h.ppx) / h.fx, y = ((float)py - h.ppy) / h.fy;
-            const double pt[4] = {(double)(z * x), (double)(z * y), (double)z, 1.0};
-            double pz = 0.0;
-            for (int k = 0; k < 4; ++k) pz += (double)h.plane[2 * 4 + k] * pt[k];
-            out = -pz;
-        }
-    }
-    return out;
+    long long px, py;
+    if (!mode_pixel(mx, my, h, &px, &py)) return nan("");
+    return height_at_pixel(px, py, (float)h.depth[py * h.dim_x + px], h);
 }
 
 // Workgroup (c, f) of 1024 threads is class c + 1 of frame f; a single frame is a grid y of 1.  `weights` is read only by the

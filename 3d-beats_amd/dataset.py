@@ -16,6 +16,13 @@ import os
 
 import numpy as np
 
+from .joint_votes import DEFAULT_MAX_VAR
+
+# Not in the reference: joint targets beside a dataset's frames, int32 [num_images, J, 3] = (tx, ty, tz) per image and joint
+# (rule V1 of include/rdf_labels.h), written by HandSceneRenderer.make_dataset(targets=True).  A directory without the file is
+# a plain dataset.
+TARGETS_FILE = 'targets.npy'
+
 
 class DecisionTreeDatasetConfig:
     @staticmethod
@@ -135,6 +142,24 @@ def write_dataset(dataset_dir, depth, labels, id_to_color):
             os.path.join(dataset_dir, f'{str(i).zfill(8)}_depth.png'))
         Image.fromarray(np.ascontiguousarray(labels[i], dtype=np.uint16)).save(
             os.path.join(dataset_dir, f'{str(i).zfill(8)}_labels.png'))
+
+
+def read_targets(dataset_dir, images):
+    """The joint targets of a dataset directory's images `images` (indices into the directory, e.g. a
+    DecisionTreeDatasetConfig's img_idxes, in that order): host int32 [len(images), J, 3]."""
+    path = os.path.join(dataset_dir, TARGETS_FILE)
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"{dataset_dir} carries no joint targets ({TARGETS_FILE}): write it with "
+                                "HandSceneRenderer.make_dataset(..., targets=True)")
+    with open(os.path.join(dataset_dir, 'config.json')) as fh:
+        total = json.loads(fh.read())['num_images']
+    t = np.load(path)
+    if t.dtype != np.int32 or t.ndim != 3 or t.shape[0] != total or t.shape[2] != 3:
+        raise ValueError(f"{path}: int32 [{total}, J, 3] expected, found {t.dtype} {list(t.shape)}")
+    idx = np.asarray(list(images), np.int64).reshape(-1)
+    if idx.size and (idx.min() < 0 or idx.max() >= total):
+        raise IndexError(f"images outside 0..{total - 1}")
+    return np.ascontiguousarray(t[idx])
 
 
 def evaluate_saved_model(model_path, dataset_dir, num_images, out_dir=None):
@@ -263,6 +288,29 @@ def refit_saved_model(model_path, dataset_dir, num_images, out_path, min_count=1
     report = _refit_on_dataset(forest, dataset_dir, num_images, min_count, fallback)
     np.save(out_path, forest.forest_cu.get())
     return report
+
+
+def fit_votes_saved_model(model_path, dataset_dir, num_images, out_path, min_count=8, max_var=DEFAULT_MAX_VAR, radius=255, chunk=64):
+    """A joint-vote table for a saved forest (joint_votes.VoteFitter): `num_images` random images (0: all) of a dataset
+    directory that carries joint targets (read_targets), read as score_saved_model reads them, summed `chunk` images a call,
+    fitted with min_count and max_var (VoteFitter.fit's) and saved with VoteTable.save at `out_path`, which
+    JointVoter takes through VoteTable.load.  Returns the fit's report."""
+    from .decision_tree import DecisionForest
+    from .device import DeviceArray
+    from .joint_votes import VoteFitter
+    forest = DecisionForest.load(model_path)
+    num_images = num_images or DecisionTreeDatasetConfig(dataset_dir).total_available_images
+    ds = DecisionTreeDatasetConfig(dataset_dir, num_images=num_images, imgs_name='votes')
+    targets = read_targets(dataset_dir, ds.img_idxes)
+    depth, labels = DeviceArray(ds.images_shape(), np.uint16), DeviceArray(ds.images_shape(), np.uint16)
+    ds.get_depth_block_cu(0, depth)
+    ds.get_labels_block_cu(0, labels)
+    fitter = VoteFitter(forest, int(targets.shape[1]), radius=radius)
+    for a in range(0, num_images, int(chunk)):
+        fitter.add(depth[a:a + chunk], labels[a:a + chunk], targets[a:a + chunk])
+    table = fitter.fit(min_count, max_var)
+    table.save(out_path)
+    return table.report
 
 
 def _prune_on_dataset(forest, dataset_dir, num_images, cost_per_leaf, min_count, max_levels, truncate):

@@ -9,10 +9,12 @@ into device depth and label images, two launches per chunk of `max_frames` on th
 StereoSensor) all three draw a clean left and a clean right frame and report what the stereo camera makes of them, in place of
 rule H's holes and noise.  The rasteriser's rules are in include/rdf_labels.h.
 """
+import os
+
 import numpy as np
 
 from . import _lib
-from .dataset import write_dataset
+from .dataset import TARGETS_FILE, write_dataset
 from .device import DeviceArray, device_ptr, get_runtime, to_device
 from .hand_model import N_PARTS, POSE_SIZE, HandModel
 
@@ -174,11 +176,13 @@ class HandSceneRenderer:
         return sensor.sense(depth_l, labels_l, depth_r, seed, empty_depth, depth_out, labels_out)
 
     def make_dataset(self, dataset_dir, num_images, seed, labels='fine', plane=None, two_hands=False, ranges=None,
-                     hole_rate=0., noise_amp=0, sensor=None):
+                     hole_rate=0., noise_amp=0, sensor=None, targets=False):
         """Sample `num_images` poses from `seed` (HandModel.sample_poses), render them in dataset convention -- no table,
         background depth 65535, label 0 = none -- and write `dataset_dir` with dataset.write_dataset and the scheme's
-        id_to_color.  plane: the camera's table plane; default look_down_plane(550 mm).  sensor: see render.  Returns the host
-        (depth, labels)."""
+        id_to_color.  plane: the camera's table plane; default look_down_plane(550 mm).  sensor: see render.  targets=True also writes
+        `targets.npy` to the directory: int32 [N, 5 or 10, 3], the fingertip_targets of the sampled poses for `plane` -- what
+        dataset.read_targets and dataset.fit_votes_saved_model read; without it the directory is what it always was.  Returns
+        the host (depth, labels)."""
         rng = np.random.default_rng(seed)
         plane = look_down_plane(550. * self.model.units_per_mm) if plane is None else plane
         poses = self.model.sample_poses(num_images, rng, ranges)
@@ -193,6 +197,8 @@ class HandSceneRenderer:
         depth, lab = depth.get(), lab.get()
         scheme = labels if isinstance(labels, str) else 'fine'
         write_dataset(dataset_dir, depth, lab, HandModel.id_to_color(scheme))
+        if targets:
+            np.save(os.path.join(dataset_dir, TARGETS_FILE), self.fingertip_targets(poses, plane, left))
         return depth, lab
 
     def camera_sequence(self, poses, plane, left_poses=None, hole_rate=0., noise_amp=0, seed=0, labels='fine', labels_out=None,

@@ -162,6 +162,12 @@ class JointVoter:
         assert nbytes > 0, "frame size or joints out of range"
         self._workspace = DeviceArray((nbytes,), np.uint8)
 
+    def sibling(self):
+        """A voter of the same forest, table and settings with a workspace of its own: what a second HandPipeline gets, so
+        that the two hands of a frame can vote on two streams without sharing an accumulator."""
+        return JointVoter(self.forest, self.table, (self.DIM_Y, self.DIM_X), self.labels_reduce, self.cell_shift, self.box,
+                          self.min_support, self.max_frames)
+
     def vote(self, depth, gate=None, scale_factor=1., out=None):
         """depth: device uint16 [N, H, W] ([H, W] is one frame).  gate: None (every pixel with a depth votes: dataset frames,
         whose background is 65535) or a device uint16 [N, H // r, W // r] map whose values other than 0 and 65535 say "hand"

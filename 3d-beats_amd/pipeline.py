@@ -20,6 +20,13 @@ from .cuda.points_ops import PointsOps
 from .device import DeviceArray, device_ptr, get_runtime
 from .engine.buffer import GpuBuffer
 
+TIP_POLICIES = {"fill": 0, "guard": 1, "votes": 2}      # RDF_TIPS_FILL, _GUARD, _VOTES of include/rdf_labels.h
+# Both are the best of the sweep that tests/perf/bench_vote_tips.py records (profiles/vote_tips_bench.json; DESIGN.md, "voted
+# fingertips"), on 424x240 stereo frames with depth units of 0.1 mm: tip_max_dist over 2..32 pixels, tip_z_tol over 10..1000
+# units.  Both lie at the low end of their sweep, and they replace the guesses the sweep started from (8 pixels, 100 units).
+DEFAULT_TIP_MAX_DIST = 2
+DEFAULT_TIP_Z_TOL = 10
+
 
 # [graph, lib, capture id, device, last replay's event, capture stream, attempts] of replay objects that were dropped
 _pending = []
@@ -63,7 +70,8 @@ def _release_deferred():
 class HandPipeline:
     def __init__(self, layered_rdf, depth_dims, labels_reduce, eval_to_train_dim_ratio, mean_shift_rounds,
                  mean_shift_variances, fingertip_idxes, intrinsics, plane, depth_mm_level=0, fused_io=True,
-                 hand_state=None, tip_first=0, soft_modes=False):
+                 hand_state=None, tip_first=0, soft_modes=False, joint_voter=None, tip_joints=None, tip_policy='fill',
+                 tip_max_dist=DEFAULT_TIP_MAX_DIST, tip_z_tol=DEFAULT_TIP_Z_TOL):
         """depth_dims = (DIM_Y, DIM_X); intrinsics = (fx, fy, ppx, ppy) of the depth stream; plane = the calibrated
         plane's 4x4 matrix (calibrated_plane.plane) or a float32 device array of 16 elements that is read every frame
         (FrameFrontEnd.calibrated_plane.plane_cu: a recalibration then reaches the heights); fingertip_idxes = 1-based
@@ -71,7 +79,38 @@ class HandPipeline:
         frame advances, on the device, from the heights where the chain wrote them (3d_bz.py:496-522 without the read).
         soft_modes=True (needs fused_io and a stack with `min_conf` set, ValueError otherwise): the modes are found by
         WeightedModes with every pixel weighted by the stack's composite confidence (rules S of include/rdf_labels.h) in place
-        of the mean shift; results land where they always do.  False: nothing is allocated or launched for it."""
+        of the mean shift; results land where they always do.  False: nothing is allocated or launched for it.
+        joint_voter: a JointVoter built for depth_dims (needs fused_io; anything else is a ValueError).  Every frame it votes
+        on the frame the forest sees -- stencilled to the hand, mirrored for the left hand, so every pixel with a depth is the
+        hand's -- and rdf_labels_vote_tips (rules T of include/rdf_labels.h) runs behind the mode launch: per fingertip it
+        chooses between the mode of the tip's class and the voted position of joint tip_joints[i] (default 0 .. n - 1, the
+        thumb-to-pinky order of HandSceneRenderer.fingertip_targets; -1: this tip never takes a vote) and writes the height
+        where the mode launch wrote it, so the hand_state and every reader of the heights see the fused heights.  tip_policy:
+        'fill' (the default: a vote only where the label route found nothing, so no tip the label route found moves),
+        'guard' (the vote also where the mode lies more than tip_max_dist depth pixels from it along x or y) or 'votes' (the
+        vote wherever there is one).  tip_z_tol: a voted tip takes the sensor's depth at its pixel when that is within
+        tip_z_tol depth units of the voted depth, else the voted depth.  The defaults of tip_max_dist and tip_z_tol are
+        the best of a sweep on stereo frames (DEFAULT_TIP_MAX_DIST, DEFAULT_TIP_Z_TOL above), not guesses.  `tips` /
+        `tips_batch` then hold the device int32 rows (px, py, z, source) of the last frame / batch.  A voter that already
+        serves another pipeline is replaced by its sibling(), as the stack is.  None: nothing is allocated or launched."""
+        n_tips = len(fingertip_idxes)
+        if joint_voter is not None:
+            from .joint_votes import JointVoter
+            if not isinstance(joint_voter, JointVoter):
+                raise ValueError(f"joint_voter must be a JointVoter, not {type(joint_voter).__name__}")
+            if (joint_voter.DIM_Y, joint_voter.DIM_X) != (int(depth_dims[0]), int(depth_dims[1])):
+                raise ValueError(f"joint_voter was built for frames of {(joint_voter.DIM_Y, joint_voter.DIM_X)}, not "
+                                 f"{(int(depth_dims[0]), int(depth_dims[1]))}")
+            if not fused_io:
+                raise ValueError("joint_voter needs fused_io=True")
+            if tip_policy not in TIP_POLICIES:
+                raise ValueError(f"tip_policy must be one of {sorted(TIP_POLICIES)}, not {tip_policy!r}")
+            tip_joints = list(range(n_tips)) if tip_joints is None else [int(j) for j in tip_joints]
+            if len(tip_joints) != n_tips or any(j < -1 or j >= joint_voter.J for j in tip_joints):
+                raise ValueError(f"tip_joints must name one joint in -1 .. {joint_voter.J - 1} per fingertip ({n_tips}), not "
+                                 f"{tip_joints}")
+            if not (0 <= int(tip_max_dist) <= 65535 and 0 <= int(tip_z_tol) <= 65535):
+                raise ValueError("tip_max_dist and tip_z_tol must be in 0..65535")
         # (what soft_modes cannot serve is refused before anything is allocated or the stack is marked as this pipeline's)
         if soft_modes and not fused_io:
             raise ValueError("soft_modes needs fused_io=True")
@@ -132,6 +171,35 @@ class HandPipeline:
             from .soft_modes import WeightedModes
             self.weighted_modes = WeightedModes()
             self.weights_image = GpuBuffer(l, np.uint16)
+        self.joint_voter, self.tips, self.tips_batch = None, None, None
+        if joint_voter is not None:
+            owner = getattr(joint_voter, "_pipeline_owner", None)
+            if owner is not None and owner() is not None:
+                joint_voter = joint_voter.sibling()
+            joint_voter._pipeline_owner = weakref.ref(self)
+            self.joint_voter = joint_voter
+            self.tip_policy, self.tip_max_dist, self.tip_z_tol = tip_policy, int(tip_max_dist), int(tip_z_tol)
+            self.tip_joints = tip_joints
+            self._lb = _lib.load("labels")
+            self._tip_joints = DeviceArray((n_tips,), np.int32).set(np.asarray(tip_joints, np.int32))
+            self._joints = DeviceArray((1, joint_voter.J, 4), np.int32)
+            self.tips = DeviceArray((n_tips, 4), np.int32)
+
+    def _vote(self, depth_2, joints):
+        """The voter's launches for the frames the forest sees (depth_2 [n, DIM_Y, DIM_X], background 65535: gate=None takes
+        exactly the hand's pixels)."""
+        self.joint_voter.vote(depth_2, gate=None, scale_factor=self.EVAL_TO_TRAIN_DIM_RATIO, out=joints)
+
+    def _vote_tips(self, n, means_ptr, joints, flip_x, height_depth_ptr, heights_ptr, heights_stride, tips):
+        """rdf_labels_vote_tips behind the mode launch of n frames: the heights where that launch wrote them."""
+        fx, fy, ppx, ppy = self.intrinsics
+        rc = self._lb.rdf_labels_vote_tips(means_ptr, n, self._L, self._ids.ptr, self._tip_joints.ptr, len(self.fingertip_idxes),
+                                           joints.ptr, self.joint_voter.J, 1 if flip_x else 0, height_depth_ptr, self.DIM_X,
+                                           self.DIM_Y, self.LABELS_REDUCE, fx, fy, ppx, ppy, self._plane.ptr,
+                                           TIP_POLICIES[self.tip_policy], self.tip_max_dist, self.tip_z_tol, heights_ptr,
+                                           heights_stride, tips.ptr, self._rt.stream())
+        _lib.check(self._lb, rc, "rdf_labels_vote_tips")
+        tips.mark_dirty()
 
     def run(self, depth_image, depth_image_mm_groups, g_id, flip_x, height_depth=None):
         """depth_image: GpuBuffer uint16 [DIM_Y, DIM_X] (the frame, 0 = no reading);
@@ -154,7 +222,9 @@ class HandPipeline:
         its composite to `labels_batch[f]`; each frame bit for bit what enqueue() computes for it.  No RGBA image is written
         and no hand_state is stepped: the caller steps it, once for both hands.  The batch buffers are sized on first use,
         for the largest n seen.  With soft_modes the third call is two: the stack's composite_weights_batch into
-        `weights_batch[f]`, then rdf_labels_weighted_modes for the n frames."""
+        `weights_batch[f]`, then rdf_labels_weighted_modes for the n frames.  With a joint_voter its cast runs on the prepared
+        frames (in chunks of the voter's max_frames, `joints_batch[f]`) and rdf_labels_vote_tips follows the mode launch:
+        the fused heights land in the same rows, the tips in `tips_batch[f]`."""
         if not self.fused_io:
             raise ValueError("enqueue_batch needs fused_io=True")
         depth_images, group_images, height_depth = (a.cu() if hasattr(a, "cu") else a
@@ -169,6 +239,9 @@ class HandPipeline:
             self._means_batch = DeviceArray((n, self._L, 2), np.float64)
             if self.soft_modes:
                 self._weights_batch = DeviceArray((n, self.LABELS_DIM_Y, self.LABELS_DIM_X), np.uint16)
+            if self.joint_voter is not None:
+                self._joints_batch = DeviceArray((n, self.joint_voter.J, 4), np.int32)
+                self._tips_batch = DeviceArray((n, len(self.fingertip_idxes), 4), np.int32)
             self._batch_capacity = n
         dims = np.array([self.DIM_X, self.DIM_Y], dtype=np.int32)
         depth_2, labels = self._depth_batch[:n], self._labels_batch[:n]
@@ -176,6 +249,9 @@ class HandPipeline:
         self.points_ops.prepare_hand_depth_batch(n, dims, self.depth_mm_level, g_id, group_images, depth_images, depth_2,
                                                  flip_x)
         self.layered_rdf.run_hand_batch(depth_2, labels, self.EVAL_TO_TRAIN_DIM_RATIO, flip_x)
+        if self.joint_voter is not None:
+            self.joints_batch, self.tips_batch = self._joints_batch[:n], self._tips_batch[:n]
+            self._vote(depth_2, self.joints_batch)
         if self.soft_modes:
             self.weights_batch = self._weights_batch[:n]
             self.layered_rdf.composite_weights_batch(n, self.weights_batch, flip_x)
@@ -183,13 +259,15 @@ class HandPipeline:
                 self.mean_shift_rounds, labels, self.weights_batch, self._L, self.mean_shift_variances, self._ids,
                 len(self.fingertip_idxes), height_depth, self.LABELS_REDUCE, self.intrinsics, self._plane, self.means_batch.ptr,
                 heights_out_ptr, heights_stride)
-            self.means_batch.mark_dirty()
-            return
-        self.mean_shift.run_device_with_heights_batch(
-            self.mean_shift_rounds, labels, self._L, self.mean_shift_variances, self._ids, len(self.fingertip_idxes),
-            height_depth, self.LABELS_REDUCE, self.intrinsics, self._plane, self.means_batch.ptr, heights_out_ptr,
-            heights_stride)
+        else:
+            self.mean_shift.run_device_with_heights_batch(
+                self.mean_shift_rounds, labels, self._L, self.mean_shift_variances, self._ids, len(self.fingertip_idxes),
+                height_depth, self.LABELS_REDUCE, self.intrinsics, self._plane, self.means_batch.ptr, heights_out_ptr,
+                heights_stride)
         self.means_batch.mark_dirty()
+        if self.joint_voter is not None:
+            self._vote_tips(n, self.means_batch.ptr, self.joints_batch, flip_x, device_ptr(height_depth), heights_out_ptr,
+                            heights_stride, self.tips_batch)
 
     @property
     def heights_ptr(self):
@@ -213,9 +291,12 @@ class HandPipeline:
         address, and its cache key) with what they were at capture, and raises RuntimeError BEFORE anything is enqueued
         when one differs -- after
         `LeafRefitter.apply`, a `forest_cu.set(...)` or a re-pack: capture again.  (A bare `replay.graph.replay()` is
-        not covered.)  A stack with `min_conf` set (the gated, step-by-step path) is not captured: NotImplementedError."""
+        not covered.)  A stack with `min_conf` set (the gated, step-by-step path) is not captured, and neither is a pipeline with
+        a joint_voter: NotImplementedError, before anything is recorded."""
         if getattr(self.layered_rdf, "min_conf", None) is not None:
             raise NotImplementedError("HandPipeline.capture: the stack has min_conf set; capture of the gated path is not built")
+        if self.joint_voter is not None:
+            raise NotImplementedError("HandPipeline.capture: capture of the joint voter's cast is not built")
         import torch
         scale = self.EVAL_TO_TRAIN_DIM_RATIO
         side = torch.cuda.Stream()
@@ -298,6 +379,16 @@ class HandPipeline:
                 self.hand_state.state_ptr        # (its device side exists before a capture starts)
 
     def _chain(self, depth_image, depth_image_mm_groups, g_id, flip_x, height_depth):
+        self._modes_chain(depth_image, depth_image_mm_groups, g_id, flip_x, height_depth)
+        if self.joint_voter is not None:
+            # (the cast was enqueued in front of the mode launch, behind the forest: _modes_chain)
+            base = self._host[1] if self._host is not None else self._result.ptr
+            self._vote_tips(1, base, self._joints, flip_x, device_ptr(height_depth.cu()), base + self._L * 2 * 8,
+                            len(self.fingertip_idxes), self.tips)
+            if self._host is None:
+                self._result.mark_dirty()
+
+    def _modes_chain(self, depth_image, depth_image_mm_groups, g_id, flip_x, height_depth):
         dims = np.array([self.DIM_X, self.DIM_Y], dtype=np.int32)
         ldims = np.array([self.LABELS_DIM_X, self.LABELS_DIM_Y], dtype=np.int32)
         po = self.points_ops
@@ -308,6 +399,8 @@ class HandPipeline:
                                   depth_image.cu(), self.depth_image_2.cu(), flip_x)
             self.layered_rdf.run_hand(self.depth_image_2, self.labels_image, self.EVAL_TO_TRAIN_DIM_RATIO, flip_x,
                                       self.labels_image_rgba)
+            if self.joint_voter is not None:
+                self._vote(self.depth_image_2.cu(), self._joints)
         else:
             # the reference's sequence, kernel for kernel (3d_bz.py:396-456)
             self.depth_image_group.cu().fill(0)

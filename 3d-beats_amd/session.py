@@ -17,7 +17,7 @@ from .device import DeviceArray, get_runtime
 from .frontend import FrameFrontEnd
 from .grouping import HandGrouping
 from .hand_state import MAX_VELOCITY, MIN_VELOCITY, VELOCITY_SENSITIVE, HandState
-from .pipeline import HandPipeline
+from .pipeline import DEFAULT_TIP_MAX_DIST, DEFAULT_TIP_Z_TOL, HandPipeline
 
 TRAIN_DIM_X = 848
 
@@ -38,14 +38,21 @@ class BeatsSession:
                  mean_shift_variances=(50., 8., 8., 8., 8., 8., 8.), fingertip_idxes=(2, 3, 4, 5, 6), z_thresh_offset=25.,
                  min_velocity=10., max_velocity=120., velocity_sensitive=True, scale_factor=None,
                  fingertip_thresholds=(200., 160., 160., 160., 160.), first_notes=(36, 41), max_frames=8,
-                 num_random_guesses=25000, seed=None, fused_io=True, capacity=4096, post_filter=None, soft_modes=False):
+                 num_random_guesses=25000, seed=None, fused_io=True, capacity=4096, post_filter=None, soft_modes=False,
+                 joint_votes=None, tip_joints=None, tip_policy='fill', tip_max_dist=DEFAULT_TIP_MAX_DIST,
+                 tip_z_tol=DEFAULT_TIP_Z_TOL):
         """layered_rdf: a LayeredDecisionForest built for depth_dims = (DIM_Y, DIM_X) and labels_reduce; intrinsics = (focal,
         ppx, ppy) of the depth camera.  The other defaults are the app's (3d_bz.py:49-124); scale_factor = DIM_X / 848 when
         None.  max_frames = the batch of run_sequence's front end and grouping.  post_filter: a DepthPostFilter of the same
         depth_dims that calibrate, tick and run_sequence pass their frames through first; its temporal state runs on from
         call to call (post_filter.reset() starts it afresh).  Without one nothing is allocated or launched for it.
         soft_modes: both hands' pipelines find their modes weighted by the stack's confidence (HandPipeline's soft_modes: needs
-        fused_io and a layered_rdf with min_conf set); False, the default, changes nothing."""
+        fused_io and a layered_rdf with min_conf set); False, the default, changes nothing.
+        joint_votes: (forest, table) or (forest, table, settings) -- a DecisionForest, a VoteTable fitted to it and a dict of
+        JointVoter's keyword arguments (labels_reduce, cell_shift, box, min_support).  One JointVoter per hand is built for
+        depth_dims with max_frames the session's and handed to the hand's pipeline with tip_joints, tip_policy, tip_max_dist
+        and tip_z_tol (HandPipeline's; the left hand's frame is mirrored, so both hands use the same joints): tick and both
+        kinds of run_sequence then step the notes from the voted fingertips' heights.  None, the default, changes nothing."""
         self._rt = get_runtime()
         self.DIM_Y, self.DIM_X = int(depth_dims[0]), int(depth_dims[1])
         self.max_frames = int(max_frames)
@@ -64,10 +71,21 @@ class BeatsSession:
         self.hand_state.z_thresh_offset = z_thresh_offset
         args = ((self.DIM_Y, self.DIM_X), labels_reduce, scale, mean_shift_rounds, list(mean_shift_variances),
                 list(fingertip_idxes), (focal, focal, ppx, ppy), self.front_end.calibrated_plane.plane_cu)
+        voters, tips = (None, None), {}
+        if joint_votes is not None:
+            from .joint_votes import JointVoter
+            if not 2 <= len(joint_votes) <= 3:
+                raise ValueError("joint_votes is (forest, table) or (forest, table, settings)")
+            settings = dict(joint_votes[2]) if len(joint_votes) == 3 else {}
+            if "max_frames" in settings:
+                raise ValueError("joint_votes: the voters' max_frames is the session's")
+            voters = tuple(JointVoter(joint_votes[0], joint_votes[1], (self.DIM_Y, self.DIM_X), max_frames=self.max_frames,
+                                      **settings) for _ in range(2))
+            tips = dict(tip_joints=tip_joints, tip_policy=tip_policy, tip_max_dist=tip_max_dist, tip_z_tol=tip_z_tol)
         self.right = HandPipeline(layered_rdf, *args, depth_mm_level=depth_mm_level, fused_io=fused_io,
-                                  hand_state=self.hand_state, tip_first=0, soft_modes=soft_modes)
+                                  hand_state=self.hand_state, tip_first=0, soft_modes=soft_modes, joint_voter=voters[0], **tips)
         self.left = HandPipeline(layered_rdf, *args, depth_mm_level=depth_mm_level, fused_io=fused_io,
-                                 hand_state=self.hand_state, tip_first=n, soft_modes=soft_modes)
+                                 hand_state=self.hand_state, tip_first=n, soft_modes=soft_modes, joint_voter=voters[1], **tips)
         self.n_tips = 2 * n
         hm, wm = self.grouping.depth_mm_dims
         self._raw = DeviceArray((self.max_frames, self.DIM_Y, self.DIM_X), np.uint16)

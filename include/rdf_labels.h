@@ -798,6 +798,60 @@ int rdf_labels_votes_cast(const uint16_t *depth, int n_img, int dim_x, int dim_y
                           int n_joints, int cell_shift, int box, uint32_t min_support, void *workspace, int32_t *joints_out,
                           void *stream);
 
+/*
+ * Voted fingertips: the label route and the joint votes joined.  rdf_labels_vote_tips runs behind the mode launch of a hand's
+ * chain (rdf_mean_shift_heights, rdf_mean_shift_heights_batch or rdf_labels_weighted_modes) and behind rdf_labels_votes_cast:
+ * per frame and fingertip it chooses between the mode of the tip's class and the voted position of the tip's joint, finds a
+ * depth for the chosen pixel and writes the tip's height where the mode launch wrote it -- a tip whose class has no pixel gets
+ * a height from its vote.  The reference has no counterpart; tests/vote_tips_numpy.py restates the rules bit for bit.
+ *
+ *   means       float64 [n_img][L][2] = (x, y), L = num_classes: the mode finder's output, in label pixels, never flipped.
+ *   class_ids   int [n_ids], 1-based classes;  tip_joints int [n_ids], a joint index each (anything outside 0 .. J - 1, -1 by
+ *               convention: this tip never takes a vote).
+ *   joints      int32 [n_img][J][4] = (X, Y, Z, S): rdf_labels_votes_cast's output (rule V5), in the frame the voter saw --
+ *               mirrored in x when flip_x is set, as the hand's chain mirrors the left hand's frame.
+ *   depth       uint16 [n_img][dim_y][dim_x]: the frame heights are looked up in (the raw camera frame, never flipped).
+ *   plane       float32 [16], the calibrated plane's 4x4 matrix, row-major;  fx, fy, ppx, ppy: the depth camera.
+ *   heights_out float64, heights_out[f * heights_stride + i]; what lies between the rows is not touched.
+ *   tips_out    int32 [n_img][n_ids][4] = (px, py, z, source); may be NULL.
+ *   floordiv and clamp as in rules V.  means and heights_out may be mapped pinned host memory.
+ *
+ * Per frame f and tip i:
+ * T1. The mode candidate.  c = class_ids[i]; none if c is outside 1 .. L.  Else (mx, my) = means[f][c - 1]; none if either is
+ *     NaN or |.| >= 1e9.  Else (pxm, pym) = (trunc(mx) * r, trunc(my) * r) with r = labels_reduce; none if that is off the
+ *     frame.  Exactly the conditions under which rule S7 (rdf_fingertip_heights) gives a height.
+ * T2. The vote candidate.  j = tip_joints[i]; none if j is outside 0 .. J - 1.  Else (X, Y, Z, S) = joints[f][j]; none if S
+ *     <= 0, and none on a frame without pixels.  Else Xu = flip_x ? 16 * dim_x - X : X (a pixel centre is at +8, so the
+ *     centre of pixel p maps to the centre of pixel dim_x - 1 - p); pxv = clamp(floordiv(Xu, 16), 0, dim_x - 1), pyv =
+ *     clamp(floordiv(Y, 16), 0, dim_y - 1): the centre of a border cell can lie past the frame when the frame is no multiple
+ *     of the cell.
+ * T3. The choice.  RDF_TIPS_FILL: the mode if there is one, else the vote.  RDF_TIPS_GUARD: with both candidates, the mode if
+ *     max(|pxm - pxv|, |pym - pyv|) <= max_dist, else the vote; with one candidate, that one.  RDF_TIPS_VOTES: the vote if
+ *     there is one, else the mode.  With neither, the height is NaN and the tip (-1, -1, 0, 0): source 0.
+ * T4. The depth.  From a mode: z = depth[f][pym][pxm] as it is, 0 and 65535 included, as rule S7 takes it; source 1.  From a
+ *     vote, with zs = depth[f][pyv][pxv]: if zs is neither 0 nor 65535 and |zs - Z| <= z_tol, z = zs, source 2 (the tip is
+ *     seen, and the sensor knows its depth better than the regression does); else z = Z, source 3 (hidden, or in a hole).
+ * T5. The height.  Rule S7's arithmetic on (px, py, z): x = ((float)px - ppx) / fx and y alike in fp32, the point ((float)z * x,
+ *     (float)z * y, (float)z, 1) promoted to fp64, height = -(plane[8] * pt[0] + plane[9] * pt[1] + plane[10] * pt[2] + plane[11]
+ *     * pt[3]) summed from 0.0 in that order with the plane promoted to fp64.  A mode-sourced height is bit for bit what the
+ *     mode launch wrote.  tips_out[f][i] = (px, py, z, source).
+ * T6. Arguments.  A negative size, labels_reduce < 1, policy outside 0 .. 2, max_dist or z_tol outside 0 .. 65535,
+ *     heights_stride < n_ids, n_ids or num_classes of 0, n_joints outside 1 .. RDF_VOTES_MAX_JOINTS, dim_x or dim_y above 65535
+ *     or a misaligned pointer (8 bytes for means and heights_out, 4 for class_ids, tip_joints and plane, 2 for depth, 16 for
+ *     joints and tips_out) is RDF_ERR_BAD_ARG; n_img * n_ids >= 2^31 or n_img * dim_y * dim_x >= 2^31 RDF_ERR_TOO_LARGE; n_img
+ *     == 0 is a successful no-op; else a NULL pointer (tips_out excepted) is RDF_ERR_NULL_PTR.  A rejected call launches and
+ *     writes nothing.  An accepted call is one launch on the caller's stream, one lane per (frame, tip) on a capped grid that
+ *     strides over the pairs; nothing is read back.
+ */
+#define RDF_TIPS_FILL 0
+#define RDF_TIPS_GUARD 1
+#define RDF_TIPS_VOTES 2
+int rdf_labels_vote_tips(const double *means, int n_img, int num_classes, const int *class_ids, const int *tip_joints,
+                         int n_ids, const int32_t *joints, int n_joints, int flip_x, const uint16_t *depth, int dim_x,
+                         int dim_y, int labels_reduce, float fx, float fy, float ppx, float ppy, const float *plane,
+                         int policy, int max_dist, int z_tol, double *heights_out, int heights_stride,
+                         int32_t *tips_out, void *stream);
+
 int rdf_labels_abi_version(void);
 const char *rdf_labels_build_id(void);
 const char *rdf_labels_error_string(int code);
