@@ -32,6 +32,7 @@ from .refit import LeafRefitter  # noqa: F401
 from .rerender import SceneRerender  # noqa: F401
 from .score import Calibration, ConfidenceScorer, LabelScorer, Score  # noqa: F401
 from .session import BeatsSession  # noqa: F401
+from .shape import ShapeVoter  # noqa: F401
 from .soft_modes import WeightedModes  # noqa: F401
 from .stereo_sensor import StereoSensor  # noqa: F401
 from .util import MAX_UINT16  # noqa: F401
@@ -63,6 +64,6 @@ def install_reference_aliases(force=False):
 
 
 __all__ = ["DecisionTree", "DecisionForest", "LayeredDecisionForest", "DecisionTreeEvaluator", "DecisionTreeTrainer",
-           "GpuBuffer", "CalibratedPlane", "ColorLabeler", "RecordingConverter", "SceneRerender", "HandModel", "HandSceneRenderer", "StereoSensor", "PoseFitter", "LabelScorer", "Score", "ConfidenceScorer", "Calibration", "LeafRefitter", "ForestPruner", "VoteFitter", "VoteTable", "JointVoter", "FrameFrontEnd", "DepthPostFilter", "HandGrouping", "HandPipeline", "HandState", "BeatsSession", "WeightedModes", "HostFramesEvaluator",
+           "GpuBuffer", "CalibratedPlane", "ColorLabeler", "RecordingConverter", "SceneRerender", "HandModel", "HandSceneRenderer", "StereoSensor", "PoseFitter", "LabelScorer", "Score", "ConfidenceScorer", "Calibration", "LeafRefitter", "ForestPruner", "VoteFitter", "VoteTable", "JointVoter", "ShapeVoter", "FrameFrontEnd", "DepthPostFilter", "HandGrouping", "HandPipeline", "HandState", "BeatsSession", "WeightedModes", "HostFramesEvaluator",
            "DeviceArray", "HipRuntime", "MAX_UINT16", "RdfError", "device_ptr", "get_runtime", "set_runtime",
            "to_device", "host_mapped_array", "library_path", "synth", "install_reference_aliases"]

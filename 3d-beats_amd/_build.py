@@ -45,14 +45,16 @@ LIBRARIES = {lib.key: lib for lib in (
     # body is the mean shift's own: rdf_modes.hpp is a header of this library and of "hip", and a change to it rebuilds both;
     # and the joint votes, the fourth user of rdf_forest_ref.hpp's walk: offsets towards the joints summed per leaf slot, a vote
     # table made of them, the votes of every hand pixel cast into an accumulator per joint and the accumulator's mode; and the
-    # voted fingertips, which choose per tip between the mode's pixel and the vote's and take rdf_modes.hpp's height of it
+    # voted fingertips, which choose per tip between the mode's pixel and the vote's and take rdf_modes.hpp's height of it; and
+    # the hand's shape, the fifth user of the walk: every hand pixel's shares of its vote pooled per frame, and the held decision
     Library("labels", os.path.join(HERE, "csrc", "librdf_labels.so"),
             [os.path.join(HERE, "csrc", "labels_hip.hip"), os.path.join(HERE, "csrc", "rerender_hip.hip"),
              os.path.join(HERE, "csrc", "score_hip.hip"), os.path.join(HERE, "csrc", "hand_scene_hip.hip"),
              os.path.join(HERE, "csrc", "pose_fit_hip.hip"), os.path.join(HERE, "csrc", "stereo_sensor_hip.hip"),
              os.path.join(HERE, "csrc", "forest_refit_hip.hip"), os.path.join(HERE, "csrc", "forest_prune_hip.hip"),
              os.path.join(HERE, "csrc", "forest_posterior_hip.hip"), os.path.join(HERE, "csrc", "forest_votes_hip.hip"),
-             os.path.join(HERE, "csrc", "vote_tips_hip.hip"), os.path.join(HERE, "csrc", "soft_modes_hip.hip")],
+             os.path.join(HERE, "csrc", "vote_tips_hip.hip"), os.path.join(HERE, "csrc", "forest_shape_hip.hip"),
+             os.path.join(HERE, "csrc", "soft_modes_hip.hip")],
             [os.path.join(HERE, "..", "include", "rdf_labels.h"), os.path.join(HERE, "csrc", "rdf_kernel_util.hpp"),
              os.path.join(HERE, "csrc", "rdf_raster.hpp"), os.path.join(HERE, "csrc", "rdf_device.hpp"),
              os.path.join(HERE, "csrc", "rdf_modes.hpp"), os.path.join(HERE, "csrc", "rdf_forest_ref.hpp")], "rdf_labels_"),

@@ -253,6 +253,10 @@ BINDINGS = {
         "rdf_labels_vote_tips": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_int,
                                           _c_void_p, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _c_float, _c_void_p,
                                           _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p]),
+        "rdf_labels_shape_pool": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_void_p, _c_int,
+                                           _c_int, _c_float, _c_void_p, _c_void_p]),
+        "rdf_labels_shape_decide": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_void_p, _c_void_p,
+                                             _c_void_p]),
         "rdf_labels_abi_version": (_c_int, []),
         "rdf_labels_build_id": (ctypes.c_char_p, []),
         "rdf_labels_error_string": (ctypes.c_char_p, [_c_int]),

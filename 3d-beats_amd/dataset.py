@@ -22,6 +22,9 @@ from .joint_votes import DEFAULT_MAX_VAR
 # (rule V1 of include/rdf_labels.h), written by HandSceneRenderer.make_dataset(targets=True).  A directory without the file is
 # a plain dataset.
 TARGETS_FILE = 'targets.npy'
+# Not in the reference either: the hand shape of every frame of a shape dataset, int32 [num_images], written by
+# HandSceneRenderer.make_shape_dataset.
+SHAPES_FILE = 'shapes.npy'
 
 
 class DecisionTreeDatasetConfig:
@@ -160,6 +163,56 @@ def read_targets(dataset_dir, images):
     if idx.size and (idx.min() < 0 or idx.max() >= total):
         raise IndexError(f"images outside 0..{total - 1}")
     return np.ascontiguousarray(t[idx])
+
+
+def read_shapes(dataset_dir, images):
+    """The hand shapes of a shape dataset's images `images` (indices into the directory, e.g. a DecisionTreeDatasetConfig's
+    img_idxes, in that order): host int32 [len(images)], indices into the `shapes` the directory was made with
+    (HandSceneRenderer.make_shape_dataset); every hand pixel of image n carries the label 1 + shapes[n]."""
+    path = os.path.join(dataset_dir, SHAPES_FILE)
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"{dataset_dir} carries no hand shapes ({SHAPES_FILE}): write it with "
+                                "HandSceneRenderer.make_shape_dataset")
+    with open(os.path.join(dataset_dir, 'config.json')) as fh:
+        total = json.loads(fh.read())['num_images']
+    s = np.load(path)
+    if s.dtype != np.int32 or s.shape != (total,):
+        raise ValueError(f"{path}: int32 [{total}] expected, found {s.dtype} {list(s.shape)}")
+    idx = np.asarray(list(images), np.int64).reshape(-1)
+    if idx.size and (idx.min() < 0 or idx.max() >= total):
+        raise IndexError(f"images outside 0..{total - 1}")
+    return np.ascontiguousarray(s[idx])
+
+
+def score_shape_model(model_path, dataset_dir, num_images, labels_reduce=1, **voter_settings):
+    """A shape forest (train_forest on a make_shape_dataset directory) on `num_images` random images of a shape dataset,
+    frame by frame: ShapeVoter.pool and .decide on the device, one read of the rows.  Returns a dict: `confusion` int64
+    [C, C + 1], the frames by true class (1 + shape index; row 0 stays empty) and raw class, the last column the frames
+    without a shape (raw -1); `accuracy`, the share of frames whose pooled SOFT vote names the true class; `accuracy_hard`,
+    the same for the hard vote, the argmax of the pool's per-class counts of pixel labels (first greatest; a frame without a
+    voting pixel counts as wrong); `frames`; `raw` and `truth`, int64 [frames], raw as decided and truth as a class.
+    voter_settings: ShapeVoter's min_pixels and min_conf; `hold` plays no part, the held decision is not scored."""
+    from .decision_tree import DecisionForest
+    from .device import DeviceArray
+    from .shape import ShapeVoter
+    forest = DecisionForest.load(model_path)
+    ds = DecisionTreeDatasetConfig(dataset_dir, num_images=num_images, imgs_name='test')
+    n, h, w = ds.images_shape()
+    depth = DeviceArray((n, h, w), np.uint16)
+    ds.get_depth_block_cu(0, depth)
+    truth = read_shapes(dataset_dir, ds.img_idxes).astype(np.int64) + 1
+    voter = ShapeVoter(forest, (h, w), labels_reduce=labels_reduce, **voter_settings)
+    C = voter.C
+    pool_cu = voter.pool(depth)
+    raw = voter.decide(pool_cu).get()[:, 0].astype(np.int64)
+    pool = pool_cu.get()
+    hard = np.where(pool[:, 2 * C] > 0, np.argmax(pool[:, C:2 * C], axis=1), -1)
+    confusion = np.zeros((C, C + 1), np.int64)
+    for t, r in zip(truth.tolist(), raw.tolist()):
+        if 0 <= t < C:
+            confusion[t, C if r < 0 else r] += 1
+    return dict(confusion=confusion, accuracy=float(np.mean(raw == truth)) if n else float('nan'),
+                accuracy_hard=float(np.mean(hard == truth)) if n else float('nan'), frames=int(n), raw=raw, truth=truth)
 
 
 def evaluate_saved_model(model_path, dataset_dir, num_images, out_dir=None):

@@ -43,6 +43,18 @@ PALM_SIDES, PALM_RINGS, FINGER_SIDES, FINGER_RINGS = 12, 5, 8, 2
 # what sample_poses draws from, uniformly: (low, high); lengths in mm, angles in radians
 SAMPLE_RANGES = {"x": (-60., 60.), "y": (-110., -30.), "height": (60., 140.), "yaw": (-0.6, 0.6), "pitch": (-0.3, 0.2),
                  "roll": (-0.35, 0.35), "spread": (-0.12, 0.12), "flexion": (0., 0.6)}
+# Hand shapes, what shape_poses draws a finger's angles from: shape -> finger -> ((spread low, high), (flexion low, high)), the
+# flexion range for each of the finger's three joints.  An extended finger flexes at most 0.25 a joint, a curled one at least
+# 1.0 (three joints of 1.0 to 1.45 fold the tip back onto the palm); the thumb, which folds across the palm, curls less.
+_OUT, _CURLED, _THUMB_IN = ((-0.12, 0.12), (0., 0.25)), ((-0.05, 0.05), (1.0, 1.45)), ((-0.05, 0.05), (0.55, 0.9))
+SHAPES = {
+    "open":  {"thumb": _OUT, "index": _OUT, "middle": _OUT, "ring": _OUT, "pinky": _OUT},
+    "fist":  {"thumb": _THUMB_IN, "index": _CURLED, "middle": _CURLED, "ring": _CURLED, "pinky": _CURLED},
+    "point": {"thumb": _THUMB_IN, "index": _OUT, "middle": _CURLED, "ring": _CURLED, "pinky": _CURLED},
+    # thumb and index bent towards each other, the other three extended
+    "pinch": {"thumb": ((-0.3, -0.15), (0.35, 0.55)), "index": ((-0.05, 0.05), (0.5, 0.75)), "middle": _OUT, "ring": _OUT,
+              "pinky": _OUT},
+}
 REST_FLEXION = 0.25             # press_sequence: every joint of a resting finger
 PRESS_SPEED_MM = 4.             # press_sequence: the tip's descent per frame
 
@@ -182,6 +194,29 @@ class HandModel:
         rng.random((n, 26)) call, so the same seed gives the same poses.  The default ranges put the wrist below the middle
         of the view of a camera that looks down its plane space's -z (y = -110..-30 mm, so that the fingers cross the
         centre) at 60..140 mm above the table."""
+        return self._draw_poses(n, rng, ranges, None)
+
+    def shape_poses(self, shape, n, rng, ranges=None):
+        """sample_poses with every finger's spread and flexion ranges taken from SHAPES[shape] (a name, or a table entry of
+        its form): the wrist and the hand's angles come from SAMPLE_RANGES and `ranges` as they do there; one
+        rng.random((n, 26)) call, the same seed gives the same poses, and a mirrored model gives the mirror images."""
+        return self._draw_poses(n, rng, ranges, SHAPES[shape] if isinstance(shape, str) else shape)
+
+    def shape_dataset_poses(self, num_images, rng, shapes=tuple(SHAPES), ranges=None):
+        """The poses of a shape dataset (HandSceneRenderer.make_shape_dataset): frame n is of shape shapes[n % len(shapes)].
+        One shape_poses call per shape, in the order of `shapes`, for the frames of that shape.  Returns (poses float64
+        [num_images, 26], shape indices int32 [num_images])."""
+        shapes = tuple(shapes)
+        assert shapes and all(s in SHAPES for s in shapes), shapes
+        num_images = int(num_images)
+        index = (np.arange(num_images) % len(shapes)).astype(np.int32)
+        poses = np.empty((num_images, POSE_SIZE), np.float64)
+        for k, shape in enumerate(shapes):
+            at = np.flatnonzero(index == k)
+            poses[at] = self.shape_poses(shape, len(at), rng, ranges)
+        return poses, index
+
+    def _draw_poses(self, n, rng, ranges, fingers):
         r = dict(SAMPLE_RANGES)
         r.update(ranges or {})
         u = self.units_per_mm
@@ -192,8 +227,9 @@ class HandModel:
         for k, name in enumerate(("yaw", "pitch", "roll")):
             lo[3 + k], hi[3 + k] = r[name]
         for f in range(5):
-            lo[6 + 4 * f], hi[6 + 4 * f] = r["spread"]
-            lo[7 + 4 * f:10 + 4 * f], hi[7 + 4 * f:10 + 4 * f] = r["flexion"]
+            spread, flexion = (r["spread"], r["flexion"]) if fingers is None else fingers[FINGERS[f]]
+            lo[6 + 4 * f], hi[6 + 4 * f] = spread
+            lo[7 + 4 * f:10 + 4 * f], hi[7 + 4 * f:10 + 4 * f] = flexion
         poses = lo + (hi - lo) * rng.random((int(n), POSE_SIZE))
         if self.is_mirrored:
             poses[:, (0, 3, 5)] *= -1.         # the other hand's poses are the mirror images of this hand's

@@ -4,7 +4,8 @@ rigged hand in Blender for this (datagen/) and ships no recordings.
 
 `HandSceneRenderer.render` draws a batch of poses -- one hand (16 parts) or two (32: a right hand, then its mirror image) --
 into device depth and label images, two launches per chunk of `max_frames` on the current stream, nothing read back.
-`make_dataset` writes a directory that DecisionTreeDatasetConfig, train_forest and score_saved_model read as any other;
+`make_dataset` writes a directory that DecisionTreeDatasetConfig, train_forest and score_saved_model read as any other,
+`make_shape_dataset` one whose frames are labelled by the hand's shape (hand_model.SHAPES), for a shape.ShapeVoter's forest;
 `camera_sequence` gives raw frames with the table under the hand, the input of BeatsSession.run_sequence.  With `sensor=` (a
 StereoSensor) all three draw a clean left and a clean right frame and report what the stereo camera makes of them, in place of
 rule H's holes and noise.  The rasteriser's rules are in include/rdf_labels.h.
@@ -14,10 +15,12 @@ import os
 import numpy as np
 
 from . import _lib
-from .dataset import TARGETS_FILE, write_dataset
+from .dataset import SHAPES_FILE, TARGETS_FILE, write_dataset
 from .device import DeviceArray, device_ptr, get_runtime, to_device
-from .hand_model import N_PARTS, POSE_SIZE, HandModel
+from .hand_model import N_PARTS, POSE_SIZE, SHAPES, HandModel
 
+# make_shape_dataset: the colour of shape k's label, 1 + k (at most as many shapes as a ShapeVoter's forest has classes but 0)
+SHAPE_COLORS = tuple((40 + 14 * k, 250 - 13 * k, (97 * k) % 256, 255) for k in range(15))
 Z_NEAR, Z_FAR = 50., 50000.         # SceneRerender's planes
 FRAME_SEED_STEP = 0x9E3779B9        # rule H: frame n under seed s is frame 0 under seed s + n * this
 
@@ -200,6 +203,26 @@ class HandSceneRenderer:
         if targets:
             np.save(os.path.join(dataset_dir, TARGETS_FILE), self.fingertip_targets(poses, plane, left))
         return depth, lab
+
+    def make_shape_dataset(self, dataset_dir, num_images, seed, shapes=tuple(SHAPES), plane=None, ranges=None, hole_rate=0.,
+                           noise_amp=0, sensor=None):
+        """A training set for a SHAPE forest (shape.ShapeVoter): frame n shows one hand of shape shapes[n % len(shapes)]
+        (HandModel.shape_dataset_poses from `seed`), rendered as make_dataset renders, and every hand pixel of it carries the
+        label 1 + n % len(shapes), 0 elsewhere.  Written with dataset.write_dataset, one colour per shape, and `shapes.npy`,
+        int32 [N], the shape index of every frame (dataset.read_shapes); train_forest trains on the directory as on any
+        other.  Returns the host (depth, labels, shape indices)."""
+        shapes = tuple(shapes)
+        assert 1 <= len(shapes) <= len(SHAPE_COLORS), f"1 .. {len(SHAPE_COLORS)} shapes"
+        rng = np.random.default_rng(seed)
+        plane = look_down_plane(550. * self.model.units_per_mm) if plane is None else plane
+        poses, index = self.model.shape_dataset_poses(num_images, rng, shapes, ranges)
+        depth, lab = self.render(self.transforms(poses, plane), 'fine', None, 65535, int(seed) & 0xFFFFFFFF, hole_rate,
+                                 noise_amp, sensor=sensor)
+        depth, lab = depth.get(), lab.get()
+        lab = np.where(lab != 0, (1 + index)[:, None, None], 0).astype(np.uint16)
+        write_dataset(dataset_dir, depth, lab, {1 + k: SHAPE_COLORS[k] for k in range(len(shapes))})
+        np.save(os.path.join(dataset_dir, SHAPES_FILE), index)
+        return depth, lab, index
 
     def camera_sequence(self, poses, plane, left_poses=None, hole_rate=0., noise_amp=0, seed=0, labels='fine', labels_out=None,
                         sensor=None):

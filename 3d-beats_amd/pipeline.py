@@ -71,7 +71,7 @@ class HandPipeline:
     def __init__(self, layered_rdf, depth_dims, labels_reduce, eval_to_train_dim_ratio, mean_shift_rounds,
                  mean_shift_variances, fingertip_idxes, intrinsics, plane, depth_mm_level=0, fused_io=True,
                  hand_state=None, tip_first=0, soft_modes=False, joint_voter=None, tip_joints=None, tip_policy='fill',
-                 tip_max_dist=DEFAULT_TIP_MAX_DIST, tip_z_tol=DEFAULT_TIP_Z_TOL):
+                 tip_max_dist=DEFAULT_TIP_MAX_DIST, tip_z_tol=DEFAULT_TIP_Z_TOL, shape_voter=None):
         """depth_dims = (DIM_Y, DIM_X); intrinsics = (fx, fy, ppx, ppy) of the depth stream; plane = the calibrated
         plane's 4x4 matrix (calibrated_plane.plane) or a float32 device array of 16 elements that is read every frame
         (FrameFrontEnd.calibrated_plane.plane_cu: a recalibration then reaches the heights); fingertip_idxes = 1-based
@@ -92,8 +92,24 @@ class HandPipeline:
         tip_z_tol depth units of the voted depth, else the voted depth.  The defaults of tip_max_dist and tip_z_tol are
         the best of a sweep on stereo frames (DEFAULT_TIP_MAX_DIST, DEFAULT_TIP_Z_TOL above), not guesses.  `tips` /
         `tips_batch` then hold the device int32 rows (px, py, z, source) of the last frame / batch.  A voter that already
-        serves another pipeline is replaced by its sibling(), as the stack is.  None: nothing is allocated or launched."""
+        serves another pipeline is replaced by its sibling(), as the stack is.  None: nothing is allocated or launched.
+        shape_voter: a ShapeVoter built for depth_dims (needs fused_io; anything else is a ValueError).  Every frame it
+        classifies the frame the forest sees -- stencilled to the hand, mirrored for the left hand, so one shape forest trained
+        on right hands serves both -- with gate=None and the pipeline's scale factor, behind the stack's launches; `shape`
+        (device int32 [4] = raw, conf, held, changed) / `shape_batch` ([n, 4]) hold the last frame's / batch's rows, and the
+        held shape lives in the voter's device state.  Means, heights, tips and the hand state are what they are without
+        it.  A voter that already serves another pipeline is replaced by its sibling().  None: nothing is allocated or
+        launched."""
         n_tips = len(fingertip_idxes)
+        if shape_voter is not None:
+            from .shape import ShapeVoter
+            if not isinstance(shape_voter, ShapeVoter):
+                raise ValueError(f"shape_voter must be a ShapeVoter, not {type(shape_voter).__name__}")
+            if (shape_voter.DIM_Y, shape_voter.DIM_X) != (int(depth_dims[0]), int(depth_dims[1])):
+                raise ValueError(f"shape_voter was built for frames of {(shape_voter.DIM_Y, shape_voter.DIM_X)}, not "
+                                 f"{(int(depth_dims[0]), int(depth_dims[1]))}")
+            if not fused_io:
+                raise ValueError("shape_voter needs fused_io=True")
         if joint_voter is not None:
             from .joint_votes import JointVoter
             if not isinstance(joint_voter, JointVoter):
@@ -184,6 +200,18 @@ class HandPipeline:
             self._tip_joints = DeviceArray((n_tips,), np.int32).set(np.asarray(tip_joints, np.int32))
             self._joints = DeviceArray((1, joint_voter.J, 4), np.int32)
             self.tips = DeviceArray((n_tips, 4), np.int32)
+        self.shape_voter, self.shape, self.shape_batch = None, None, None
+        if shape_voter is not None:
+            owner = getattr(shape_voter, "_pipeline_owner", None)
+            if owner is not None and owner() is not None:
+                shape_voter = shape_voter.sibling()
+            shape_voter._pipeline_owner = weakref.ref(self)
+            self.shape_voter = shape_voter
+            self.shape = DeviceArray((4,), np.int32)
+
+    def _classify_shape(self, depth_2, out):
+        """The shape voter's launches for the frames the forest sees (background 65535: gate=None takes the hand's pixels)."""
+        self.shape_voter.classify(depth_2, gate=None, scale_factor=self.EVAL_TO_TRAIN_DIM_RATIO, out=out)
 
     def _vote(self, depth_2, joints):
         """The voter's launches for the frames the forest sees (depth_2 [n, DIM_Y, DIM_X], background 65535: gate=None takes
@@ -224,7 +252,8 @@ class HandPipeline:
         for the largest n seen.  With soft_modes the third call is two: the stack's composite_weights_batch into
         `weights_batch[f]`, then rdf_labels_weighted_modes for the n frames.  With a joint_voter its cast runs on the prepared
         frames (in chunks of the voter's max_frames, `joints_batch[f]`) and rdf_labels_vote_tips follows the mode launch:
-        the fused heights land in the same rows, the tips in `tips_batch[f]`."""
+        the fused heights land in the same rows, the tips in `tips_batch[f]`.  With a shape_voter its classify runs on the
+        prepared frames, in time order, into `shape_batch[f]`."""
         if not self.fused_io:
             raise ValueError("enqueue_batch needs fused_io=True")
         depth_images, group_images, height_depth = (a.cu() if hasattr(a, "cu") else a
@@ -242,6 +271,8 @@ class HandPipeline:
             if self.joint_voter is not None:
                 self._joints_batch = DeviceArray((n, self.joint_voter.J, 4), np.int32)
                 self._tips_batch = DeviceArray((n, len(self.fingertip_idxes), 4), np.int32)
+            if self.shape_voter is not None:
+                self._shape_batch = DeviceArray((n, 4), np.int32)
             self._batch_capacity = n
         dims = np.array([self.DIM_X, self.DIM_Y], dtype=np.int32)
         depth_2, labels = self._depth_batch[:n], self._labels_batch[:n]
@@ -252,6 +283,9 @@ class HandPipeline:
         if self.joint_voter is not None:
             self.joints_batch, self.tips_batch = self._joints_batch[:n], self._tips_batch[:n]
             self._vote(depth_2, self.joints_batch)
+        if self.shape_voter is not None:
+            self.shape_batch = self._shape_batch[:n]
+            self._classify_shape(depth_2, self.shape_batch)
         if self.soft_modes:
             self.weights_batch = self._weights_batch[:n]
             self.layered_rdf.composite_weights_batch(n, self.weights_batch, flip_x)
@@ -292,11 +326,13 @@ class HandPipeline:
         when one differs -- after
         `LeafRefitter.apply`, a `forest_cu.set(...)` or a re-pack: capture again.  (A bare `replay.graph.replay()` is
         not covered.)  A stack with `min_conf` set (the gated, step-by-step path) is not captured, and neither is a pipeline with
-        a joint_voter: NotImplementedError, before anything is recorded."""
+        a joint_voter or a shape_voter: NotImplementedError, before anything is recorded."""
         if getattr(self.layered_rdf, "min_conf", None) is not None:
             raise NotImplementedError("HandPipeline.capture: the stack has min_conf set; capture of the gated path is not built")
         if self.joint_voter is not None:
             raise NotImplementedError("HandPipeline.capture: capture of the joint voter's cast is not built")
+        if self.shape_voter is not None:
+            raise NotImplementedError("HandPipeline.capture: capture of the shape voter's launches is not built")
         import torch
         scale = self.EVAL_TO_TRAIN_DIM_RATIO
         side = torch.cuda.Stream()
@@ -401,6 +437,8 @@ class HandPipeline:
                                       self.labels_image_rgba)
             if self.joint_voter is not None:
                 self._vote(self.depth_image_2.cu(), self._joints)
+            if self.shape_voter is not None:
+                self._classify_shape(self.depth_image_2.cu(), self.shape)
         else:
             # the reference's sequence, kernel for kernel (3d_bz.py:396-456)
             self.depth_image_group.cu().fill(0)

@@ -40,7 +40,7 @@ class BeatsSession:
                  fingertip_thresholds=(200., 160., 160., 160., 160.), first_notes=(36, 41), max_frames=8,
                  num_random_guesses=25000, seed=None, fused_io=True, capacity=4096, post_filter=None, soft_modes=False,
                  joint_votes=None, tip_joints=None, tip_policy='fill', tip_max_dist=DEFAULT_TIP_MAX_DIST,
-                 tip_z_tol=DEFAULT_TIP_Z_TOL):
+                 tip_z_tol=DEFAULT_TIP_Z_TOL, shapes=None, on_shape_fn=None):
         """layered_rdf: a LayeredDecisionForest built for depth_dims = (DIM_Y, DIM_X) and labels_reduce; intrinsics = (focal,
         ppx, ppy) of the depth camera.  The other defaults are the app's (3d_bz.py:49-124); scale_factor = DIM_X / 848 when
         None.  max_frames = the batch of run_sequence's front end and grouping.  post_filter: a DepthPostFilter of the same
@@ -52,7 +52,24 @@ class BeatsSession:
         JointVoter's keyword arguments (labels_reduce, cell_shift, box, min_support).  One JointVoter per hand is built for
         depth_dims with max_frames the session's and handed to the hand's pipeline with tip_joints, tip_policy, tip_max_dist
         and tip_z_tol (HandPipeline's; the left hand's frame is mirrored, so both hands use the same joints): tick and both
-        kinds of run_sequence then step the notes from the voted fingertips' heights.  None, the default, changes nothing."""
+        kinds of run_sequence then step the notes from the voted fingertips' heights.  None, the default, changes nothing.
+        shapes: (forest,) or (forest, settings) -- a shape forest (hand_scene.make_shape_dataset, train_forest) and a dict of
+        ShapeVoter's keyword arguments (labels_reduce, min_pixels, min_conf, hold, release, names).  One ShapeVoter per hand is
+        built for depth_dims with max_frames the session's and handed to the hand's pipeline: tick and both kinds of
+        run_sequence classify every frame of each hand, and the held shapes live on the device from call to call.
+        on_shape_fn(hand, held): called by poll() -- hand 0 is the right hand, 1 the left -- see poll.  None, the default,
+        changes nothing."""
+        if shapes is not None:        # (refused before anything is allocated)
+            from .shape import SETTINGS, ShapeVoter
+            if not isinstance(shapes, (tuple, list)) or not 1 <= len(shapes) <= 2:
+                raise ValueError("shapes is (forest,) or (forest, settings)")
+            shape_settings = dict(shapes[1]) if len(shapes) == 2 else {}
+            if "max_frames" in shape_settings:
+                raise ValueError("shapes: the voters' max_frames is the session's")
+            if set(shape_settings) - set(SETTINGS):
+                raise ValueError(f"shapes: unknown settings {sorted(set(shape_settings) - set(SETTINGS))}")
+            if not fused_io:
+                raise ValueError("shapes needs fused_io=True")
         self._rt = get_runtime()
         self.DIM_Y, self.DIM_X = int(depth_dims[0]), int(depth_dims[1])
         self.max_frames = int(max_frames)
@@ -82,10 +99,17 @@ class BeatsSession:
             voters = tuple(JointVoter(joint_votes[0], joint_votes[1], (self.DIM_Y, self.DIM_X), max_frames=self.max_frames,
                                       **settings) for _ in range(2))
             tips = dict(tip_joints=tip_joints, tip_policy=tip_policy, tip_max_dist=tip_max_dist, tip_z_tol=tip_z_tol)
+        shape_voters = (None, None)
+        if shapes is not None:
+            shape_voters = tuple(ShapeVoter(shapes[0], (self.DIM_Y, self.DIM_X), max_frames=self.max_frames, **shape_settings)
+                                 for _ in range(2))
+        self.on_shape_fn, self.last_shapes, self._delivered_shapes = on_shape_fn, None, [-1, -1]
         self.right = HandPipeline(layered_rdf, *args, depth_mm_level=depth_mm_level, fused_io=fused_io,
-                                  hand_state=self.hand_state, tip_first=0, soft_modes=soft_modes, joint_voter=voters[0], **tips)
+                                  hand_state=self.hand_state, tip_first=0, soft_modes=soft_modes, joint_voter=voters[0],
+                                  shape_voter=shape_voters[0], **tips)
         self.left = HandPipeline(layered_rdf, *args, depth_mm_level=depth_mm_level, fused_io=fused_io,
-                                 hand_state=self.hand_state, tip_first=n, soft_modes=soft_modes, joint_voter=voters[1], **tips)
+                                 hand_state=self.hand_state, tip_first=n, soft_modes=soft_modes, joint_voter=voters[1],
+                                 shape_voter=shape_voters[1], **tips)
         self.n_tips = 2 * n
         hm, wm = self.grouping.depth_mm_dims
         self._raw = DeviceArray((self.max_frames, self.DIM_Y, self.DIM_X), np.uint16)
@@ -136,8 +160,19 @@ class BeatsSession:
         self.left.enqueue(self._clean_f[0], self._groups_f[0], 2, True, height_depth=raw)
 
     def poll(self):
-        """HandState.poll(): waits for the stream and delivers the events since the last poll."""
-        return self.hand_state.poll()
+        """HandState.poll(): waits for the stream and delivers the events since the last poll.  With `shapes` and an
+        on_shape_fn it then reads each hand's held shape (16 bytes a hand) and calls on_shape_fn(hand, held) for a hand whose
+        held shape differs from the one last delivered (-1, no shape, at the start).  Only the latest state is delivered:
+        changes between two polls collapse -- a shape that came and went between them is never seen, and one that changed
+        twice arrives as one call.  The per-frame rows are in `last_shapes` after run_sequence."""
+        events = self.hand_state.poll()
+        if getattr(self, "on_shape_fn", None) is not None and getattr(self.right, "shape_voter", None) is not None:
+            for hand, pipe in enumerate((self.right, self.left)):
+                held = int(pipe.shape_voter.state.get()[0])
+                if held != self._delivered_shapes[hand]:
+                    self._delivered_shapes[hand] = held
+                    self.on_shape_fn(hand, held)
+        return events
 
     # -- offline --
     def run_sequence(self, frames, batched=False):
@@ -149,13 +184,21 @@ class BeatsSession:
         batched=True (needs fused_io): the per-hand chains take the whole block too -- HandPipeline.enqueue_batch for the
         right hand writes columns 0-4 of the block's log rows, for the left hand columns 5-9, and ONE note step advances
         all ten fingertips over the block's frames.  Same events, heights and state, bit for bit; a prepare, one launch a
-        forest layer, a composite and a mean shift per hand and block instead of per hand and frame, and no copies."""
+        forest layer, a composite and a mean shift per hand and block instead of per hand and frame, and no copies.
+        With `shapes` the rows (raw, conf, held, changed) of every frame and hand are logged on the device too and left in
+        `last_shapes`, host int32 [F, 2, 4] (right hand first), read once after the last frame: the same bytes for both
+        kinds of run, and the voters' state runs on from call to call."""
         if batched and not (self.right.fused_io and self.left.fused_io):
             raise ValueError("run_sequence(batched=True) needs a session built with fused_io=True")
         F = int(frames.shape[0])
         n = self.n_tips // 2
         log = DeviceArray((max(F, 1), self.n_tips), np.float64)
         lib, stream = self._rt.lib, self._rt.stream
+        shape_log = DeviceArray((2, max(F, 1), 4), np.int32) if getattr(self.right, "shape_voter", None) is not None else None
+
+        def log_shapes(hand, rows, first, count):
+            rc = lib.rdf_memcpy_device_async(shape_log.ptr + (hand * max(F, 1) + first) * 16, rows.ptr, count * 16, stream())
+            _lib.check(lib, rc, "rdf_memcpy_device_async")
         for a in range(0, F, self.max_frames):
             b = min(F - a, self.max_frames)
             raw = self._camera_frames(frames[a:a + b], b)
@@ -167,6 +210,9 @@ class BeatsSession:
                 self.right.enqueue_batch(self._clean[:b], self._groups[:b], 1, False, raw, row, self.n_tips)
                 self.left.enqueue_batch(self._clean[:b], self._groups[:b], 2, True, raw, row + n * 8, self.n_tips)
                 self.hand_state.step_device(row, 0, self.n_tips, n_frames=b)
+                if shape_log is not None:
+                    log_shapes(0, self.right.shape_batch, a, b)
+                    log_shapes(1, self.left.shape_batch, a, b)
                 continue
             for i in range(b):
                 raw_i = _Frame(raw[i])
@@ -176,5 +222,9 @@ class BeatsSession:
                     rc = lib.rdf_memcpy_device_async(log.ptr + ((a + i) * self.n_tips + pipe.tip_first) * 8, pipe.heights_ptr,
                                                      n * 8, stream())
                     _lib.check(lib, rc, "rdf_memcpy_device_async")
+                    if shape_log is not None:
+                        log_shapes(0 if pipe is self.right else 1, pipe.shape, a + i, 1)
         events = self.poll()
+        if shape_log is not None:
+            self.last_shapes = np.ascontiguousarray(shape_log.get()[:, :F].transpose(1, 0, 2))
         return events, log.get()[:F]

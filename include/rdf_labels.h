@@ -799,6 +799,63 @@ int rdf_labels_votes_cast(const uint16_t *depth, int n_img, int dim_x, int dim_y
                           void *stream);
 
 /*
+ * The hand's shape: the forest's per-pixel votes pooled over a frame.  Every consumer above is per pixel or per joint; here the
+ * leaf distributions a hand pixel reaches vote for a class of the WHOLE frame -- with a forest trained on frames labelled by
+ * hand shape (open, fist, ...), the shape classification forest of Keskin et al. -- the votes of a frame are pooled, and the
+ * pooled vote names the shape.  rdf_labels_shape_pool pools; rdf_labels_shape_decide turns a sequence of pooled votes into a
+ * decision that is stable from frame to frame.  The reference has no counterpart; the rules below are this library's own,
+ * tests/shape_numpy.py restates them, and the kernels match that byte for byte: a pixel's sums are made in a stated order and
+ * everything added across pixels is an integer, so no result depends on the order in which pixels are visited.
+ *
+ *   forest  float32 [T][N][E], the reference layout.  1 <= T, 1 <= D <= 30, 1 <= C <= RDF_POSTERIOR_MAX_CLASSES.
+ *   depth   uint16 [n_img][dim_y][dim_x];  filter uint16 [n_img][Hl][Wl] with r = labels_reduce, Hl = dim_y / r, Wl = dim_x / r.
+ *   pool    uint64 [n_img][2 C + 2], 8-byte aligned: C soft sums, C hard votes, voting pixels, dead pixels.
+ *   state   int32 [4] = (held, candidate, run, miss); a fresh state is (-1, -1, 0, 0).
+ *   out     int32 [n_frames][4] = (raw, conf, held, changed).
+ *
+ * G1. Pixels: exactly rule Q1.  Label pixel (x, y) of image i reads depth pixel (x * r, y * r); the filter is tested first
+ *     (filter_class != -1 and filter[i][y][x] != filter_class: skipped), then the pixel's own depth (0 or 65535: skipped).  A
+ *     skipped pixel adds nothing to any word.
+ * G2. Sums: exactly rule Q2 (rule R2's walk, acc fp32, trees in index order, the leaf slot's PDF added class by class, a walk
+ *     that falls off adds nothing).  S is rule Q4's fp32 sum of acc in class order, label rule Q3's argmax.
+ * G3. Shares.  If S > 0: q[c] = min(max(floor((acc[c] / S) * 65535.0f), 0), 65535) for every c < C -- rule Q4's expression (one
+ *     IEEE divide, one multiply, rule R2's floor: saturating, NaN -> 0) per class.  Otherwise (S is 0, negative or NaN) the
+ *     pixel is DEAD.
+ * G4. Pool.  A pixel with S > 0: pool[i][c] += q[c] for every c, pool[i][C + label] += 1, pool[i][2 C] += 1.  A dead pixel:
+ *     pool[i][2 C + 1] += 1.  The call ADDS; the caller zeroes.  Everything added is an integer: the row is the same bytes in
+ *     any visiting order.
+ * G5. Arguments of rdf_labels_shape_pool.  T < 1, D outside 1..30, C outside 1..RDF_POSTERIOR_MAX_CLASSES, r < 1, a negative
+ *     dimension, filter_class outside -1..65535 or a misaligned pointer (2 bytes for depth and filter, 4 for forest, 8 for
+ *     pool) is RDF_ERR_BAD_ARG; n_img * dim_y * dim_x >= 2^31 RDF_ERR_TOO_LARGE; zero label pixels is a successful no-op; else
+ *     a NULL depth, forest or pool, or a NULL filter with filter_class != -1, is RDF_ERR_NULL_PTR.  A rejected call launches
+ *     nothing and leaves pool untouched.  An accepted call is one launch on the caller's stream, nothing read back: one lane
+ *     per label pixel, a wave leaves at once when none of its 64 pixels is evaluated, the sums stay in registers; the lanes of
+ *     a wave that belong to one image sum their shares and counts across the wave, and lane w adds word w of the row, if it is
+ *     not zero, with one 64-bit integer atomic (a wave that straddles two images does so once per image).  No
+ *     floating-point atomics.
+ * G6. Raw (rdf_labels_shape_decide), per frame f:  total = the sum over c < C of pool[f][c].  If pool[f][2 C] < min_pixels or
+ *     total == 0: raw = -1, conf = 0.  Else raw = the first class with the greatest soft sum (best = 0; for c ascending,
+ *     pool[f][c] > pool[f][best] replaces best: rule Q3's tie rule) and conf = floordiv(pool[f][raw] * 65535, total) in 64-bit
+ *     integers (below 2^63 for a frame of fewer than 2^31 pixels pooled once).
+ * G7. Hold, frames in index order.  valid = raw != -1 and conf >= min_conf.  Not valid: candidate = -1, run = 0, miss += 1
+ *     (it stays at 2^31 - 1); if release > 0, miss >= release and held != -1: held = -1, changed = 1.  Valid: miss = 0; if raw
+ *     == held: candidate = -1, run = 0; else if raw == candidate, run += 1, else candidate = raw, run = 1; then if run >=
+ *     hold: held = raw, candidate = -1, run = 0, changed = 1.  changed is 0 otherwise.  out[f] = (raw, conf, held, changed)
+ *     with held as it is AFTER frame f.  state is read at the start of the call and written at its end: two calls over frames
+ *     [0, a) and [a, n) equal one call over [0, n).
+ * G8. Arguments of rdf_labels_shape_decide.  n_frames < 0, C outside 1..RDF_POSTERIOR_MAX_CLASSES, min_pixels < 0, min_conf
+ *     outside 0..65535, hold < 1, release < 0 or a misaligned pointer (8 bytes for pool, 4 for state and out) is
+ *     RDF_ERR_BAD_ARG; n_frames == 0 is a successful no-op; else a NULL pointer is RDF_ERR_NULL_PTR.  A rejected call launches
+ *     nothing and leaves state and out untouched.  An accepted call is one launch of one lane on the caller's stream -- the
+ *     frames are a sequence, and few -- and reads nothing back.  Neither call needs a workspace.
+ */
+int rdf_labels_shape_pool(const uint16_t *depth, int n_img, int dim_x, int dim_y, const float *forest, int n_trees, int max_depth,
+                          int n_classes, const uint16_t *filter, int filter_class, int labels_reduce, float scale_factor,
+                          uint64_t *pool, void *stream);
+int rdf_labels_shape_decide(const uint64_t *pool, int n_frames, int n_classes, int min_pixels, int min_conf, int hold,
+                            int release, int32_t *state, int32_t *out, void *stream);
+
+/*
  * Voted fingertips: the label route and the joint votes joined.  rdf_labels_vote_tips runs behind the mode launch of a hand's
  * chain (rdf_mean_shift_heights, rdf_mean_shift_heights_batch or rdf_labels_weighted_modes) and behind rdf_labels_votes_cast:
  * per frame and fingertip it chooses between the mode of the tip's class and the voted position of the tip's joint, finds a
